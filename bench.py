@@ -1,6 +1,13 @@
 """bench.py — FairyGen animation hot path on MI355X: decoded frames/sec and sec/clip.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            (N>1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]      (N>1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the clip and prints the result line.  --full adds what the headline does not need:
+`roofline` (HIP events around the attention, conv and GEMM launches of the timed clip) and `cpu_baseline` (the CPU oracle
+timed on a sample of the workload, skipped with --no-cpu-baseline).  --dump-outputs DIR writes, after the timed clip, what
+it computed as float32 .npy files: DIR/latents.npy (the denoised latents) and DIR/video.npy (the decoded video; above
+DUMP_MAX_ELEMENTS elements, DIR/video_sample.npy holds its values at a fixed, seeded set of flat indices instead).  All
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json metric / configs[2]): Wan2.2-TI2V-5B, 704x1280x121, TI2V (first latent frame pinned),
 CFG 5.0, sigma shift 5.0, merged rank-32 motion LoRA fused at load, random-init bf16 weights with the reference's
@@ -11,7 +18,7 @@ inference.py's tiled=True unless --untiled), inputs resident in HBM; value = fra
 is the headline configuration (BASELINE.json: "@ 50 steps"); ms_per_step = t_clip / K (decode amortised).  The `metric`
 string names the K that was actually run; whatever K the caller passes, config.frames_per_s_at_50_steps carries the
 BASELINE metric: measured directly when K = 50, otherwise derived as 121 / (50 x measured denoise step + measured decode)
-and labelled so.  `roofline` describes the dominant kernel (self-attention) and lists, under "kernels", the other MFMA
+and labelled so.  `roofline` (--full) describes the dominant kernel (self-attention) and lists, under "kernels", the other MFMA
 consumers of the clip measured with HIP events on the launch stream: the VAE conv kernels (MFMA fraction and algorithmic
 HBM GB/s of the decode) and the hipBLASLt GEMMs of the DiT blocks.
 N > 1 ("strong" scaling: one clip, total work fixed): world = cfg_parallel x sp (fairygen_amd/sequence_parallel.py):
@@ -41,11 +48,26 @@ PEAK_FP8_TFLOPS = 5000.0       # dense fp8 MFMA (block-scaled f8f6f4 form), same
 # separate --pmc FETCH_SIZE / WRITE_SIZE passes, KB units, gfx950 x2 correction on FETCH_SIZE), keyed by (Nq, Nkv, H).
 # PMC collection cannot run inside the timed bench; other shapes report null.
 PMC_HBM_BYTES_PER_LAUNCH = {(27280, 27280, 24): 2.110e9}
+# --dump-outputs: largest array written whole (float32, 24 MiB); the headline latents (5.2 M elements) fit, the video is sampled
+DUMP_MAX_ELEMENTS = 6 * 2 ** 20
 
 
 def seeded(shape, seed, dtype=torch.bfloat16):
     g = torch.Generator("cpu").manual_seed(seed)
     return torch.randn(shape, generator=g, dtype=torch.float32).to(dtype)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor as out_dir/<name>.npy in float32; one of more than DUMP_MAX_ELEMENTS elements as
+    out_dir/<name>_sample.npy: its values at DUMP_MAX_ELEMENTS flat indices drawn from a fixed seed, in ascending order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            g = torch.Generator("cpu").manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMENTS,), generator=g).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def build_pipeline(args, device):
@@ -282,7 +304,11 @@ def main():
     ap.add_argument("--untiled", action="store_true", help="single_decode instead of the reference's tiled=True decode")
     ap.add_argument("--no-lora", action="store_true")
     ap.add_argument("--layers", type=int, default=0, help="debug: fewer DiT layers (reported in config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (HIP events around the kernels) and cpu_baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed clip, write its latents and (sampled) video as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--cpu-tokens", type=int, default=0, help="cpu_baseline sample: DiT block token count (0 = the real N, no scaling)")
     ap.add_argument("--skip-vae", action="store_true", help="debug: denoise loop only (reported in config)")
     ap.add_argument("--gelu-epilogue", type=int, default=1, help="0: separate GELU kernel after ffn.0 instead of the GEMM epilogue")
@@ -392,8 +418,9 @@ def main():
             if pipe.parallel is not None and pipe.parallel.world.active:      # first-use set-up of the tile broadcast stays untimed
                 pipe.parallel.world.broadcast(torch.zeros(1024, dtype=torch.bfloat16, device=device), src=0)
         torch.cuda.synchronize()
-        timer = KernelTimer()
-        timer.install()
+        timer = KernelTimer() if args.full else None
+        if timer is not None:
+            timer.install()
         if distributed:
             barrier()
         torch.cuda.synchronize()
@@ -404,11 +431,14 @@ def main():
             barrier()
         torch.cuda.synchronize()
         t_clip = time.perf_counter() - t0
-        timer.uninstall()
+        if timer is not None:
+            timer.uninstall()
     t_clip = sync_max(t_clip)
 
     if rank == 0:
-        st = timer.self_attention_stats()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"latents": latents} if video is None else {"latents": latents, "video": video})
+        st = timer.self_attention_stats() if timer is not None else None
         roofline = None
         if st:
             roofline = {"bound": "mfma", "kernel": "attn_fwd_w4_kernel (fg_attn_fwd_bf16, self-attention launches: main kernel + split-KV merge)",
@@ -441,8 +471,9 @@ def main():
                                                                     if rehearsal else "")) if pipe.parallel is not None else
                                       ("single" + (" (1-rank RCCL process group: barrier + MAX all-reduce)" if distributed else "")),
                        "weights": "random-init bf16, reference key/shape set"},
-            "roofline": roofline,
         }
+        if args.full:
+            line["roofline"] = roofline
         from fairygen_amd import wan_video as _wv, wan_video_dit as _wd
         line["config"]["gelu"] = ("gemm_p_kernel epilogue (mode 4)" if _wd.GEMM_BACKEND == "all" and args.linear_dtype == "bf16" else
                                   "fused into ffn.2's row quantisation" if args.linear_dtype == "fp8" else
@@ -466,7 +497,7 @@ def main():
             line["config"]["DEBUG_num_layers"] = args.layers
         if args.skip_vae:
             line["config"]["DEBUG_skip_vae"] = True
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, n_tokens, F_, args.steps, (lat_shape[2], lat_shape[3] // 2, lat_shape[4] // 2))
         print(json.dumps(line))
     if distributed:

@@ -412,7 +412,7 @@ def test_fullwidth_vae_decoder_small_latent_vs_oracle():
     assert cos(out, ref32) > 0.999
 
 
-def test_pipeline_call_end_to_end(tmp_path, tiny_vae):
+def test_pipeline_call_end_to_end(tmp_path, tiny_vae, monkeypatch):
     """from_pretrained(ModelConfig(path=...)) -> load_lora -> pipe(...) -> frames, through the reference's call
     surface, on tiny synthetic checkpoints registered under their own key hashes."""
     from fairygen_amd import ModelConfig, WanVideoPipeline, loader
@@ -421,6 +421,8 @@ def test_pipeline_call_end_to_end(tmp_path, tiny_vae):
     vsd = synthetic.random_state_dict(synthetic.vae_shapes(dec_dim=32, dim=32, with_prefix=False), seed=1234)
     dpath = synthetic.save_checkpoint(dsd, str(tmp_path / "dit.safetensors"))
     vpath = synthetic.save_checkpoint(vsd, str(tmp_path / "vae.safetensors"))
+    # registry and module entries are undone after the test: the host-logic tests expect these seeded checkpoints to be unknown
+    monkeypatch.setattr(loader, "MODEL_CONFIGS", list(loader.MODEL_CONFIGS))
     loader.register_model_config({"model_hash": loader.hash_model_file(dpath), "model_name": "wan_video_dit",
                                   "model_class": "fairygen_amd.wan_video_dit.WanModel", "extra_kwargs": cfg})
     loader.register_model_config({"model_hash": loader.hash_model_file(vpath), "model_name": "wan_video_vae",
@@ -430,7 +432,7 @@ def test_pipeline_call_end_to_end(tmp_path, tiny_vae):
     from fairygen_amd.wan_video_vae import WanVideoVAE38
     mod = types.ModuleType("tests_tiny_vae")
     mod.TinyVAE = lambda: WanVideoVAE38(dim=32, dec_dim=32)
-    sys.modules["tests_tiny_vae"] = mod
+    monkeypatch.setitem(sys.modules, "tests_tiny_vae", mod)
     pipe = WanVideoPipeline.from_pretrained(torch_dtype=torch.bfloat16, device="cuda",
                                             model_configs=[ModelConfig(path=dpath), ModelConfig(path=vpath)])
     lora = synthetic.random_lora(synthetic.dit_shapes(cfg), rank=4, seed=4321)

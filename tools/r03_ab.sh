@@ -6,11 +6,11 @@ mkdir -p $O
 cd $R
 for rep in 1 2; do
   for be in all fused; do
-    FAIRYGEN_GEMM=$be timeout -k 10 300 python bench.py --steps 6 --warmup 1 --no-cpu-baseline > $O/r03_ab_${be}_$rep.json 2> $O/r03_ab_${be}_$rep.err || exit 1
+    FAIRYGEN_GEMM=$be timeout -k 10 300 python bench.py --full --steps 6 --warmup 1 --no-cpu-baseline > $O/r03_ab_${be}_$rep.json 2> $O/r03_ab_${be}_$rep.err || exit 1
   done
 done
 for be in own lib; do
-  FAIRYGEN_FP8_GEMM=$be timeout -k 10 300 python bench.py --steps 6 --warmup 1 --no-cpu-baseline --linear-dtype fp8 > $O/r03_ab_fp8_${be}.json 2> $O/r03_ab_fp8_${be}.err || exit 1
+  FAIRYGEN_FP8_GEMM=$be timeout -k 10 300 python bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --linear-dtype fp8 > $O/r03_ab_fp8_${be}.json 2> $O/r03_ab_fp8_${be}.err || exit 1
 done
 python - <<'PY'
 import json, glob, os
