@@ -306,7 +306,7 @@ int fg_dupup3d_add_bf16(const void* x, const void* main_path, void* out, int T, 
     FG_CHECK_ARG(T > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout % 8 == 0 && (ft == 1 || ft == 2) && (fs == 1 || fs == 2),
                  "fg_dupup3d_add_bf16: bad sizes");
     FG_CHECK_ARG((Cout * ft * fs * fs) % Cin == 0, "fg_dupup3d_add_bf16: out_channels*factor must be divisible by in_channels");
-    FG_CHECK_ARG(FG_ALIGNED16(main_path) && FG_ALIGNED16(out), "fg_dupup3d_add_bf16: misaligned pointer");
+    FG_CHECK_ARG(FG_ALIGNED16(x) && FG_ALIGNED16(main_path) && FG_ALIGNED16(out), "fg_dupup3d_add_bf16: misaligned pointer");
     const int drop = first_chunk ? ft - 1 : 0;
     const int To = T * ft - drop, Ho = H * fs, Wo = W * fs, repeats = Cout * ft * fs * fs / Cin;
     if (To <= 0) return FG_OK;

@@ -197,8 +197,9 @@ class VideoVAE38_(nn.Module):
         self._conv_states = None
         self._down_cache = {}
         self.z_dim = z_dim
-        # latent frames per decoder call after the first (1 = the reference's chunking; identical arithmetic per output for any value).  8 is what
-        # the conv kernel's 32-bit offsets allow at the (30, 52) tile; measured on it: 4 -> 808 ms, 6 -> 790, 8 -> 786 (fewer, larger launches)
+        # latent frames per decoder call after the first (1 = the reference's chunking; bit-identical output for any value, tested with 1 / 3 / 8
+        # by test_tiny_vae_decode_group_invariance and at the (30, 52) tile by test_fullwidth_vae_decode_group_invariance_at_bench_tile).  8 is
+        # what the conv kernel's 32-bit offsets allow at the (30, 52) tile; measured on it: 4 -> 808 ms, 6 -> 790, 8 -> 786 (fewer, larger launches)
         self.max_chunk_group = 8
 
     # ------------------------------------------------------------------ weight preparation
@@ -313,8 +314,10 @@ class VideoVAE38_(nn.Module):
         video = torch.empty((3, frames, 16 * h, 16 * w), dtype=z.dtype, device=z.device)
         # The reference decodes one latent frame per decoder call (:1337-1348).  Every op after the first chunk is
         # causal in time with the 2-frame feature cache, so latent frames 1.. can go through the decoder in groups
-        # with identical arithmetic per output; larger groups fill the chip on the low-resolution layers.  The
-        # group is bounded by the 32-bit byte offsets of the conv kernel (largest ring: (4G+2, 8h, 8w, widest C)).
+        # with identical arithmetic per output (the 128x128 and 256x256 conv kernels a layer switches between with the
+        # group size accumulate in the same order: test_conv_launch_size_invariance); larger groups fill the chip on
+        # the low-resolution layers.  The group is bounded by the 32-bit byte offsets of the conv kernel (largest ring:
+        # (4G+2, 8h, 8w, widest C)).
         widest = max(st.cin for st in self._states().values())
         group = int(max(1, min(self.max_chunk_group, (3.5e9 / (8 * h * 8 * w * min(widest, 512) * 2) - 2) // 4)))
         t0, i = 0, 0

@@ -220,7 +220,8 @@ int fg_conv3d_cl_bf16(const void* x, const void* w_packed, const void* bias,
 int fg_conv_tile_choice(int T, int H, int W, int Cout);
 
 /* out = main + DupUp3D(x): models/wan_video_vae.py:417-439,510-512.  x (T,H,W,Cin); main/out
- * (T*ft - drop, H*fs, W*fs, Cout) where drop = ft-1 if first_chunk. */
+ * (T*ft - drop, H*fs, W*fs, Cout) where drop = ft-1 if first_chunk.  Cout % 8 == 0; x, main and out
+ * 16-byte aligned (x is read with 16-byte vector loads when Cin % 8 == 0). */
 int fg_dupup3d_add_bf16(const void* x, const void* main_path, void* out,
                         int T, int H, int W, int Cin, int Cout, int ft, int fs, int first_chunk,
                         fg_stream_t stream);

@@ -94,6 +94,117 @@ def test_conv_full_size_sampled_pixels(hip, cin, cout, T, Hh, Ww):
     assert (y2 - 0.5 * y1).abs().max().item() < 3e-2
 
 
+# ---------------------------------------------------------------------------------- VAE kernels on tensors above 2 GiB
+# The (30, 52) latent tile of the bench decoded in groups of 8 latent frames: 32 frames at 240x416 on the last two stages.  One
+# 512-channel frame there is 102 236 160 bytes, so byte offsets pass 2^31 in frame 21; the checks sample frame 0, the last frames and
+# the spatial borders.
+T8, H8, W8 = 32, 240, 416
+TOP = (0, 21, T8 - 1)               # first frame, the frame where offsets pass 2^31, last frame
+
+
+def _rand_frames(shape, seed, scale=1.0):
+    """_rand without the fp32 copy of the whole tensor: filled one frame at a time."""
+    g = torch.Generator("cuda").manual_seed(seed)
+    x = torch.empty(shape, dtype=torch.bfloat16, device="cuda")
+    for t in range(shape[0]):
+        x[t] = (torch.randn(shape[1:], generator=g, device="cuda", dtype=torch.float32) * scale).to(torch.bfloat16)
+    return x
+
+
+def _window(x, t, y, xx, kt, ks, up=False):
+    """fp32 (1, C, kt, ks, ks) receptive field of output pixel (t, y, xx) in the channels-last input x: frames t .. t+kt-1, zeros outside
+    the image, read through the nearest-2x upsample when `up`."""
+    hin, win, c = x.shape[1:]
+    h, w, p = hin << up, win << up, ks // 2
+    out = torch.zeros((kt, ks, ks, c), device=x.device)
+    for dy in range(ks):
+        for dx in range(ks):
+            yy, xc = y + dy - p, xx + dx - p
+            if 0 <= yy < h and 0 <= xc < w:
+                out[:, dy, dx] = x[t:t + kt, yy >> up, xc >> up].float()
+    return out.permute(3, 0, 1, 2).unsqueeze(0)
+
+
+PIXELS = [(t, y, xx) for t in TOP for (y, xx) in ((0, 0), (H8 - 1, W8 - 1), (0, W8 - 1), (H8 - 1, 0), (H8 // 2, W8 // 2 + 1))] + \
+         [(T8 - 2, 1, 207), (22, 239, 3)]
+
+
+def test_vae_conv_input_above_2gib(hip):
+    """The first 240x416 conv of a group-8 chunk: a (34, 240, 416, 512) ring (3.48 GB, under the kernel's 0xF0000000-byte limit of
+    32-bit offsets) -> 256 couts, 3x3x3, on the hand-scheduled 256x256 kernel; sampled pixels against F.conv3d in fp32."""
+    cin, cout = 512, 256
+    lib = hip.load()
+    assert lib.fg_conv_tile_choice(T8, H8, W8, cout) == 256 and cin % 64 == 0 and cout % 256 == 0      # conv3d_cl_w4_kernel
+    x = _rand_frames((T8 + 2, H8, W8, cin), 21)
+    assert x.numel() * 2 > 3.4e9
+    w = _rand((cout, cin, 3, 3, 3), 22, scale=(cin * 27) ** -0.5)
+    b = _rand((cout,), 23, scale=0.1)
+    y = hip.conv3d_cl(x, hip.conv_pack_weight(w), b, cout, 3, 3)
+    assert y.shape == (T8, H8, W8, cout)
+    for (t, yy, xx) in PIXELS:
+        ref = F.conv3d(_window(x, t, yy, xx, 3, 3), w.float(), b.float())[0, :, 0, 0, 0]
+        assert (y[t, yy, xx].float() - ref).abs().max().item() < 3e-2, (t, yy, xx)
+    del x, y
+    torch.cuda.empty_cache()
+
+
+def test_vae_conv_output_above_2gib(hip):
+    """The 3x3 Conv2d of Resample38 after the nearest-2x upsample, 512 channels, 120x208 -> 240x416 with a residual: the output
+    (32, 240, 416, 512) is 3.27 GB.  Sampled pixels: bf16(conv + bias) + residual against fp32 on the upsampled window."""
+    c = 512
+    lib = hip.load()
+    assert lib.fg_conv_tile_choice(T8, H8, W8, c) == 256
+    x = _rand_frames((T8, H8 // 2, W8 // 2, c), 24)
+    res = _rand_frames((T8, H8, W8, c), 25)
+    w = _rand((c, c, 3, 3), 26, scale=(c * 9) ** -0.5)
+    b = _rand((c,), 27, scale=0.1)
+    y = hip.conv3d_cl(x, hip.conv_pack_weight(w), b, c, 1, 3, upsample2x=True, residual=res)
+    assert y.shape == (T8, H8, W8, c) and y.numel() * 2 > 3.2e9
+    for (t, yy, xx) in PIXELS:
+        conv = F.conv3d(_window(x, t, yy, xx, 1, 3, up=True), w.float().unsqueeze(2), b.float())[0, :, 0, 0, 0]
+        ref = conv.to(torch.bfloat16).float() + res[t, yy, xx].float()
+        assert (y[t, yy, xx].float() - ref).abs().max().item() < 3e-2, (t, yy, xx)
+    del x, res, y
+    torch.cuda.empty_cache()
+
+
+def test_vae_rmsnorm_silu_above_2gib(hip):
+    """RMS_norm * SiLU over the (32, 240, 416, 512) activation (3.27 GB): whole image rows at frame 0, across the 2^31-byte mark and at
+    the last frame, against the oracle's rms_norm_c + SiLU to 1 bf16 ulp."""
+    from oracle import wan_vae
+    from test_hip_kernels import assert_close_bf16
+    c = 512
+    x = _rand_frames((T8, H8, W8, c), 28, scale=2.0)
+    g = (1 + 0.1 * _rand((c,), 29).float()).to(torch.bfloat16)
+    y = hip.vae_rmsnorm_silu(x, g, True)
+    for (t, yy) in ((0, 0), (0, H8 - 1), (21, 1), (T8 - 1, 0), (T8 - 1, H8 - 1)):
+        xs = x[t, yy].cpu().t().reshape(1, c, W8, 1, 1)          # (1, C, pixels, 1, 1)
+        want = F.silu(wan_vae.rms_norm_c({"n.gamma": g.cpu().view(c, 1, 1, 1)}, "n", xs))
+        assert_close_bf16(y[t, yy].cpu(), want.reshape(c, W8).t(), 1.0, f"rmsnorm_silu frame {t} row {yy}")
+    del x, y
+    torch.cuda.empty_cache()
+
+
+def test_vae_dupup3d_above_2gib(hip):
+    """The 1024 -> 512 DupUp3D shortcut of the third up block (ft = 1, fs = 2) from (32, 120, 208, 1024) onto a (32, 240, 416, 512) main
+    path (3.27 GB): aligned crops of x and main through the oracle's dup_up3d + add equal the kernel's output crops bit for bit."""
+    from oracle import wan_vae
+    cin, cout, hc, wc = 1024, 512, 3, 4
+    x = _rand_frames((T8, H8 // 2, W8 // 2, cin), 30)
+    main = _rand_frames((T8, H8, W8, cout), 31)
+    out = hip.dupup3d_add(x, main, cout, 1, 2, False)
+    assert out.shape == main.shape
+    for t in TOP + (T8 - 2,):
+        for (y0, x0) in ((0, 0), (H8 // 2 - hc, W8 // 2 - wc), (0, W8 // 2 - wc), (H8 // 2 - hc, 0), (57, 101)):
+            xs = x[t:t + 1, y0:y0 + hc, x0:x0 + wc].cpu().permute(3, 0, 1, 2).unsqueeze(0)      # (1, Cin, 1, hc, wc)
+            ms = main[t:t + 1, 2 * y0:2 * (y0 + hc), 2 * x0:2 * (x0 + wc)].cpu().permute(3, 0, 1, 2).unsqueeze(0)
+            want = ms + wan_vae.dup_up3d(xs, cout, 1, 2, False)
+            got = out[t:t + 1, 2 * y0:2 * (y0 + hc), 2 * x0:2 * (x0 + wc)].cpu().permute(3, 0, 1, 2).unsqueeze(0)
+            assert torch.equal(got, want), (t, y0, x0)
+    del x, main, out
+    torch.cuda.empty_cache()
+
+
 def test_token_kernels_full_size_statistics(hip):
     """LN+modulate / RMSNorm+RoPE on the full (27 280, 3072) token tensor: row statistics and norm preservation."""
     from fairygen_amd.wan_video_dit import precompute_freqs_cis_3d

@@ -592,7 +592,58 @@ def test_conv_upsample_interleave_residual(hip):
     assert (_ncthw(got.cpu()).float() - want.float()).abs().max().item() < 3e-2
 
 
-@pytest.mark.parametrize("C,silu", [(1024, True), (256, True), (32, False), (512, True)])
+def _crand(shape, seed, scale=1.0):
+    g = torch.Generator("cuda").manual_seed(seed)
+    return (torch.randn(shape, generator=g, device="cuda", dtype=torch.float32) * scale).to(torch.bfloat16)
+
+
+def test_conv_launch_size_invariance(hip):
+    """Output frame f of a causal conv reads ring frames f..f+kt-1 only, so one call on a ring of T+2 frames must give, frame by
+    frame, exactly what calls on sub-rings give (ring[a : a+n+2] -> frames a..a+n-1, the decoder's chunk groups 1 + 8 + 2).  The
+    shapes put the 1- and 2-frame calls on the 128x128 kernel and the 8- and 11-frame calls on the hand-scheduled 256x256 one
+    (conv3d_cl_w4_kernel: Cin % 64 == 0, Cout % 256 == 0), so the two kernels must agree bit for bit (same k order)."""
+    lib = hip.load()
+    splits = [(0, 1), (1, 8), (9, 2)]
+    T = 11
+
+    def tiles(h, w, cout):
+        return {n: lib.fg_conv_tile_choice(n, h, w, cout) for n in (1, 2, 8, T)}
+
+    # the 30x52 stage: 3x3x3 causal conv 1024 -> 1024, without and with the residual of ResidualBlock
+    c = 1024
+    assert tiles(30, 52, c) == {1: 128, 2: 128, 8: 256, T: 256}
+    ring = _crand((T + 2, 30, 52, c), 1)
+    packed = hip.conv_pack_weight(_crand((c, c, 3, 3, 3), 2, scale=(c * 27) ** -0.5))
+    bias = _crand((c,), 3, scale=0.1)
+    res = _crand((T, 30, 52, c), 4)
+    for r in (None, res):
+        full = hip.conv3d_cl(ring, packed, bias, c, 3, 3, residual=r)
+        for a, n in splits:
+            part = hip.conv3d_cl(ring[a:a + n + 2], packed, bias, c, 3, 3, residual=None if r is None else r[a:a + n])
+            assert torch.equal(part, full[a:a + n]), (a, n, r is not None)
+    # time_conv of Resample38 upsample3d: 1024 -> 2048, kt = 3, ks = 1, channel halves interleaved in time (frames 2a .. 2a+2n-1)
+    assert tiles(30, 52, 2 * c) == {1: 128, 2: 256, 8: 256, T: 256}
+    packed = hip.conv_pack_weight(_crand((2 * c, c, 3, 1, 1), 5, scale=(c * 3) ** -0.5))
+    bias = _crand((2 * c,), 6, scale=0.1)
+    full = hip.conv3d_cl(ring, packed, bias, 2 * c, 3, 1, time_interleave=True)
+    assert full.shape == (2 * T, 30, 52, c)
+    for a, n in splits:
+        part = hip.conv3d_cl(ring[a:a + n + 2], packed, bias, 2 * c, 3, 1, time_interleave=True)
+        assert torch.equal(part, full[2 * a:2 * a + 2 * n]), (a, n)
+    del ring, res
+    # the 3x3 Conv2d of Resample38 after the nearest-2x upsample (frames independent): 512 channels, 15x26 -> 30x52
+    c = 512
+    assert tiles(30, 52, c) == {1: 128, 2: 128, 8: 256, T: 256}
+    x = _crand((T, 15, 26, c), 7)
+    packed = hip.conv_pack_weight(_crand((c, c, 3, 3), 8, scale=(c * 9) ** -0.5))
+    bias = _crand((c,), 9, scale=0.1)
+    full = hip.conv3d_cl(x, packed, bias, c, 1, 3, upsample2x=True)
+    assert full.shape == (T, 30, 52, c)
+    for a, n in splits:
+        assert torch.equal(hip.conv3d_cl(x[a:a + n], packed, bias, c, 1, 3, upsample2x=True), full[a:a + n]), (a, n)
+
+
+@pytest.mark.parametrize("C,silu",[(1024, True), (256, True), (32, False), (512, True)])
 def test_vae_rmsnorm_silu(hip, C, silu):
     x = seeded((1, C, 2, 5, 7), 70, scale=2.0)
     g = (1 + 0.1 * seeded((C, 1, 1, 1), 71)).to(torch.bfloat16)
@@ -602,7 +653,12 @@ def test_vae_rmsnorm_silu(hip, C, silu):
     assert_close_bf16(_ncthw(got.cpu()), want, 1.0, "vae rmsnorm")
 
 
-@pytest.mark.parametrize("cin,cout,ft,fs,first", [(64, 64, 2, 2, True), (64, 64, 2, 2, False), (64, 32, 1, 2, False), (128, 64, 1, 2, True)])
+@pytest.mark.parametrize("cin,cout,ft,fs,first", [
+    (64, 64, 2, 2, True), (64, 64, 2, 2, False), (64, 32, 1, 2, False), (128, 64, 1, 2, True),
+    (256, 64, 1, 2, False),                                 # source stride 4: the widest vector-load form
+    (256, 32, 2, 2, True), (256, 32, 2, 2, False),          # stride 8: scalar gathers, repeats = 1 (shift 0)
+    (32, 48, 1, 2, False),                                  # repeats = 6: not a power of two, gathers with an integer division
+    (12, 24, 1, 2, False), (12, 24, 2, 2, True), (12, 24, 2, 2, False)])    # Cin % 8 != 0: x rows not 16-byte vectors
 def test_dupup3d_add(hip, cin, cout, ft, fs, first):
     x = seeded((1, cin, 2, 3, 4), 80)
     sc = wan_vae.dup_up3d(x, cout, ft, fs, first)

@@ -322,6 +322,53 @@ def test_tiny_vae_decode_vs_golden(tiny_vae, golden):
     assert cos(out_t, g["tiled_bf16"]) > 0.9995
 
 
+def _decode_chunks(monkeypatch, vae, z, group):
+    """vae.model.decode(z) unclamped with decoder groups of `group` latent frames -> (video, chunk sizes the decoder was called with)."""
+    from fairygen_amd.wan_video_vae import VideoVAE38_
+    sizes, inner = [], VideoVAE38_._decoder_chunk
+
+    def record(self, x, first_chunk):
+        sizes.append(x.shape[0])
+        return inner(self, x, first_chunk)
+    with monkeypatch.context() as m:
+        m.setattr(VideoVAE38_, "_decoder_chunk", record)
+        m.setattr(vae.model, "max_chunk_group", group)
+        with torch.no_grad():
+            video = vae.model.decode(z, vae.scale, clamp=False)
+    torch.cuda.synchronize()
+    return video, sizes
+
+
+def test_tiny_vae_decode_group_invariance(tiny_vae, monkeypatch):
+    """Latent frames 1.. go through the decoder in groups of max_chunk_group (default 8); the reference decodes one frame per call.
+    Every op after the first chunk is causal with the 2-frame cache, so the output must be bit-identical for any group size."""
+    vae, _ = tiny_vae
+    z = seeded((1, 48, 11, 2, 2), 36).cuda()
+    default = vae.model.max_chunk_group
+    outs = {}
+    for group, want in ((1, [1] * 11), (3, [1, 3, 3, 3, 1]), (8, [1, 8, 2])):
+        outs[group], sizes = _decode_chunks(monkeypatch, vae, z, group)
+        assert sizes == want, (group, sizes)
+    assert vae.model.max_chunk_group == default
+    assert outs[1].shape == (1, 3, 41, 32, 32)
+    assert torch.equal(outs[3], outs[1]) and torch.equal(outs[8], outs[1])
+
+
+def test_tiny_vae_decode_group8_vs_reference_golden(tiny_vae, golden):
+    """The default group of 8 (chunks 1 + 8 + 2) against the reference's one-frame-per-call decode (oracle/gen_vae_long.py)."""
+    g = golden("vae_long.safetensors")
+    vae, _ = tiny_vae
+    assert vae.model.max_chunk_group == 8
+    z = seeded((1, 48, 11, 2, 2), 36)
+    with torch.no_grad():
+        out = vae.decode(z.cuda(), device="cuda", tiled=False)
+    ref32 = g["decode_f32"].clamp(-1, 1)
+    assert out.shape == g["decode_bf16"].shape == (1, 3, 41, 32, 32)
+    err_ref = (g["decode_bf16"].float() - ref32).abs().max().item()
+    err = (out.float().cpu() - ref32).abs().max().item()
+    assert err <= 2 * err_ref + 1e-2, (err, err_ref)
+
+
 def test_tiny_vae_encode_vs_golden(tiny_vae, golden):
     """First-frame conditioning path: WanVideoVAE38.encode([image]) untiled and tiled."""
     g = golden("vae_tiny.safetensors")
@@ -390,6 +437,28 @@ def test_fullwidth_tiled_vae_decode_vs_reference_golden(golden):
     assert cos(sub, ref) > 0.9995
     assert (sub - f32).abs().mean().item() <= 1.25 * (ref - f32).abs().mean().item() + 1e-3
     del vae
+    torch.cuda.empty_cache()
+
+
+def test_fullwidth_vae_decode_group_invariance_at_bench_tile(monkeypatch):
+    """The real decoder on one (30, 52) latent tile, the bench's: the default group of 8 (chunks 1 + 8 + 1) must give the bits of the
+    reference's one-frame-per-call order.  The group-8 chunk makes the 512-channel ring of the first 240x416 conv (34, 240, 416, 512)
+    = 3.48 GB, so the conv, RMS_norm*SiLU and DupUp3D kernels address beyond 2^31 bytes; every ring then grows from 1 to 8 frames
+    and is reused for the last 1-frame chunk."""
+    from fairygen_amd.wan_video_vae import WanVideoVAE38
+    with torch.device("meta"):
+        vae = WanVideoVAE38()
+    vae.load_state_dict(synthetic.random_state_dict(synthetic.vae_shapes(), seed=1234), assign=True)
+    vae = vae.to(device="cuda", dtype=torch.bfloat16).eval()
+    assert vae.model.max_chunk_group == 8
+    z = seeded((1, 48, 10, 30, 52), 37).cuda()
+    one, sizes1 = _decode_chunks(monkeypatch, vae, z, 1)
+    assert sizes1 == [1] * 10
+    eight, sizes8 = _decode_chunks(monkeypatch, vae, z, 8)
+    assert sizes8 == [1, 8, 1]
+    assert one.shape == (1, 3, 37, 480, 832)
+    assert torch.equal(eight, one), (eight.float() - one.float()).abs().max().item()
+    del vae, one, eight
     torch.cuda.empty_cache()
 
 

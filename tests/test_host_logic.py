@@ -107,6 +107,10 @@ def test_argument_validation_through_the_c_abi():
     rc = lib.fg_conv3d_cl_bf16(ctypes.c_void_p(16), ctypes.c_void_p(16), ctypes.c_void_p(16), None, ctypes.c_void_p(16),
                                1, 4, 4, 8, 8, 2, 3, 0, 0, None)
     assert rc == -1 and b"kt and ks" in lib.fg_last_error()
+    # DupUp3D reads x with 16-byte vector loads: a misaligned x is refused.  H * fs = 80 000 rows exceed the grid, so even a library
+    # without the alignment check returns an error here before any launch
+    rc = lib.fg_dupup3d_add_bf16(ctypes.c_void_p(18), ctypes.c_void_p(16), ctypes.c_void_p(16), 1, 40000, 1, 64, 64, 1, 2, 0, None)
+    assert rc == -1 and b"misaligned" in lib.fg_last_error()
     assert lib.fg_conv_packed_bytes(12, 256, 3, 3, 3) == 27 * 128 * 256 * 2
     assert lib.fg_conv_packed_bytes(1024, 48, 3, 3, 3) == 27 * 1024 * 64 * 2
 

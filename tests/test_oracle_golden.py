@@ -192,6 +192,16 @@ def test_vae_tiny_decode(golden):
     assert torch.allclose(wan_vae.vae_decode(sd32, z.float(), tiled=False), g["decode_f32"], atol=1e-5, rtol=1e-5)
 
 
+def test_vae_tiny_decode_long(golden):
+    """11 latent frames (41 video frames): the oracle's one-frame-per-call decode against the reference's (oracle/gen_vae_long.py)."""
+    g = golden("vae_long.safetensors")
+    sd = synthetic.random_state_dict(synthetic.vae_shapes(dec_dim=32, dim=32), seed=1234)
+    z = seeded((1, 48, 11, 2, 2), 36)
+    assert torch.equal(wan_vae.vae_decode(sd, z, tiled=False), g["decode_bf16"])
+    sd32 = {k: v.float() for k, v in sd.items()}
+    assert torch.allclose(wan_vae.vae_decode(sd32, z.float(), tiled=False), g["decode_f32"], atol=1e-5, rtol=1e-5)
+
+
 def test_vae_tiny_encode(golden):
     g = golden("vae_tiny.safetensors")
     sd = synthetic.random_state_dict(synthetic.vae_shapes(dec_dim=32, dim=32), seed=1234)
