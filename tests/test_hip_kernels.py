@@ -523,6 +523,64 @@ def test_attention_w4_strided_qkv(hip):
     assert (got.float().cpu() - ref32).abs().max().item() <= 2 * err_ref + 2e-3
 
 
+# norm weights ~3: peaked logits (std ~9) as trained heads have them; there near-tied keys make the bf16 chain itself err by ~0.28, which
+# hides a scale error of 2 %.  ~1: logit std ~1, where dropping the fold costs ~6x the bf16 chain's error (CPU emulation, N = 1 950)
+@pytest.mark.parametrize("norm_w", [3.0, 1.0])
+@pytest.mark.parametrize("grid", [(5, 15, 26),        # N = 1 950: 7 q-blocks + 158 rows; 30 KV tiles + 30 keys
+                                  (13, 15, 26)])      # N = 5 070: config 2's grid
+def test_rope_fold_into_w4_attention(hip, grid, norm_w):
+    """Self-attention composed as WanModel._self_attention_steps runs it: q, k, v are column slices of one (1, N, 3*3072) buffer,
+    fg_rmsnorm_rope_bf16 normalises and rotates k and q with the product's own tables (WanModel.rope_tables: in the default form q's fp32
+    table carries the folded 1.0201 of 1/sqrt(128)), fg_attn_fwd_bf16 (w4 kernel: Nkv > 1024) runs with attn_scale()'s scale' =
+    2^-3 / log2(e).  Reference: the plain chain of models/wan_video_dit.py:91-110,139-146 in high precision (RMSNorm in fp32, rope_apply
+    on the fp64 table, attention in fp32 with 1/sqrt(d)); yardstick: the same chain at the reference's bf16 rounding points.
+    Norm weights ~norm_w set the logit scale; a few tokens get their own pre-norm q row as k (RoPE turns both by the same angle: near
+    one-hot rows early, mid-sequence and in the ragged last KV tile).  Criterion: error to the fp32 chain <= 2x the bf16 chain's + floor,
+    overall and on the spiked rows.  Three forms: the default (fp32 tables + fold + pre-multiplied kernel body), fold_attn_scale=False
+    (fp32 tables, plain body) and rope_mode="f64" (fp64 tables, plain body)."""
+    from fairygen_amd import synthetic
+    from fairygen_amd.wan_video_dit import WanModel
+    heads, c, eps = 24, 3072, 1e-6
+    f, h, w_ = grid
+    n = f * h * w_
+    spikes = [3, n // 3, n // 2, n - 2]
+    assert n > 1024 and n % 64 and (n - 2) // 64 == (n - 1) // 64          # w4 kernel; the last spike is in the ragged last KV tile
+    qkv = seeded((1, n, 3 * c), 150)
+    for t in spikes:
+        qkv[0, t, c:2 * c] = qkv[0, t, :c]
+    wq = (norm_w + 0.1 * seeded((c,), 151, torch.float32)).to(torch.bfloat16)
+    wk = (norm_w + 0.1 * seeded((c,), 152, torch.float32)).to(torch.bfloat16)
+    xq, xk, v = qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:]
+    table = wan_dit.rope_table_3d(128, f, h, w_)
+    q32 = wan_dit.rope_apply(wan_dit.rms_norm(xq.float(), wq.float(), eps), table, heads)
+    k32 = wan_dit.rope_apply(wan_dit.rms_norm(xk.float(), wk.float(), eps), table, heads)
+    logits = q32[0, :256, :128] @ k32[0, :, :128].T / 128 ** 0.5           # head 0, first q-block
+    assert logits.std().item() >= 0.9 * norm_w ** 2, logits.std().item()
+    ref32 = wan_dit.attention(q32, k32, v.float(), heads)
+    ref16 = wan_dit.attention(wan_dit.rope_apply(wan_dit.rms_norm(xq, wq, eps), table, heads),
+                              wan_dit.rope_apply(wan_dit.rms_norm(xk, wk, eps), table, heads), v, heads).float()
+    err_ref = (ref16 - ref32).abs().max().item()
+    err_ref_spikes = (ref16[0, spikes] - ref32[0, spikes]).abs().max().item()
+    d, wq_d, wk_d = dev(qkv), dev(wq), dev(wk)
+    m = WanModel(**synthetic.TINY_DIT_KWARGS)              # head_dim 128: the product's own tables and scale split
+    for form, fold_on, mode in (("default", True, "f32"), ("fold_attn_scale=False", False, "f32"), ('rope_mode="f64"', True, "f64")):
+        m.fold_attn_scale, m.rope_mode = fold_on, mode
+        cos, sin = m.rope_tables(f, h, w_, "cuda")
+        rk, rq = ((cos, None), (sin, None)) if cos.dtype == torch.float32 else ((cos, sin), (cos, sin))
+        scale, fold = m.attn_scale()
+        k = hip.rmsnorm_rope(d[..., c:2 * c], wk_d, heads, eps, *rk)
+        q = hip.rmsnorm_rope(d[..., :c], wq_d, heads, eps, *rq)
+        got = (hip.attention(q, k, d[..., 2 * c:], heads) if scale is None else
+               hip.attention(q, k, d[..., 2 * c:], heads, scale=scale)).float().cpu()
+        assert torch.isfinite(got).all(), form
+        err = (got - ref32).abs().max().item()
+        err_spikes = (got[0, spikes] - ref32[0, spikes]).abs().max().item()
+        print(f"N={n} {form}: err {err:.5f} (bf16 chain {err_ref:.5f}), spiked rows {err_spikes:.5f} ({err_ref_spikes:.5f})")
+        assert err <= 2 * err_ref + 2e-3, f"{form}: err {err} vs the bf16 chain's {err_ref}"
+        assert err_spikes <= 2 * err_ref_spikes + 2e-3, f"{form}, spiked rows: err {err_spikes} vs the bf16 chain's {err_ref_spikes}"
+        assert (fold != 1.0) == (form == "default") and (scale is None) == (form != "default"), (form, scale, fold)
+
+
 def test_attention_strided_inputs(hip):
     heads, n = 2, 150
     c = heads * 128

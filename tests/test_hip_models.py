@@ -599,19 +599,28 @@ def test_config1_full_width_vs_reference_golden(golden):
     torch.cuda.empty_cache()
 
 
-def test_config2_forward_full_width_vs_reference_golden(golden):
-    """One forward of BASELINE.json configs[1] (480x832x49: N = 5 070 tokens, a ragged 19.8 query blocks with the split-KV tail)
-    at the full model width against the reference's own bf16 prediction (oracle/gen_config2_forward.py; the oracle equalled
-    it bit for bit) with the fp32 evaluation as yardstick: max|hip - f32| <= 2 max|ref_bf16 - f32| + floor."""
+@pytest.fixture(scope="module")
+def full_dit():
+    """The full-width DiT (30 blocks, dim 3072) on the synthetic weights of the reference-run goldens (seed 1234, CPU generator),
+    loaded once for the config-2 tests."""
     from fairygen_amd.loader import TI2V_5B_DIT_KWARGS
-    from fairygen_amd.wan_video import model_fn_wan_video
     from fairygen_amd.wan_video_dit import WanModel
-    g = golden("config2_forward.safetensors")
     cfg = dict(TI2V_5B_DIT_KWARGS)
     with torch.device("meta"):
         dit = WanModel(**cfg)
     dit.load_state_dict(synthetic.random_state_dict(synthetic.dit_shapes(cfg), seed=1234), assign=True)
-    dit = dit.to(device="cuda", dtype=torch.bfloat16).eval()
+    yield dit.to(device="cuda", dtype=torch.bfloat16).eval()
+    dit.to("meta")          # pytest keeps the fixture's value until after this teardown: free the weights themselves
+    torch.cuda.empty_cache()
+
+
+def test_config2_forward_full_width_vs_reference_golden(golden, full_dit):
+    """One forward of BASELINE.json configs[1] (480x832x49: N = 5 070 tokens, a ragged 19.8 query blocks with the split-KV tail)
+    at the full model width against the reference's own bf16 prediction (oracle/gen_config2_forward.py; the oracle equalled
+    it bit for bit) with the fp32 evaluation as yardstick: max|hip - f32| <= 2 max|ref_bf16 - f32| + floor."""
+    from fairygen_amd.wan_video import model_fn_wan_video
+    g = golden("config2_forward.safetensors")
+    dit = full_dit
     lat = seeded((1, 48, 13, 30, 52), 1)
     lat[:, :, 0:1] = seeded((1, 48, 1, 30, 52), 4)
     ctx = seeded((1, 512, 4096), 2); ctx[:, 64:] = 0
@@ -624,6 +633,90 @@ def test_config2_forward_full_width_vs_reference_golden(golden):
     assert err <= 2 * err_ref + 1e-2, (err, err_ref)
     assert cos(sub, ref) > 0.9995 and (sub - f32).abs().mean().item() <= 1.25 * (ref - f32).abs().mean().item() + 1e-4
     del dit
+    torch.cuda.empty_cache()
+
+
+def _config2_loop_inputs():
+    noise = seeded((1, 48, 13, 30, 52), 1)
+    ctx_p = seeded((1, 512, 4096), 2); ctx_p[:, 64:] = 0
+    ctx_n = seeded((1, 512, 4096), 3); ctx_n[:, 128:] = 0
+    return noise, ctx_p, ctx_n, seeded((1, 48, 1, 30, 52), 4)
+
+
+def _config2_loop_steps(dit, monkeypatch):
+    """pipe.denoise, 3 steps CFG 5 shift 5 with the TI2V pin, as configured at call time; returns the latents after every step — the
+    tensors hip.cfg_euler returned, into which the loop then re-pins frame 0 in place."""
+    from fairygen_amd import hip
+    from fairygen_amd.wan_video import WanVideoPipeline
+    noise, ctx_p, ctx_n, z0 = _config2_loop_inputs()
+    pipe = WanVideoPipeline(device="cuda", torch_dtype=torch.bfloat16)
+    pipe.dit = dit
+    pipe.scheduler.set_timesteps(3, denoising_strength=1.0, shift=5.0)
+    latents = noise.clone()
+    latents[:, :, 0:1] = z0
+    shared = {"latents": latents.cuda(), "fuse_vae_embedding_in_latents": True, "first_frame_latents": z0.cuda()}
+    steps, cfg_euler = [], hip.cfg_euler
+
+    def keep(*args, **kwargs):
+        steps.append(cfg_euler(*args, **kwargs))
+        return steps[-1]
+    with monkeypatch.context() as m, torch.no_grad():
+        m.setattr(hip, "cfg_euler", keep)
+        out = pipe.denoise(shared, {"context": ctx_p.cuda()}, {"context": ctx_n.cuda()}, 5.0, progress_bar_cmd=lambda x: x)
+    assert len(steps) == 3 and steps[-1] is out
+    return steps
+
+
+def _assert_config2_loop_vs_golden(steps, g, what):
+    """The config-1 / config-2 criteria at every step k: cos(hip_k, ref_k) >= 0.999 and mean|hip_k - f32_k| <= 1.1 mean|ref_k - f32_k|
+    + 1e-4; at step 0 also max|hip_0 - f32_0| <= 2 max|ref_0 - f32_0| + 1e-2; frame 0 equal to the pinned first frame after every step."""
+    z0 = _config2_loop_inputs()[3]
+    for k, lat in enumerate(steps):
+        assert torch.equal(lat[:, :, 0:1].cpu(), z0), f"{what}: frame 0 after step {k}"
+        sub, ref, f32 = lat[:, ::8].float().cpu(), g[f"ref_bf16_step{k}"].float(), g[f"f32_step{k}"]
+        assert sub.shape == ref.shape == f32.shape == (1, 6, 13, 30, 52)
+        c, mean_hip, mean_ref = cos(sub, ref), (sub - f32).abs().mean().item(), (ref - f32).abs().mean().item()
+        max_hip, max_ref = (sub - f32).abs().max().item(), (ref - f32).abs().max().item()
+        print(f"{what} step {k}: cos(hip, ref) {c:.6f}; mean|hip - f32| {mean_hip:.5f} vs mean|ref - f32| {mean_ref:.5f}; "
+              f"max {max_hip:.4f} vs {max_ref:.4f}")
+        assert c >= 0.999, f"{what} step {k}: cos {c}"
+        assert mean_hip <= 1.1 * mean_ref + 1e-4, f"{what} step {k}: mean {mean_hip} vs the reference's {mean_ref}"
+        if k == 0:
+            assert max_hip <= 2 * max_ref + 1e-2, f"{what} step 0: max {max_hip} vs the reference's {max_ref}"
+
+
+def test_config2_loop_full_width_vs_reference_golden(golden, full_dit, monkeypatch):
+    """Three CFG denoise steps of BASELINE.json configs[1] (N = 5 070 tokens) at the full model width on the production kernel mix —
+    attn_fwd_w4_kernel with the folded softmax scale, the own GEMM for every block Linear, the shared CFG prefix, the cross-attention K/V
+    cache, the fused CFG + Euler kernel and the TI2V re-pin — against the reference's own loop (oracle/gen_config2_loop.py; the oracle
+    equalled it bit for bit at every step) with the fp32 evaluation as yardstick.  Then the same loop (a) with the prefix and the cache
+    off: bit-identical at every step (they remove work exactly), (b) with fold_attn_scale=False and (c) with GEMM_BACKEND "fused"
+    (round 2's default): the same reference criteria."""
+    from fairygen_amd import wan_video, wan_video_dit
+    g = golden("config2_loop.safetensors")
+    dit = full_dit
+    n, c, ffn = 13 * 15 * 26, dit.dim, dit.blocks[0].ffn[0].weight.shape[0]
+    # the mix the benchmark times: Nkv > 1024 selects the w4 kernel; every block Linear on the own GEMM; the fold is on; both caches on
+    assert n > 1024 and wan_video_dit.GEMM_BACKEND == "all"
+    assert all(wan_video_dit.own_gemm_ok(n, cols, k) for cols, k in ((3 * c, c), (c, c), (ffn, c), (c, ffn)))
+    assert dit.attn_scale()[1] != 1.0
+    assert wan_video.CFG_SHARE_PREFIX and wan_video.CROSS_KV_CACHE
+    base = _config2_loop_steps(dit, monkeypatch)
+    _assert_config2_loop_vs_golden(base, g, "default")
+    with monkeypatch.context() as m:
+        m.setattr(wan_video, "CFG_SHARE_PREFIX", False)
+        m.setattr(wan_video, "CROSS_KV_CACHE", False)
+        plain = _config2_loop_steps(dit, monkeypatch)
+    for k, (a, b) in enumerate(zip(base, plain)):
+        assert torch.equal(a, b), f"(a) prefix and cache off: step {k} differs by {(a.float() - b.float()).abs().max().item()}"
+    with monkeypatch.context() as m:
+        m.setattr(dit, "fold_attn_scale", False)
+        assert dit.attn_scale() == (None, 1.0)
+        _assert_config2_loop_vs_golden(_config2_loop_steps(dit, monkeypatch), g, "fold_attn_scale=False")
+    with monkeypatch.context() as m:
+        m.setattr(wan_video_dit, "GEMM_BACKEND", "fused")
+        _assert_config2_loop_vs_golden(_config2_loop_steps(dit, monkeypatch), g, 'GEMM_BACKEND="fused"')
+    del base, plain
     torch.cuda.empty_cache()
 
 

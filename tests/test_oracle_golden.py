@@ -153,6 +153,22 @@ def test_oracle_full_width_config1(golden):
             assert torch.equal(lat, g[f"latents_step{i}"]), f"step {i}"
 
 
+def test_config2_loop_fixture_parts_and_pin(golden):
+    """tests/golden/config2_loop.part{0,1,2}.safetensors (oracle/gen_config2_loop.py, cut along the last dimension): the parts join to
+    the stored shapes, and frame 0 of every step equals the sampled channels of the TI2V first frame bit for bit in the reference's bf16
+    loop and in the fp32 one (the pin after every step, and a check that the parts are joined in order)."""
+    g = golden("config2_loop.safetensors")
+    assert sorted(g) == sorted(f"{kind}_step{k}" for kind in ("ref_bf16", "f32") for k in range(3))
+    z0 = seeded((1, 48, 1, 30, 52), 4)[:, ::8]
+    for k in range(3):
+        ref, f32 = g[f"ref_bf16_step{k}"], g[f"f32_step{k}"]
+        assert ref.dtype == torch.bfloat16 and f32.dtype == torch.float32
+        assert ref.shape == f32.shape == (1, 6, 13, 30, 52)
+        assert torch.equal(ref[:, :, 0:1], z0) and torch.equal(f32[:, :, 0:1], z0.float()), f"step {k}"
+        if k:
+            assert not torch.equal(ref[:, :, 1:], g[f"ref_bf16_step{k - 1}"][:, :, 1:])
+
+
 def test_scheduler(golden):
     g = golden("scheduler.safetensors")
     for n in (4, 30, 50):
