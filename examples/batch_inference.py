@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--weights", required=True)
     ap.add_argument("--tokenizer", required=True)
     ap.add_argument("--lora")
+    ap.add_argument("--lora-dir", help="per-shot adapters: <dir>/<shot name>.safetensors, hot-loaded before that shot (HIP backend) and dropped after it")
     ap.add_argument("--input", required=True)
     ap.add_argument("--output", required=True)
     ap.add_argument("--replica-size", type=int, default=2)
@@ -34,7 +35,12 @@ def main():
         dist.init_process_group("nccl")
     sched = ShotScheduler(replica_size=a.replica_size)
     pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8)
-    done = sched.run_folder(pipe, a.input, a.output, negative_prompt=NEGATIVE, num_frames=81, seed=1, tiled=True)
+    lora_for_shot = None
+    if a.lora_dir:
+        def lora_for_shot(name):
+            path = os.path.join(a.lora_dir, name + ".safetensors")
+            return path if os.path.exists(path) else None
+    done = sched.run_folder(pipe, a.input, a.output, negative_prompt=NEGATIVE, lora_for_shot=lora_for_shot, num_frames=81, seed=1, tiled=True)
     for name, path in done:
         if path:
             print(f"saved: {path}")

@@ -59,15 +59,25 @@ class ShotScheduler:
         return [s for i, s in enumerate(shots) if i % self.n_replicas == self.replica_id]
 
     def run_folder(self, pipe, input_folder, output_folder, negative_prompt="", size=(832, 480), fps=15, quality=5,
-                   **call_kwargs):
+                   lora_for_shot=None, **call_kwargs):
         """batch_inference.py end to end for this process's share: open image + prompt, pipe(...), save_video.
-        Returns [(shot name, output path)] (paths only on the replica's writer rank)."""
+        Returns [(shot name, output path)] (paths only on the replica's writer rank).
+        lora_for_shot: optional callable, shot name -> path of that shot's adapter file or None.  Before a shot whose adapter differs
+        from the one in place, the hot-loaded adapter is dropped (pipe.clear_lora()) and the new one attached unfused on the HIP
+        backend (pipe.load_lora(pipe.dit, path, hotload=True, hot_backend="hip")): no reload of the base weights between shots."""
         from PIL import Image
         from .data import save_video
         self.attach(pipe)
         os.makedirs(output_folder, exist_ok=True)
-        done = []
+        done, current = [], None
         for base, img_path, txt_path in self.my_shots(list_shots(input_folder)):
+            wanted = lora_for_shot(base) if lora_for_shot is not None else None
+            if wanted != current:
+                if current is not None:
+                    pipe.clear_lora()
+                if wanted is not None:
+                    pipe.load_lora(pipe.dit, wanted, hotload=True, hot_backend="hip")
+                current = wanted
             image = Image.open(img_path).convert("RGB").resize(size)
             with open(txt_path, "r", encoding="utf-8") as f:
                 prompt = f.read().strip()

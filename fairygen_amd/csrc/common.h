@@ -51,6 +51,13 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
     return 0.5f * x * (1.0f + t);
 }
 
+// GELU(tanh) exactly as the asm epilogue of the DiT GEMM computes it (gen_gemm_p.py emit_gelu_words; shared with its reduce kernel and fg_lora_apply_bf16): y * rcp(1 + exp2(y * (c1 + c2 y^2)))
+__device__ __forceinline__ float gelu_tanh_epilogue(float y) {
+    const float c1 = (float)(-2.0 * 0.7978845608028654 * 1.4426950408889634), c2 = (float)(-2.0 * 0.7978845608028654 * 1.4426950408889634 * 0.044715);
+    const float arg = __builtin_fmaf(y * y, c2, c1) * y;
+    return y * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(arg) + 1.0f);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -13,7 +13,7 @@ import torch
 _LIB_PATH = os.environ.get("FAIRYGEN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfairygen_hip.so")
 _lib = None
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 _i64, _i32, _f32, _vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
@@ -32,6 +32,7 @@ _SIGNATURES = {
     "fg_act_bf16": [_vp, _vp, _i64, _i32, _vp],
     "fg_gemm_epilogue_bf16": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp],
     "fg_gemm_fp8_bf16": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp],
+    "fg_lora_apply_bf16": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp],
     "fg_attn_fwd_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _f32, _vp, _i64, _vp],
     "fg_cfg_euler_bf16": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _vp],
     "fg_vae_rmsnorm_silu_bf16": [_vp, _vp, _vp, _i64, _i32, _i32, _vp],
@@ -399,6 +400,40 @@ def gemm_fp8(x_fp8, scale_a, weight_fp8, bias, out=None, residual=False, mod=Non
     ws = _gemm_ws(x_fp8, m, n, k, workspace)
     _call("fg_gemm_fp8_bf16", _ptr(x_fp8), x_fp8.stride(0), _ptr(scale_a), _ptr(weight_fp8), _ptr(bias), _ptr(out), n, m, n, k, mode, gate,
           gate_rows, gate_ld, first, _ptr(ws), _stream(x_fp8))
+    return out
+
+
+LORA_RANK_TILE, LORA_MAX_RANK, LORA_MAX_GROUPS = 32, 128, 4      # fg_lora_apply_bf16: per-group rank padded to 32s, at most 128; column groups
+_LORA_MODES = {"write": 0, "add": 1, "gate": 2, "gelu_tanh": 4}
+
+
+def lora_apply(x, a, b, out, groups=1, mode="add", mod=None, gate_idx=None):
+    """Hot-loaded LoRA adapters of one Linear (AutoWrappedLinear.lora_forward, core/vram/layers.py:417-436) on fg_lora_apply_bf16, in place
+    on `out`: with l_g = bf16(bf16(x @ a_g^T) @ b_g^T) for each of the `groups` column groups of `out` (3: q | k | v of the fused
+    projection), mode "write": out_g = l_g; "add": out_g += l_g; "gate": out_g += gate * l_g (gate = vector gate_idx of `mod`, as
+    gemm_epilogue's residual form); "gelu_tanh": out_g = gelu_tanh(out_g + l_g).  x (..., K) with a dense last dim (2-D / (1, rows, K)
+    when strided), out likewise with groups * Ng columns; a: (groups * R, K) the stacked alpha * A, b: (groups * Ng, R) the stacked B,
+    R a multiple of 32 up to 128 (WanModel pads with zeros)."""
+    _dev(x, "x"), _dev(a, "a"), _dev(b, "b"), _dev(out, "out")
+    if mode not in _LORA_MODES:
+        raise HipLibraryError(f"lora_apply: mode must be one of {sorted(_LORA_MODES)}")
+    k, n = x.shape[-1], out.shape[-1]
+    if x.stride(-1) != 1 or out.stride(-1) != 1 or not a.is_contiguous() or not b.is_contiguous() or a.dim() != 2 or b.dim() != 2:
+        raise HipLibraryError("lora_apply: x and out must be dense in their last dim, a and b contiguous matrices")
+    x2 = x.reshape(-1, k) if x.is_contiguous() else (x.squeeze(0) if x.dim() == 3 else x)
+    o2 = out.view(-1, n) if out.is_contiguous() else (out.squeeze(0) if out.dim() == 3 else out)
+    if x2.dim() != 2 or o2.dim() != 2 or x2.shape[0] != o2.shape[0]:
+        raise HipLibraryError("lora_apply: strided tensors must be 2-D (rows, C) or (1, rows, C), with the same rows in x and out")
+    r = b.shape[1]
+    if groups < 1 or n % groups or a.shape != (groups * r, k) or b.shape[0] != n:
+        raise HipLibraryError(f"lora_apply: a {tuple(a.shape)} / b {tuple(b.shape)} do not fit x (.., {k}) -> out (.., {n}) in {groups} group(s)")
+    gate, gate_rows, gate_ld, first = None, 1, n, 0
+    if mode == "gate":
+        if mod is None or mod.mod_rows not in (1, 2) or mod.c != n:
+            raise HipLibraryError("lora_apply: mode 'gate' needs a ModTable of 1 or 2 rows of N values")
+        gate, gate_rows, gate_ld, first = mod.vec(gate_idx), mod.mod_rows, mod.ld, mod.first_rows
+    _call("fg_lora_apply_bf16", _ptr(x2), x2.stride(0), _ptr(a), _ptr(b), _ptr(o2), o2.stride(0), x2.shape[0], k, n // groups, r, groups,
+          _LORA_MODES[mode], gate, gate_rows, gate_ld, first, _stream(x))
     return out
 
 

@@ -402,11 +402,19 @@ class WanVideoPipeline(torch.nn.Module):
     def load_models_to_device(self, model_names):
         pass        # models stay resident in HBM (no VRAM management on this path)
 
-    def load_lora(self, module, lora_config=None, alpha=1, hotload=None, state_dict=None):
+    def load_lora(self, module, lora_config=None, alpha=1, hotload=None, state_dict=None, hot_backend=None):
         """base_pipeline.py:231-266.  hotload=None / False: fuse into the base weights (what inference.py does).
         hotload=True: keep the adapter unfused next to the Linear (AutoWrappedLinear.lora_forward semantics,
         core/vram/layers.py:417-436) so `clear_lora()` can drop it again.  The reference only allows that on modules
-        under its VRAM manager; here the weights are always resident in HBM, so any module with `add_hot_lora` takes it."""
+        under its VRAM manager; here the weights are always resident in HBM, so any module with `add_hot_lora` takes it.
+        hot_backend (with hotload=True; None leaves the module's setting, "torch" unless set before): "torch" evaluates the adapters
+        like the reference, op by op on library GEMMs, and the block Linears that carry one leave the own GEMM's fused stores;
+        "hip" stacks the adapters of every block Linear (one rounding for their sum instead of one per adapter) and applies them with
+        fg_lora_apply_bf16 next to fg_gemm_epilogue_bf16, which keeps its residual / gate / GELU stores.  Still on the "torch" path
+        with "hip": cross-attention k / v (512 context rows, computed once per denoise loop), the fp8 Linear mode, and any Linear whose
+        stacked rank is above 128 or whose in- / out-features are not multiples of 64.  `clear_lora()` leaves the setting alone."""
+        if hot_backend not in (None, "torch", "hip"):
+            raise ValueError(f"hot_backend must be 'torch' or 'hip', got {hot_backend!r}")
         if state_dict is None:
             if isinstance(lora_config, str):
                 lora = load_state_dict(lora_config, torch_dtype=self.torch_dtype, device=self.device)
@@ -420,6 +428,8 @@ class WanVideoPipeline(torch.nn.Module):
         if hotload:
             if not hasattr(module, "add_hot_lora"):
                 raise ValueError("VRAM Management is not enabled. LoRA hotloading is not supported.")
+            if hot_backend is not None:
+                module.hot_lora_backend = hot_backend
             updated = 0
             for name, sub in module.named_modules():
                 a_key, b_key = f"{name}.lora_A.weight", f"{name}.lora_B.weight"

@@ -92,6 +92,26 @@ def gemm_residual(x, a, weight, bias, mod=None, gate_idx=None):
     return hip.gemm_epilogue(a, weight, bias, out=x, residual=True, mod=mod, gate_idx=gate_idx)
 
 
+def stack_hot_loras(per_group, shapes, device, dtype):
+    """The operands of hip.lora_apply for column groups that share an input: per_group[g] = [(alpha * A (r, K), B (Ng, r)), ...] (may be
+    empty), shapes[g] = (K, Ng).  Per group the adapters are concatenated along the rank — sum_i (x A_i^T) B_i^T = (x [A_i]^T) [B_i]^T, the
+    same sum with one rounding instead of one per adapter — and zero-padded to the kernel's rank R (the largest group's, in 32s).
+    Returns (A (G * R, K), B (G * Ng, R)), or None when a group's stacked rank is above the kernel's 128."""
+    rank = max(sum(a.shape[0] for a, _ in ads) for ads in per_group)
+    r = -(-max(rank, 1) // hip.LORA_RANK_TILE) * hip.LORA_RANK_TILE
+    if r > hip.LORA_MAX_RANK:
+        return None
+    a_st = torch.zeros((len(per_group), r, shapes[0][0]), dtype=dtype, device=device)
+    b_st = [torch.zeros((ng, r), dtype=dtype, device=device) for _, ng in shapes]
+    for g, ads in enumerate(per_group):
+        at = 0
+        for a, b in ads:
+            a_st[g, at:at + a.shape[0]] = a.to(device=device, dtype=dtype)
+            b_st[g][:, at:at + a.shape[0]] = b.to(device=device, dtype=dtype)
+            at += a.shape[0]
+    return a_st.view(-1, shapes[0][0]), torch.cat(b_st, 0).contiguous()
+
+
 class RMSNorm(nn.Module):
     def __init__(self, dim, eps=1e-5):
         super().__init__()
@@ -220,6 +240,10 @@ class WanModel(nn.Module):
         self.gelu_epilogue = True
         # hot-loaded (unfused) LoRA adapters: module name -> [(alpha*A (r,in), B (out,r)), ...]; see add_hot_lora
         self.hot_loras = {}
+        # how the block Linears evaluate them: "torch" (default): _hot, the reference's arithmetic op by op on library GEMMs; "hip": the
+        # adapters of a Linear stacked (stack_hot_loras) and applied by fg_lora_apply_bf16 next to the own GEMM's fused store (_hot_apply)
+        self.hot_lora_backend = "torch"
+        self._hot_packs = {}
         # fp8 Linear mode of the blocks (None = bf16 GEMMs); see enable_fp8_linear
         self.fp8_dtype = None
         self._ones = {}
@@ -239,6 +263,7 @@ class WanModel(nn.Module):
         out = super()._apply(fn, *args, **kwargs)
         self.invalidate_fused()
         self._rope_cache = {}
+        self._hot_packs = {}
         return out
 
     # ------------------------------------------------------------------ fp8 Linear mode (core/vram/layers.py:312,321-357)
@@ -281,16 +306,45 @@ class WanModel(nn.Module):
         w = mod.weight
         self.hot_loras.setdefault(name, []).append((lora_a.to(device=w.device, dtype=w.dtype).contiguous(),
                                                     lora_b.to(device=w.device, dtype=w.dtype).contiguous()))
+        self._hot_packs = {}
 
     def clear_hot_loras(self):
         n = len(self.hot_loras)
         self.hot_loras = {}
+        self._hot_packs = {}
         return n
 
     def _hot(self, name, x, out):
         """out (+)= sum of the adapters of `name` applied to x; `out` may be a column slice of a fused projection."""
         for a, b in self.hot_loras.get(name, ()):
             out += (x @ a.T) @ b.T
+        return out
+
+    def _hot_pack(self, names):
+        """hot_lora_backend "hip": the stacked operands (A, B) of the Linears `names` (one, or q, k, v of a block: column groups of one
+        output that share the input), built once and kept until the adapters or the device change.  None: no adapter on any of them.
+        False: shapes fg_lora_apply_bf16 refuses (stacked rank above 128, in- or out-features not a multiple of 64) — the caller takes
+        the "torch" path for that Linear."""
+        if names not in self._hot_packs:
+            per_group = [self.hot_loras.get(n, ()) for n in names]
+            pack = None
+            if any(per_group):
+                ws = [self.get_submodule(n).weight for n in names]
+                fits = all(w.shape == ws[0].shape and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0 for w in ws) and len(names) <= hip.LORA_MAX_GROUPS
+                pack = (fits and stack_hot_loras(per_group, [(w.shape[1], w.shape[0]) for w in ws], ws[0].device, ws[0].dtype)) or False
+            self._hot_packs[names] = pack
+        return self._hot_packs[names]
+
+    def _hot_apply(self, names, x, out, use_hip):
+        """out += the adapters of the Linears `names` (column groups of out) applied to x: one fg_lora_apply_bf16 launch when `use_hip`
+        and the kernel takes the pack, else _hot per Linear."""
+        pack = self._hot_pack(names) if use_hip else False
+        if pack:
+            return hip.lora_apply(x, pack[0], pack[1], out, groups=len(names), mode="add")
+        if pack is False:
+            c = out.shape[-1] // len(names)
+            for j, nm in enumerate(names):
+                self._hot(nm, x, out[..., j * c:(j + 1) * c])
         return out
 
     # ------------------------------------------------------------------ host-side tables
@@ -338,7 +392,7 @@ class WanModel(nn.Module):
         x = x.view(b, f, h, w, px, py, pz, self.out_dim).permute(0, 7, 1, 4, 2, 5, 3, 6)
         return x.reshape(b, self.out_dim, f * px, h * py, w * pz)
 
-    def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, own, lin):
+    def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, own, lin, hip_hot=False):
         """Block i's self-attention half (reference :139-146, :225-226): h = modulate(norm1(x)) in; returns the residual stream after
         x += gate_msa * o(attn(...)) and h = norm3(x).  Yields right after each exchange of a token-sharded run has been started.
         lin: the fp8 Linear closure of the block (None in bf16 mode)."""
@@ -354,9 +408,8 @@ class WanModel(nn.Module):
             qkv = gemm_bias_own(h, wqkv, bqkv)
         else:
             qkv = gemm_bias(h, wqkv, bqkv)
-        if hot:
-            for j, nm in enumerate(("q", "k", "v")):
-                self._hot(f"blocks.{i}.self_attn.{nm}", h, qkv[..., j * c:(j + 1) * c])
+        if hot:      # one launch on the fused buffer (hip backend), or per projection on its column slice
+            self._hot_apply(tuple(f"blocks.{i}.self_attn.{nm}" for nm in "qkv"), h, qkv, hip_hot)
         v = qkv[..., 2 * c:]
         # rope tables per operand: fp64 (cos, sin) for both, or the fp32 interleaved tables of k and q (rope_tables)
         rk, rq = ((cos, None), (sin, None)) if cos.dtype == torch.float32 else ((cos, sin), (cos, sin))
@@ -392,13 +445,16 @@ class WanModel(nn.Module):
             k, v = pending.wait()
             a = sa.attn(q, k, v) if scale is None else sa.attn(q, k, v, scale=scale)
         # x += gate_msa*y ; h = norm3(x)  (reference :225-226)
-        if own and own_gemm_ok(a.shape[1], c, c):      # the gated add happens in the GEMM's store
+        pk = self._hot_pack((f"blocks.{i}.self_attn.o",)) if hip_hot else None
+        if own and own_gemm_ok(a.shape[1], c, c) and pk is not False:      # the gated add happens in the GEMM's store
             x = gemm_residual(x, a, sa.o.weight, sa.o.bias, mod, 2)
+            if pk:      # x += gate_msa * l: the gate distributes over Linear + adapter
+                hip.lora_apply(a, pk[0], pk[1], x, mode="gate", mod=mod, gate_idx=2)
             h = hip.ln_affine(x, blk.norm3.weight, blk.norm3.bias, eps)
         else:
             y = gemm_bias(a, sa.o.weight, sa.o.bias) if fp8 is None else lin(a, 1, sa.o.bias)
             if hot:
-                self._hot(f"blocks.{i}.self_attn.o", a, y)
+                self._hot_apply((f"blocks.{i}.self_attn.o",), a, y, hip_hot)
             if fp8 is not None and not hot and FP8_FOLD:
                 x, h = hip.residual_ln_affine_fp8(x, y, blk.norm3.weight, blk.norm3.bias, eps, mod, 2, x_out=x)
             else:
@@ -449,6 +505,8 @@ class WanModel(nn.Module):
         sharded = shard is not None and shard.active
         hot = bool(self.hot_loras)
         fp8 = self.fp8_dtype
+        # adapters on fg_lora_apply_bf16 next to the own GEMMs (docstring of hot_lora_backend's setter, WanVideoPipeline.load_lora)
+        hip_hot = hot and fp8 is None and self.hot_lora_backend == "hip"
         ctx8 = hip.fp8_quant_rows(context) if fp8 is not None else None      # the text context is the same for all blocks
         mods = [hip.ModTable((blk.modulation.to(mod_rows_t.dtype) + mod_rows_t).contiguous(), first_rows) for blk in blocks]
         # fp8 mode: the four norms of a block feed fp8 Linears only, so they hand over (e4m3 rows, row scales) directly;
@@ -463,7 +521,7 @@ class WanModel(nn.Module):
                 w8 = blk.fp8_weights(fp8)
                 # t: a bf16 tensor (quantised here) or the (fp8 rows, scales) pair a fused norm kernel already produced
                 lin = lambda t, j, bias, act=None: self._scaled_linear(*(t if isinstance(t, tuple) else hip.fp8_quant_rows(t, act)), w8[j], bias)      # noqa: E731
-            own = fp8 is None and not hot and mod.mod_rows in (1, 2)
+            own = fp8 is None and (not hot or hip_hot) and mod.mod_rows in (1, 2)
             if cfg_prefix is not None and i == 0 and "owner" in cfg_prefix:
                 if cfg_prefix.get("taken"):
                     raise RuntimeError("cfg_prefix is shared by exactly two forwards of one step (one computes block 0's self-attention half, "
@@ -485,7 +543,7 @@ class WanModel(nn.Module):
                     cfg_prefix["owner"] = True
             # --- self attention (reference :139-146)
             if not reuse:
-                x, h = yield from self._self_attention_steps(i, blk, mod, x, h, cos, sin, shard, shard_total, own, lin if fp8 is not None else None)
+                x, h = yield from self._self_attention_steps(i, blk, mod, x, h, cos, sin, shard, shard_total, own, lin if fp8 is not None else None, hip_hot)
                 if cfg_prefix is not None and i == 0:
                     cfg_prefix["x_sa"] = x.clone()
             # --- cross attention (reference :170-185)
@@ -494,7 +552,7 @@ class WanModel(nn.Module):
             else:
                 qc = lin(h, 2, ca.q.bias)
             if hot:
-                self._hot(f"blocks.{i}.cross_attn.q", h, qc)
+                self._hot_apply((f"blocks.{i}.cross_attn.q",), h, qc, hip_hot)
             qc = hip.rmsnorm_rope(qc, ca.norm_q.weight, nh, eps)
             if kv_cache is not None and i in kv_cache:
                 kc, vc = kv_cache[i]
@@ -508,13 +566,16 @@ class WanModel(nn.Module):
                     kv_cache[i] = (kc, vc)
             ac = ca.attn(qc, kc, vc)
             # x += y ; h = modulate(norm2(x))  (reference :226-227)
-            if own and own_gemm_ok(ac.shape[1], c, c):
+            pk = self._hot_pack((f"blocks.{i}.cross_attn.o",)) if hip_hot else None
+            if own and own_gemm_ok(ac.shape[1], c, c) and pk is not False:
                 x = gemm_residual(x, ac, ca.o.weight, ca.o.bias)
+                if pk:
+                    hip.lora_apply(ac, pk[0], pk[1], x, mode="add")
                 h = hip.ln_modulate(x, mod, 3, 4, eps)
             else:
                 y = gemm_bias(ac, ca.o.weight, ca.o.bias) if fp8 is None else lin(ac, 4, ca.o.bias)
                 if hot:
-                    self._hot(f"blocks.{i}.cross_attn.o", ac, y)
+                    self._hot_apply((f"blocks.{i}.cross_attn.o",), ac, y, hip_hot)
                 if fold8:
                     x, h = hip.residual_ln_modulate_fp8(x, y, mod, None, 3, 4, eps, x_out=x)
                 else:
@@ -526,6 +587,10 @@ class WanModel(nn.Module):
                     self._hot(f"blocks.{i}.ffn.0", h, pre)
                 y = lin(pre, 6, blk.ffn[2].bias, "gelu_tanh")
                 f = None
+            elif hip_hot and self._hot_pack((f"blocks.{i}.ffn.0",)):      # the adapter adds to the pre-activation: GELU moves from the GEMM's store into the adapter kernel's
+                pk = self._hot_pack((f"blocks.{i}.ffn.0",))
+                pre = (gemm_bias_own if GEMM_BACKEND == "all" and own_gemm_ok(h.shape[1], blk.ffn[0].weight.shape[0], c) else gemm_bias)(h, blk.ffn[0].weight, blk.ffn[0].bias)
+                f = hip.lora_apply(h, pk[0], pk[1], pre, mode="gelu_tanh")
             elif hot and f"blocks.{i}.ffn.0" in self.hot_loras:      # the adapter adds to the pre-activation: no epilogue fusion
                 f = hip.activation(self._hot(f"blocks.{i}.ffn.0", h, gemm_bias(h, blk.ffn[0].weight, blk.ffn[0].bias)), "gelu_tanh")
             elif GEMM_BACKEND == "all" and own_gemm_ok(h.shape[1], blk.ffn[0].weight.shape[0], c):      # GELU(tanh) in the own GEMM's store
@@ -534,8 +599,11 @@ class WanModel(nn.Module):
                 f = gemm_bias_gelu(h, blk.ffn[0].weight, blk.ffn[0].bias)
             else:
                 f = hip.activation(gemm_bias(h, blk.ffn[0].weight, blk.ffn[0].bias), "gelu_tanh")
-            if own and GEMM_BACKEND != "fused-ffn2" and own_gemm_ok(f.shape[1], c, f.shape[2]):      # x += gate_mlp * ffn.2(f) in the store
+            pk = self._hot_pack((f"blocks.{i}.ffn.2",)) if hip_hot else None
+            if own and GEMM_BACKEND != "fused-ffn2" and own_gemm_ok(f.shape[1], c, f.shape[2]) and pk is not False:      # x += gate_mlp * ffn.2(f) in the store
                 x = gemm_residual(x, f, blk.ffn[2].weight, blk.ffn[2].bias, mod, 5)
+                if pk:
+                    hip.lora_apply(f, pk[0], pk[1], x, mode="gate", mod=mod, gate_idx=5)
                 if i + 1 < len(blocks):
                     h = hip.ln_modulate(x, mods[i + 1], 0, 1, eps, out=h)
                 continue
@@ -544,7 +612,7 @@ class WanModel(nn.Module):
             if hot and f"blocks.{i}.ffn.2" in self.hot_loras:
                 if f is None:
                     f = hip.activation(pre.clone(), "gelu_tanh")
-                self._hot(f"blocks.{i}.ffn.2", f, y)
+                self._hot_apply((f"blocks.{i}.ffn.2",), f, y, hip_hot)
             if i + 1 < len(blocks) and fold8:
                 x, h = hip.residual_ln_modulate_fp8(x, y, mod, 5, 0, 1, eps, x_out=x, norm_mod=mods[i + 1])
             elif i + 1 < len(blocks):   # x += gate_mlp*y fused with the NEXT block's modulate(norm1(x))

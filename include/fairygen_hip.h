@@ -34,7 +34,7 @@ extern "C" {
 
 typedef void* fg_stream_t;   /* hipStream_t */
 
-int         fg_version(void);            /* ABI version, currently 3 */
+int         fg_version(void);            /* ABI version, currently 4 */
 const char* fg_last_error(void);         /* thread-local, valid until the next failing call */
 
 /* ------------------------------------------------------------------ DiT token-side kernels (HBM-bound)
@@ -100,6 +100,21 @@ int64_t fg_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int fg_gemm_epilogue_bf16(const void* a, int64_t lda, const void* w, const void* bias, void* c, int64_t ldc,
                           int64_t M, int64_t N, int64_t K, int mode, const void* gate, int64_t gate_rows, int64_t gate_ld,
                           int64_t first_rows, void* workspace, fg_stream_t stream);
+
+/* Hot-loaded (unfused) LoRA adapters of one Linear, AutoWrappedLinear.lora_forward (core/vram/layers.py:417-436: `out = out + x @ A^T @ B^T`
+ * per adapter, in the pipeline dtype), for the adapters stacked along the rank and for G column groups that share the input x
+ * (G = 3: q | k | v on the fused qkv buffer; else 1), in ONE launch next to fg_gemm_epilogue_bf16:
+ *     t_g = bf16(x[M, K] A_g[R, K]^T),  l_g = bf16(t_g[M, R] B_g[Ng, R]^T)      (fp32 accumulate, one rounding each)
+ *     out[:, g*Ng:(g+1)*Ng] = epi(out[:, g*Ng:(g+1)*Ng], l_g)
+ * mode 0: l (plain write);  1: out + l;  2: out + bf16(gate * l), the gate table as in mode 2 of fg_gemm_epilogue_bf16 (1 or 2 rows of
+ * gate_ld elements, rows < first_rows take row 0; here 16-byte aligned rows);  4: gelu_tanh(bf16(out + l)), the GEMM's GELU.
+ * x: leading dimension ldx; out: leading dimension ldc >= G*Ng; a: the stacked (G*R, K) matrix (alpha folded in), b: the stacked
+ * (G*Ng, R) matrix, both contiguous.  R is the per-group rank, padded by the host with zero rows of A / zero columns of B to 32, 64, 96
+ * or 128; K %% 64 == 0, Ng %% 64 == 0, 1 <= G <= 4, ldx %% 8 == 0, ldc %% 8 == 0.  Rows >= M and columns >= G*Ng are not touched.
+ * x is read once per pass: one pass for G = 1 and for (G = 3, R = 32), else one per group. */
+int fg_lora_apply_bf16(const void* x, int64_t ldx, const void* a, const void* b, void* out, int64_t ldc, int64_t M, int64_t K,
+                       int64_t Ng, int64_t R, int64_t G, int mode, const void* gate, int64_t gate_rows, int64_t gate_ld,
+                       int64_t first_rows, fg_stream_t stream);
 
 /* Diagnostics for the persistent GEMM's unit scheduler: launch only `workgroups` workgroups (a multiple of the XCD count, at most one
  * per CU; 0 = one per CU again).  The units of a launch are fixed by the shape; workgroups take them from per-XCD cursors, so the result

@@ -1,0 +1,91 @@
+"""Time the DiT part of one denoise step (both CFG forwards) of the headline configuration with a rank-32 adapter on every block Linear:
+hot-loaded on each backend of WanModel.hot_lora_backend, and fused into the weights (the floor).
+
+    python tools/hot_lora_step.py --steps 3 --order torch,hip,torch,fused
+
+Every leg builds the 30-block model from the same seeds, warms up one step and reports the median of `--steps` timed steps (host clock
+around a device synchronise).  "torch" is the code path of hotload=True before the backend existed.  Prints one line per leg and a
+JSON line at the end."""
+import argparse
+import gc
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from fairygen_amd import hip, synthetic  # noqa: E402
+from fairygen_amd.loader import TI2V_5B_DIT_KWARGS  # noqa: E402
+from fairygen_amd.wan_video import WanVideoPipeline, model_fn_wan_video  # noqa: E402
+from fairygen_amd.wan_video_dit import WanModel  # noqa: E402
+
+
+def build(leg, layers, dev):
+    cfg = dict(TI2V_5B_DIT_KWARGS)
+    if layers:
+        cfg["num_layers"] = layers
+    shapes = synthetic.dit_shapes(cfg)
+    with torch.device("meta"):
+        dit = WanModel(**cfg)
+    dit.load_state_dict(synthetic.random_state_dict(shapes, seed=1234, device=dev), assign=True)
+    pipe = WanVideoPipeline(device=dev, torch_dtype=torch.bfloat16)
+    pipe.dit = dit.to(device=dev, dtype=torch.bfloat16).eval()
+    lora = synthetic.random_lora(shapes, rank=32, seed=4321)
+    if leg == "fused":
+        pipe.load_lora(pipe.dit, state_dict=lora, alpha=1)
+    else:
+        pipe.load_lora(pipe.dit, state_dict=lora, alpha=1, hotload=True, hot_backend=leg)
+    return pipe
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--layers", type=int, default=0, help="debug: fewer DiT layers")
+    ap.add_argument("--height", type=int, default=704)
+    ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--frames", type=int, default=121)
+    ap.add_argument("--order", default="torch,hip,torch,fused")
+    a = ap.parse_args()
+    hip.load()
+    dev = "cuda"
+    g = torch.Generator("cpu").manual_seed(0)
+    rnd = lambda *s: torch.randn(s, generator=g).to(torch.bfloat16).to(dev)      # noqa: E731
+    lat = rnd(1, 48, (a.frames - 1) // 4 + 1, a.height // 16, a.width // 16)
+    ctx_p, ctx_n = rnd(1, 512, 4096), rnd(1, 512, 4096)
+    ts = torch.tensor([900.0]).to(torch.bfloat16)
+    results, outs = [], {}
+    for leg in a.order.split(","):
+        pipe = build(leg, a.layers, dev)
+
+        def step():
+            with torch.no_grad():
+                p = model_fn_wan_video(pipe.dit, latents=lat, timestep=ts, context=ctx_p, fuse_vae_embedding_in_latents=True)
+                n = model_fn_wan_video(pipe.dit, latents=lat, timestep=ts, context=ctx_n, fuse_vae_embedding_in_latents=True)
+            return n + 5.0 * (p - n)
+        out = step()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(a.steps):
+            t0 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        times.sort()
+        med = times[len(times) // 2]
+        ref = outs.setdefault("first", out.float())
+        diff = (out.float() - ref).abs().max().item()
+        print(f"{leg:6s}: DiT step (2 CFG forwards) median {med * 1e3:8.1f} ms, min {times[0] * 1e3:8.1f} ms; max|out - first leg's| = {diff:.4f} "
+              f"(max|out| = {out.float().abs().max().item():.2f})", flush=True)
+        results.append({"leg": leg, "step_ms": round(med * 1e3, 2), "min_ms": round(times[0] * 1e3, 2), "max_abs_diff_vs_first_leg": diff})
+        del pipe, out
+        gc.collect()
+        torch.cuda.empty_cache()
+    print(json.dumps({"tool": "hot_lora_step", "height": a.height, "width": a.width, "frames": a.frames, "layers": a.layers or 30, "steps": a.steps,
+                      "legs": results}))
+
+
+if __name__ == "__main__":
+    main()

@@ -3,6 +3,7 @@
     python tools/microbench.py attn --nq 27280 --nkv 27280 --heads 24
     python tools/microbench.py conv --cin 1024 --cout 1024 --t 1 --h 44 --w 80 --kt 3 --ks 3
     python tools/microbench.py elementwise --rows 27280
+    python tools/microbench.py lora --rows 27280 --rank 32
 """
 import argparse
 import os
@@ -28,9 +29,59 @@ def timeit(fn, iters, warmup=3):
     return ts[len(ts) // 2], ts[0]
 
 
+def lora_table(a, rnd):
+    """Per block Linear with a hot-loaded rank-`--rank` adapter: the Linear plus its adapter (and the residual / gate / GELU that
+    follows it) as each backend of WanModel.hot_lora_backend evaluates them — "torch": library GEMM, x @ A^T @ B^T per adapter, a
+    separate elementwise kernel; "hip": fg_gemm_epilogue_bf16 with its fused store, then fg_lora_apply_bf16 — and the adapter kernel alone."""
+    from fairygen_amd.wan_video_dit import stack_hot_loras
+    m, r, c, ff = a.rows, a.rank, 3072, 14336
+    table = rnd(2, 6, c)
+    mod = hip.ModTable(table, m // 3)
+    print(f"rows {m}, rank {r}; times in us (median of {a.iters})")
+    for name, k, n, groups, mode in [("self_attn.qkv", c, 3 * c, 3, "add"), ("self_attn.o", c, c, 1, "gate"), ("cross_attn.q", c, c, 1, "add"),
+                                     ("cross_attn.o", c, c, 1, "resid"), ("ffn.0", c, ff, 1, "gelu_tanh"), ("ffn.2", ff, c, 1, "gate")]:
+        x, w, bias, res = rnd(1, m, k), rnd(n, k) * 0.02, rnd(n) * 0.02, rnd(1, m, c)
+        ng = n // groups
+        ads = [[(rnd(r, k) * 0.02, rnd(ng, r) * 0.02)] for _ in range(groups)]
+        a_st, b_st = stack_hot_loras(ads, [(k, ng)] * groups, x.device, x.dtype)
+        gi = 2 if name == "self_attn.o" else 5
+
+        def torch_path():
+            y = torch.nn.functional.linear(x, w, bias)
+            for g, group in enumerate(ads):
+                for la, lb in group:
+                    y[..., g * ng:(g + 1) * ng] += (x @ la.T) @ lb.T
+            if mode == "gate":
+                hip.gate_residual(res, y, mod, gi, out=res)
+            elif mode == "resid":
+                hip.gate_residual(res, y, out=res)
+            elif mode == "gelu_tanh":
+                hip.activation(y, "gelu_tanh")
+            return y
+
+        def hip_path():
+            if mode == "gate":
+                hip.gemm_epilogue(x, w, bias, out=res, residual=True, mod=mod, gate_idx=gi)
+                return hip.lora_apply(x, a_st, b_st, res, mode="gate", mod=mod, gate_idx=gi)
+            if mode == "resid":
+                hip.gemm_epilogue(x, w, bias, out=res, residual=True)
+                return hip.lora_apply(x, a_st, b_st, res, mode="add")
+            return hip.lora_apply(x, a_st, b_st, hip.gemm_epilogue(x, w, bias), groups=groups, mode=mode)
+
+        y = torch.empty((1, m, n), dtype=x.dtype, device=x.device)
+        k_mode = "add" if mode == "resid" else mode
+        kernel = lambda: hip.lora_apply(x, a_st, b_st, res if mode in ("gate", "resid") else y, groups=groups, mode=k_mode, mod=mod, gate_idx=gi)  # noqa: E731
+        fused = (lambda: hip.gemm_epilogue(x, w, bias, out=res, residual=True, mod=mod if mode == "gate" else None, gate_idx=gi)) if mode in ("gate", "resid") \
+            else (lambda: hip.gemm_epilogue(x, w, bias, act="gelu_tanh" if mode == "gelu_tanh" else None))
+        t_torch, t_hip, t_k, t_f = (timeit(fn, a.iters)[0] * 1e3 for fn in (torch_path, hip_path, kernel, fused))
+        moved = 2.0 * m * (k + (1 if mode == "write" else 2) * n)
+        print(f"{name:14s} K={k:5d} N={n:5d}: torch {t_torch:7.1f}   hip {t_hip:7.1f}   lora_apply alone {t_k:6.1f} ({moved / t_k / 1e6:.2f} TB/s of x + out in + out out)   "
+              f"adapter fused into the weights {t_f:7.1f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["attn", "conv", "elementwise"])
+    ap.add_argument("what", choices=["attn", "conv", "elementwise", "lora"])
     ap.add_argument("--nq", type=int, default=27280)
     ap.add_argument("--nkv", type=int, default=27280)
     ap.add_argument("--heads", type=int, default=24)
@@ -43,6 +94,7 @@ def main():
     ap.add_argument("--kt", type=int, default=3)
     ap.add_argument("--ks", type=int, default=3)
     ap.add_argument("--rows", type=int, default=27280)
+    ap.add_argument("--rank", type=int, default=32)
     ap.add_argument("--interleaved", action="store_true")
     ap.add_argument("--per-head", action="store_true")
     ap.add_argument("--attn-scale", default="pow2", choices=["pow2", "model", "both"],
@@ -52,6 +104,9 @@ def main():
     dev = "cuda"
     g = torch.Generator(dev).manual_seed(0)
     rnd = lambda *s: torch.randn(s, generator=g, device=dev, dtype=torch.float32).to(torch.bfloat16)  # noqa: E731
+    if a.what == "lora":
+        lora_table(a, rnd)
+        return
     if a.what == "attn":
         c = a.heads * 128
         if a.interleaved:      # q | k | v column slices of one (N, 3c) buffer, as after the Ulysses all-to-all
