@@ -111,9 +111,11 @@ __device__ __forceinline__ uint32_t cvt2_fp8(float a, float b) {
 // The same normalised row as norm_store, but handed to the fp8 Linear that consumes it (AutoWrappedLinear.fp8_linear,
 // core/vram/layers.py:331-342) without a trip through HBM: the bf16-rounded values stay in registers, the row maximum gives the
 // dynamic scale, the row leaves as e4m3 bytes + one fp32 scale — exactly fg_fp8_quant_rows_bf16's arithmetic on norm_store's output.
-template <int MODE>
+// DUAL: the bf16 row is written as well (out16, norm_store's bytes), for a hot-loaded LoRA adapter that reads the bf16 activation next to
+// the fp8 Linear (AutoWrappedLinear.forward, core/vram/layers.py:429-436).
+template <int MODE, bool DUAL = false>
 __device__ __forceinline__ void norm_store_fp8(Row& r, int C, int lane, float eps, const bf16* p0, const bf16* p1,
-                                               uint8_t* out8, float* scale_out, float fp8_max) {
+                                               uint8_t* out8, float* scale_out, float fp8_max, bf16* out16 = nullptr) {
     const int nvec = C >> 3;
     float mean, rstd;
     row_moments(r, C, lane, eps, mean, rstd);
@@ -138,6 +140,7 @@ __device__ __forceinline__ void norm_store_fp8(Row& r, int C, int lane, float ep
                 r.v[i][j] = rbf(o);
                 amax = fmaxf(amax, fabsf(r.v[i][j]));
             }
+            if (DUAL) st8(out16 + (int64_t)vi * 8, r.v[i]);
         }
     }
     amax = wave_max(amax);
@@ -167,6 +170,21 @@ __global__ FG_ROW_BOUNDS void ln_modulate_fp8_kernel(const bf16* __restrict__ x,
     load_row(x + row * C, C, lane, r);
     const int64_t m = mod_row(row, mod_rows, first_rows);
     norm_store_fp8<0>(r, C, lane, eps, shift + m * mod_ld, scale + m * mod_ld, out8 + row * C, scale_out + row, fp8_max);
+}
+
+// (bf16 row, e4m3 row, scale) of one norm in one pass.  MODE 0: p0 = shift, p1 = scale (modulation rows); 1: p0 = weight, p1 = bias.
+template <int MODE>
+__global__ FG_ROW_BOUNDS void ln_dual_kernel(const bf16* __restrict__ x, const bf16* __restrict__ p0, const bf16* __restrict__ p1,
+                                             bf16* __restrict__ out, uint8_t* __restrict__ out8, float* __restrict__ scale_out,
+                                             int64_t rows, int C, float eps, int64_t mod_rows, int64_t first_rows, int64_t mod_ld,
+                                             float fp8_max) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    Row r;
+    load_row(x + row * C, C, lane, r);
+    const int64_t m = MODE == 0 ? mod_row(row, mod_rows, first_rows) : 0;
+    norm_store_fp8<MODE, true>(r, C, lane, eps, p0 + m * mod_ld, p1 + m * mod_ld, out8 + row * C, scale_out + row, fp8_max, out + row * C);
 }
 
 __global__ FG_ROW_BOUNDS void ln_modulate_kernel(const bf16* __restrict__ x, const bf16* __restrict__ shift,
@@ -397,6 +415,33 @@ int fg_ln_modulate_fp8_bf16(const void* x, const void* shift, const void* scale,
     hipLaunchKernelGGL(ln_modulate_fp8_kernel, row_grid(rows), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (const bf16*)shift,
                        (const bf16*)scale, (uint8_t*)out_fp8, out_scale, rows, C, eps, mod_rows, first_rows, mod_ld, fp8_max);
     return fg_launch_status("fg_ln_modulate_fp8_bf16");
+}
+
+int fg_ln_modulate_dual_bf16(const void* x, const void* shift, const void* scale, void* out, void* out_fp8, float* out_scale,
+                             int64_t rows, int C, float eps, int64_t mod_rows, int64_t first_rows, int64_t mod_ld, float fp8_max,
+                             fg_stream_t stream) {
+    if (int e = check_rows("fg_ln_modulate_dual_bf16", rows, C, mod_rows, first_rows)) return e;
+    FG_CHECK_ARG(x && shift && scale && out && out_fp8 && out_scale, "fg_ln_modulate_dual_bf16: null pointer");
+    FG_CHECK_ARG(FG_ALIGNED16(x) && FG_ALIGNED16(shift) && FG_ALIGNED16(scale) && FG_ALIGNED16(out) && (((uintptr_t)out_fp8) & 7) == 0 &&
+                     mod_ld % 8 == 0 && fp8_max > 0.f,
+                 "fg_ln_modulate_dual_bf16: pointers / mod_ld must be 16-byte aligned (out_fp8: 8), fp8_max positive");
+    if (rows == 0) return FG_OK;
+    hipLaunchKernelGGL(ln_dual_kernel<0>, row_grid(rows), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (const bf16*)shift,
+                       (const bf16*)scale, (bf16*)out, (uint8_t*)out_fp8, out_scale, rows, C, eps, mod_rows, first_rows, mod_ld, fp8_max);
+    return fg_launch_status("fg_ln_modulate_dual_bf16");
+}
+
+int fg_ln_affine_dual_bf16(const void* x, const void* w, const void* b, void* out, void* out_fp8, float* out_scale, int64_t rows, int C,
+                           float eps, float fp8_max, fg_stream_t stream) {
+    if (int e = check_rows("fg_ln_affine_dual_bf16", rows, C, 1, 0)) return e;
+    FG_CHECK_ARG(x && w && b && out && out_fp8 && out_scale, "fg_ln_affine_dual_bf16: null pointer");
+    FG_CHECK_ARG(FG_ALIGNED16(x) && FG_ALIGNED16(w) && FG_ALIGNED16(b) && FG_ALIGNED16(out) && (((uintptr_t)out_fp8) & 7) == 0 &&
+                     fp8_max > 0.f,
+                 "fg_ln_affine_dual_bf16: pointers must be 16-byte aligned (out_fp8: 8), fp8_max positive");
+    if (rows == 0) return FG_OK;
+    hipLaunchKernelGGL(ln_dual_kernel<1>, row_grid(rows), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (const bf16*)w,
+                       (const bf16*)b, (bf16*)out, (uint8_t*)out_fp8, out_scale, rows, C, eps, (int64_t)1, (int64_t)0, (int64_t)0, fp8_max);
+    return fg_launch_status("fg_ln_affine_dual_bf16");
 }
 
 int fg_residual_ln_fp8_bf16(const void* x, const void* y, const void* gate, void* x_out, const void* p0, const void* p1,

@@ -13,7 +13,7 @@ import torch
 _LIB_PATH = os.environ.get("FAIRYGEN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfairygen_hip.so")
 _lib = None
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _i64, _i32, _f32, _vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
@@ -23,6 +23,8 @@ _SIGNATURES = {
     "fg_ln_affine_bf16": [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
     "fg_ln_modulate_fp8_bf16": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i64, _i64, _i64, _f32, _vp],
     "fg_residual_ln_fp8_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _i64, _i64, _i64, _f32, _vp],
+    "fg_ln_modulate_dual_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i64, _i64, _i64, _f32, _vp],
+    "fg_ln_affine_dual_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _vp],
     "fg_gate_residual_bf16": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _i64, _vp],
     "fg_residual_ln_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _i64, _i64, _i64, _vp],
     "fg_rmsnorm_rope_bf16": [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _f32, _vp],
@@ -228,6 +230,27 @@ def ln_modulate_fp8(x, mod, shift_idx, scale_idx, eps):
     _call("fg_ln_modulate_fp8_bf16", _ptr(x), mod.vec(shift_idx), mod.vec(scale_idx), _ptr(q), _ptr(sc), rows, c, eps,
           *_mod_args(mod, rows), FP8_E4M3FN_MAX, _stream(x))
     return q, sc
+
+
+def ln_modulate_dual(x, mod, shift_idx, scale_idx, eps, out=None):
+    """ln_modulate for a norm that feeds an fp8 Linear AND a hot-loaded adapter: returns (out, (x_fp8, scale)) — the bf16 row of
+    ln_modulate and the pair of ln_modulate_fp8, bit for bit, in one pass over x."""
+    rows, c = _rows(x, "x")
+    out = torch.empty_like(x) if out is None else _dev(out, "out")
+    q, sc = _fp8_rows_out(x)
+    _call("fg_ln_modulate_dual_bf16", _ptr(x), mod.vec(shift_idx), mod.vec(scale_idx), _ptr(out), _ptr(q), _ptr(sc), rows, c, eps,
+          *_mod_args(mod, rows), FP8_E4M3FN_MAX, _stream(x))
+    return out, (q, sc)
+
+
+def ln_affine_dual(x, w, b, eps, out=None):
+    """ln_affine (norm3) with both outputs: returns (out, (x_fp8, scale)) = (ln_affine(x, ...), fp8_quant_rows of it) in one pass."""
+    rows, c = _rows(x, "x")
+    _dev(w, "w"), _dev(b, "b")
+    out = torch.empty_like(x) if out is None else _dev(out, "out")
+    q, sc = _fp8_rows_out(x)
+    _call("fg_ln_affine_dual_bf16", _ptr(x), _ptr(w), _ptr(b), _ptr(out), _ptr(q), _ptr(sc), rows, c, eps, FP8_E4M3FN_MAX, _stream(x))
+    return out, (q, sc)
 
 
 def residual_ln_modulate_fp8(x, y, mod, gate_idx, shift_idx, scale_idx, eps, x_out=None, norm_mod=None):

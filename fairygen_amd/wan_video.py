@@ -410,9 +410,12 @@ class WanVideoPipeline(torch.nn.Module):
         hot_backend (with hotload=True; None leaves the module's setting, "torch" unless set before): "torch" evaluates the adapters
         like the reference, op by op on library GEMMs, and the block Linears that carry one leave the own GEMM's fused stores;
         "hip" stacks the adapters of every block Linear (one rounding for their sum instead of one per adapter) and applies them with
-        fg_lora_apply_bf16 next to fg_gemm_epilogue_bf16, which keeps its residual / gate / GELU stores.  Still on the "torch" path
-        with "hip": cross-attention k / v (512 context rows, computed once per denoise loop), the fp8 Linear mode, and any Linear whose
-        stacked rank is above 128 or whose in- / out-features are not multiples of 64.  `clear_lora()` leaves the setting alone."""
+        fg_lora_apply_bf16 next to fg_gemm_epilogue_bf16, which keeps its residual / gate / GELU stores — or, in the fp8 Linear mode
+        (enable_fp8_linear), next to fg_gemm_fp8_bf16 with its residual / gate stores: the adapters read the bf16 activation, the fp8
+        GEMM its e4m3 form, and the block's norms write both in one pass (fg_ln_modulate_dual_bf16 / fg_ln_affine_dual_bf16).  Still
+        on the "torch" path with "hip": cross-attention k / v (512 context rows, computed once per denoise loop) and any Linear whose
+        stacked rank is above 128, whose in- / out-features are not multiples of 64 or, in the fp8 mode, whose shape the own fp8 GEMM
+        does not take.  `clear_lora()` leaves the setting alone."""
         if hot_backend not in (None, "torch", "hip"):
             raise ValueError(f"hot_backend must be 'torch' or 'hip', got {hot_backend!r}")
         if state_dict is None:

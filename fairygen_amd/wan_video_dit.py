@@ -87,6 +87,11 @@ def gemm_fp8_own(xq, scale_a, w8, bias):
     return hip.gemm_fp8(xq, scale_a, w8, bias, lead_shape=(1, xq.shape[0]))
 
 
+def fp8_own_ok(n, k):
+    """Shapes fg_gemm_fp8_bf16 takes (and FAIRYGEN_FP8_GEMM leaves to it); everything else goes to torch._scaled_mm."""
+    return FP8_GEMM == "own" and n % 256 == 0 and k % 256 == 0
+
+
 def gemm_residual(x, a, weight, bias, mod=None, gate_idx=None):
     """x (the residual stream, contiguous, updated in place) += gate * Linear(a); gate = vector gate_idx of mod, or 1."""
     return hip.gemm_epilogue(a, weight, bias, out=x, residual=True, mod=mod, gate_idx=gate_idx)
@@ -241,7 +246,8 @@ class WanModel(nn.Module):
         # hot-loaded (unfused) LoRA adapters: module name -> [(alpha*A (r,in), B (out,r)), ...]; see add_hot_lora
         self.hot_loras = {}
         # how the block Linears evaluate them: "torch" (default): _hot, the reference's arithmetic op by op on library GEMMs; "hip": the
-        # adapters of a Linear stacked (stack_hot_loras) and applied by fg_lora_apply_bf16 next to the own GEMM's fused store (_hot_apply)
+        # adapters of a Linear stacked (stack_hot_loras) and applied by fg_lora_apply_bf16 next to the own GEMM's fused store (_hot_apply),
+        # the bf16 GEMM's or, in the fp8 Linear mode, fg_gemm_fp8_bf16's (_fp8_hot_residual; the adapter reads the bf16 activation)
         self.hot_lora_backend = "torch"
         self._hot_packs = {}
         # fp8 Linear mode of the blocks (None = bf16 GEMMs); see enable_fp8_linear
@@ -284,7 +290,7 @@ class WanModel(nn.Module):
         """fp8_linear's matmul (:347-354: torch._scaled_mm with row-wise scale_a, unit scale_b, bf16 bias, bf16 out): on this repo's e4m3
         MFMA kernel (fg_gemm_fp8_bf16), or — FAIRYGEN_FP8_GEMM=lib, and for shapes the kernel does not take — the library call itself."""
         n = w8.shape[0]
-        if FP8_GEMM == "own" and n % 256 == 0 and xq.shape[1] % 256 == 0:
+        if fp8_own_ok(n, xq.shape[1]):
             return gemm_fp8_own(xq, scale_a, w8, bias)
         key = (n, xq.device)
         if key not in self._ones:
@@ -347,6 +353,22 @@ class WanModel(nn.Module):
                 self._hot(nm, x, out[..., j * c:(j + 1) * c])
         return out
 
+    def _fp8_hot_residual(self, name, t, w8, bias, x, mod, gate_idx):
+        """fp8 Linear mode with hot_lora_backend "hip": x (the residual stream, in place) += gate * (fp8_linear(t) + adapters of `name`
+        on the bf16 t), gate = vector gate_idx of mod or 1 (AutoWrappedLinear.forward, core/vram/layers.py:429-436, then GateModule).
+        The add happens in fg_gemm_fp8_bf16's store and in fg_lora_apply_bf16 (the gate distributes over Linear + adapter) where the own
+        fp8 GEMM takes the shape and the adapter kernel the pack; else the "torch" backend's ops for this Linear and one residual pass."""
+        t8 = hip.fp8_quant_rows(t)
+        pk = self._hot_pack((name,))
+        gmod = mod if gate_idx is not None else None
+        if fp8_own_ok(w8.shape[0], w8.shape[1]) and mod.mod_rows in (1, 2) and pk is not False:
+            hip.gemm_fp8(*t8, w8, bias, out=x, residual=True, mod=gmod, gate_idx=gate_idx)
+            if pk:
+                hip.lora_apply(t, pk[0], pk[1], x, mode="add" if gmod is None else "gate", mod=gmod, gate_idx=gate_idx)
+            return x
+        y = self._hot_apply((name,), t, self._scaled_linear(*t8, w8, bias), True)
+        return hip.gate_residual(x, y, gmod, gate_idx, out=x)
+
     # ------------------------------------------------------------------ host-side tables
     def rope_tables(self, f, h, w, device):
         """(cos, sin) of the per-token complex table, tokens frame-major (pipelines/wan_video.py:1271-1275): two fp64
@@ -395,21 +417,26 @@ class WanModel(nn.Module):
     def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, own, lin, hip_hot=False):
         """Block i's self-attention half (reference :139-146, :225-226): h = modulate(norm1(x)) in; returns the residual stream after
         x += gate_msa * o(attn(...)) and h = norm3(x).  Yields right after each exchange of a token-sharded run has been started.
-        lin: the fp8 Linear closure of the block (None in bf16 mode)."""
+        lin: the fp8 Linear closure of the block (None in bf16 mode).  fp8 mode with hip_hot: h comes and goes as the dual-output norm's
+        (bf16 row, (e4m3 rows, scales)) — the fp8 Linears take the pair, the adapters the bf16 row."""
         c, nh, eps = self.dim, self.num_heads, self.eps
         fp8 = self.fp8_dtype if lin is not None else None
         hot = bool(self.hot_loras)
         sharded = shard is not None and shard.active
         wqkv, bqkv, _, _ = blk.fused_weights()
         sa = blk.self_attn
-        if fp8 is not None:
+        hot8 = hip_hot and fp8 is not None
+        if hot8:
+            h, h8 = h
+            qkv = lin(h8, 0, bqkv)
+        elif fp8 is not None:
             qkv = lin(h, 0, bqkv)
         elif GEMM_BACKEND == "all" and own_gemm_ok(h.shape[1], 3 * c, c):      # a plain Linear: hot adapters add to its output below
             qkv = gemm_bias_own(h, wqkv, bqkv)
         else:
             qkv = gemm_bias(h, wqkv, bqkv)
         if hot:      # one launch on the fused buffer (hip backend), or per projection on its column slice
-            self._hot_apply(tuple(f"blocks.{i}.self_attn.{nm}" for nm in "qkv"), h, qkv, hip_hot)
+            self._hot_apply(tuple(f"blocks.{i}.self_attn.{nm}" for nm in "qkv"), h, qkv, hip_hot and (not hot8 or fp8_own_ok(3 * c, c)))
         v = qkv[..., 2 * c:]
         # rope tables per operand: fp64 (cos, sin) for both, or the fp32 interleaved tables of k and q (rope_tables)
         rk, rq = ((cos, None), (sin, None)) if cos.dtype == torch.float32 else ((cos, sin), (cos, sin))
@@ -445,6 +472,9 @@ class WanModel(nn.Module):
             k, v = pending.wait()
             a = sa.attn(q, k, v) if scale is None else sa.attn(q, k, v, scale=scale)
         # x += gate_msa*y ; h = norm3(x)  (reference :225-226)
+        if hot8:      # the gated add in the fp8 GEMM's store, then norm3 with both outputs
+            x = self._fp8_hot_residual(f"blocks.{i}.self_attn.o", a, blk.fp8_weights(fp8)[1], sa.o.bias, x, mod, 2)
+            return x, hip.ln_affine_dual(x, blk.norm3.weight, blk.norm3.bias, eps)
         pk = self._hot_pack((f"blocks.{i}.self_attn.o",)) if hip_hot else None
         if own and own_gemm_ok(a.shape[1], c, c) and pk is not False:      # the gated add happens in the GEMM's store
             x = gemm_residual(x, a, sa.o.weight, sa.o.bias, mod, 2)
@@ -460,6 +490,42 @@ class WanModel(nn.Module):
             else:
                 x, h = hip.residual_ln_affine(x, y, blk.norm3.weight, blk.norm3.bias, eps, mod, 2, x_out=x)
         return x, h
+
+    def _block_tail_fp8_hot(self, i, blk, mod, next_mod, x, h, context, ctx8, lin, kv_cache):
+        """Block i after its self-attention half in the fp8 Linear mode with hot_lora_backend "hip" (reference :170-185, :208-209,
+        :226-228 on AutoWrappedLinear.forward, core/vram/layers.py:429-436): cross-attention, ffn and the next block's norm1 + modulate.
+        h = norm3(x) in, as (bf16 row, (e4m3 rows, scales)); returns x and the next h in the same form (None after the last block)."""
+        c, nh, eps = self.dim, self.num_heads, self.eps
+        ca, w8 = blk.cross_attn, blk.fp8_weights(self.fp8_dtype)
+        _, _, _, bkv_c = blk.fused_weights()
+        h, h8 = h
+        qc = self._hot_apply((f"blocks.{i}.cross_attn.q",), h, lin(h8, 2, ca.q.bias), fp8_own_ok(c, c))
+        qc = hip.rmsnorm_rope(qc, ca.norm_q.weight, nh, eps)
+        if kv_cache is not None and i in kv_cache:
+            kc, vc = kv_cache[i]
+        else:      # 512 context rows, once per denoise loop with a kv_cache: the "torch" backend's ops
+            kvc = self._scaled_linear(*ctx8, w8[3], bkv_c)
+            self._hot(f"blocks.{i}.cross_attn.k", context, kvc[..., :c])
+            self._hot(f"blocks.{i}.cross_attn.v", context, kvc[..., c:])
+            kc, vc = hip.rmsnorm_rope(kvc[..., :c], ca.norm_k.weight, nh, eps), kvc[..., c:]
+            if kv_cache is not None:
+                kv_cache[i] = (kc, vc)
+        ac = ca.attn(qc, kc, vc)
+        # x += y ; h = modulate(norm2(x))  (reference :226-227)
+        x = self._fp8_hot_residual(f"blocks.{i}.cross_attn.o", ac, w8[4], ca.o.bias, x, mod, None)
+        h, h8 = hip.ln_modulate_dual(x, mod, 3, 4, eps, out=h)
+        # --- ffn (reference :208-209,228): the adapter adds to ffn.0's pre-activation, so GELU is the adapter kernel's store (in place: f is
+        # nn.GELU's bf16 output, which ffn.2's adapter reads and its fp8 Linear quantises); without an adapter it is the GEMM's own
+        name, f0, b0 = f"blocks.{i}.ffn.0", w8[5].shape[0], blk.ffn[0].bias
+        pk = self._hot_pack((name,)) if fp8_own_ok(f0, c) else False
+        if pk is None:
+            f = hip.gemm_fp8(*h8, w8[5], b0, act="gelu_tanh", lead_shape=(1, h8[0].shape[0]))
+        elif pk:
+            f = hip.lora_apply(h, pk[0], pk[1], lin(h8, 5, b0), mode="gelu_tanh")
+        else:
+            f = hip.activation(self._hot(name, h, lin(h8, 5, b0)), "gelu_tanh")
+        x = self._fp8_hot_residual(f"blocks.{i}.ffn.2", f, w8[6], blk.ffn[2].bias, x, mod, 5)
+        return x, (hip.ln_modulate_dual(x, next_mod, 0, 1, eps, out=h) if next_mod is not None else None)
 
     # ------------------------------------------------------------------ the 30-block token forward
     def forward_tokens(self, x, context, mod_rows_t, t_rows, first_rows, rope, shard=None, shard_total=None, tea_cache=None,
@@ -505,14 +571,17 @@ class WanModel(nn.Module):
         sharded = shard is not None and shard.active
         hot = bool(self.hot_loras)
         fp8 = self.fp8_dtype
-        # adapters on fg_lora_apply_bf16 next to the own GEMMs (docstring of hot_lora_backend's setter, WanVideoPipeline.load_lora)
-        hip_hot = hot and fp8 is None and self.hot_lora_backend == "hip"
+        # adapters on fg_lora_apply_bf16 next to the own GEMMs, bf16 or fp8 (comment on hot_lora_backend, WanVideoPipeline.load_lora)
+        hip_hot = hot and self.hot_lora_backend == "hip"
+        # fp8 Linears + adapters on the HIP backend: the residual adds move into fg_gemm_fp8_bf16's store, and every norm writes the bf16
+        # row (for the adapter) and the (e4m3 rows, scales) pair (for the GEMM) in one pass: h = (bf16 row, pair)
+        hot8 = hip_hot and fp8 is not None
         ctx8 = hip.fp8_quant_rows(context) if fp8 is not None else None      # the text context is the same for all blocks
         mods = [hip.ModTable((blk.modulation.to(mod_rows_t.dtype) + mod_rows_t).contiguous(), first_rows) for blk in blocks]
         # fp8 mode: the four norms of a block feed fp8 Linears only, so they hand over (e4m3 rows, row scales) directly;
-        # a hot-loaded adapter needs the bf16 row too: then the separate quantisation stays
+        # a hot-loaded adapter needs the bf16 row too: the dual-output norms with the "hip" backend (hot8), else the separate quantisation stays
         fold8 = fp8 is not None and not hot and FP8_FOLD
-        h = (hip.ln_modulate_fp8 if fold8 else hip.ln_modulate)(x, mods[0], 0, 1, eps) if blocks else None
+        h = (hip.ln_modulate_dual if hot8 else hip.ln_modulate_fp8 if fold8 else hip.ln_modulate)(x, mods[0], 0, 1, eps) if blocks else None
         for i, blk in enumerate(blocks):
             mod = mods[i]
             wqkv, bqkv, wkv_c, bkv_c = blk.fused_weights()
@@ -535,7 +604,7 @@ class WanModel(nn.Module):
                     yield i
                 x = cfg_prefix.pop("x_sa")
                 cfg_prefix["taken"] = True
-                h = hip.ln_affine(x, blk.norm3.weight, blk.norm3.bias, eps)
+                h = (hip.ln_affine_dual if hot8 else hip.ln_affine)(x, blk.norm3.weight, blk.norm3.bias, eps)
                 reuse = True
             else:
                 reuse = False
@@ -547,6 +616,9 @@ class WanModel(nn.Module):
                 if cfg_prefix is not None and i == 0:
                     cfg_prefix["x_sa"] = x.clone()
             # --- cross attention (reference :170-185)
+            if hot8:
+                x, h = self._block_tail_fp8_hot(i, blk, mod, mods[i + 1] if i + 1 < len(blocks) else None, x, h, context, ctx8, lin, kv_cache)
+                continue
             if fp8 is None:
                 qc = gemm_bias_own(h, ca.q.weight, ca.q.bias) if own and own_gemm_ok(h.shape[1], c, c) else gemm_bias(h, ca.q.weight, ca.q.bias)
             else:

@@ -34,7 +34,7 @@ extern "C" {
 
 typedef void* fg_stream_t;   /* hipStream_t */
 
-int         fg_version(void);            /* ABI version, currently 4 */
+int         fg_version(void);            /* ABI version, currently 5 */
 const char* fg_last_error(void);         /* thread-local, valid until the next failing call */
 
 /* ------------------------------------------------------------------ DiT token-side kernels (HBM-bound)
@@ -80,6 +80,18 @@ int fg_ln_modulate_fp8_bf16(const void* x, const void* shift, const void* scale,
 int fg_residual_ln_fp8_bf16(const void* x, const void* y, const void* gate, void* x_out, const void* p0, const void* p1,
                             void* norm_fp8, float* norm_scale, int mode, int64_t rows, int C, float eps,
                             int64_t mod_rows, int64_t first_rows, int64_t mod_ld, float fp8_max, fg_stream_t stream);
+
+/* The norms of a DiT block in the fp8 Linear mode when hot-loaded LoRA adapters are attached (AutoWrappedLinear.forward,
+ * core/vram/layers.py:429-436: fp8_linear(x) for the base product, then lora_forward on the SAME bf16 x): the normalised row has two
+ * consumers, so it leaves in both forms in one pass — out (rows, C) bf16, bit for bit fg_ln_modulate_bf16's / fg_ln_affine_bf16's result
+ * (models/wan_video_dit.py:224,227 and :226), and out_fp8 (rows, C) e4m3 + out_scale (rows) fp32, byte for byte what
+ * fg_ln_modulate_fp8_bf16 / fg_fp8_quant_rows_bf16 (act 0) make of that row.  The affine form takes no residual input: in this mode the
+ * residual add that precedes norm3 happens in fg_gemm_fp8_bf16's store (mode 2).  out_fp8 8-byte aligned; fp8_max: 448 for e4m3fn. */
+int fg_ln_modulate_dual_bf16(const void* x, const void* shift, const void* scale, void* out, void* out_fp8, float* out_scale,
+                             int64_t rows, int C, float eps, int64_t mod_rows, int64_t first_rows, int64_t mod_ld,
+                             float fp8_max, fg_stream_t stream);
+int fg_ln_affine_dual_bf16(const void* x, const void* w, const void* b, void* out, void* out_fp8, float* out_scale,
+                           int64_t rows, int C, float eps, float fp8_max, fg_stream_t stream);
 
 /* nn.Linear of the DiT blocks (models/wan_video_dit.py:130-133,156-159,208-209): c[M,N] = a[M,K] w[N,K]^T + bias[N], bf16 in and
  * out, fp32 accumulation, bias added to the accumulator before the bf16 rounding — alone or with the op that follows it in the block

@@ -2,6 +2,7 @@
 hot-loaded on each backend of WanModel.hot_lora_backend, and fused into the weights (the floor).
 
     python tools/hot_lora_step.py --steps 3 --order torch,hip,torch,fused
+    python tools/hot_lora_step.py --linear-dtype fp8 --steps 3 --order torch,hip,torch,fused      # the same legs in the fp8 Linear mode
 
 Every leg builds the 30-block model from the same seeds, warms up one step and reports the median of `--steps` timed steps (host clock
 around a device synchronise).  "torch" is the code path of hotload=True before the backend existed.  Prints one line per leg and a
@@ -22,7 +23,7 @@ from fairygen_amd.wan_video import WanVideoPipeline, model_fn_wan_video  # noqa:
 from fairygen_amd.wan_video_dit import WanModel  # noqa: E402
 
 
-def build(leg, layers, dev):
+def build(leg, layers, dev, linear_dtype="bf16"):
     cfg = dict(TI2V_5B_DIT_KWARGS)
     if layers:
         cfg["num_layers"] = layers
@@ -32,6 +33,8 @@ def build(leg, layers, dev):
     dit.load_state_dict(synthetic.random_state_dict(shapes, seed=1234, device=dev), assign=True)
     pipe = WanVideoPipeline(device=dev, torch_dtype=torch.bfloat16)
     pipe.dit = dit.to(device=dev, dtype=torch.bfloat16).eval()
+    if linear_dtype == "fp8":
+        pipe.dit.enable_fp8_linear()
     lora = synthetic.random_lora(shapes, rank=32, seed=4321)
     if leg == "fused":
         pipe.load_lora(pipe.dit, state_dict=lora, alpha=1)
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--frames", type=int, default=121)
     ap.add_argument("--order", default="torch,hip,torch,fused")
+    ap.add_argument("--linear-dtype", choices=("bf16", "fp8"), default="bf16", help="fp8: every leg calls enable_fp8_linear() before the adapters are loaded")
     a = ap.parse_args()
     hip.load()
     dev = "cuda"
@@ -58,7 +62,7 @@ def main():
     ts = torch.tensor([900.0]).to(torch.bfloat16)
     results, outs = [], {}
     for leg in a.order.split(","):
-        pipe = build(leg, a.layers, dev)
+        pipe = build(leg, a.layers, dev, a.linear_dtype)
 
         def step():
             with torch.no_grad():
@@ -83,7 +87,7 @@ def main():
         del pipe, out
         gc.collect()
         torch.cuda.empty_cache()
-    print(json.dumps({"tool": "hot_lora_step", "height": a.height, "width": a.width, "frames": a.frames, "layers": a.layers or 30, "steps": a.steps,
+    print(json.dumps({"tool": "hot_lora_step", "height": a.height, "width": a.width, "frames": a.frames, "layers": a.layers or 30, "steps": a.steps, "linear_dtype": a.linear_dtype,
                       "legs": results}))
 
 
