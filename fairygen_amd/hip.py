@@ -13,7 +13,7 @@ import torch
 _LIB_PATH = os.environ.get("FAIRYGEN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfairygen_hip.so")
 _lib = None
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _i64, _i32, _f32, _vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
@@ -34,6 +34,9 @@ _SIGNATURES = {
     "fg_act_bf16": [_vp, _vp, _i64, _i32, _vp],
     "fg_gemm_epilogue_bf16": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp],
     "fg_gemm_fp8_bf16": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp],
+    "fg_gemm_sched_reset": [_vp, _vp],
+    "fg_gemm_epilogue_bf16_s": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp],
+    "fg_gemm_fp8_bf16_s": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp],
     "fg_lora_apply_bf16": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp],
     "fg_attn_fwd_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _f32, _vp, _i64, _vp],
     "fg_cfg_euler_bf16": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _vp],
@@ -54,7 +57,7 @@ _SIGNATURES = {
     "fg_gated_gelu_bf16": [_vp, _vp, _vp, _i64, _vp],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["fg_version", "fg_last_error", "fg_conv_packed_bytes", "fg_attn_workspace_bytes", "fg_attn_split_choice",
-                                                   "fg_conv_tile_choice", "fg_gemm_workspace_bytes", "fg_gemm_debug_grid"])
+                                                   "fg_conv_tile_choice", "fg_gemm_workspace_bytes", "fg_gemm_debug_grid", "fg_gemm_sched_bytes"])
 
 
 class HipLibraryError(RuntimeError):
@@ -85,6 +88,8 @@ def load():
     lib.fg_conv_tile_choice.argtypes = [_i32] * 4
     lib.fg_gemm_workspace_bytes.restype = ctypes.c_int64
     lib.fg_gemm_workspace_bytes.argtypes = [_i64] * 3
+    lib.fg_gemm_sched_bytes.restype = ctypes.c_int64
+    lib.fg_gemm_sched_bytes.argtypes = []
     lib.fg_gemm_debug_grid.restype = ctypes.c_int
     lib.fg_gemm_debug_grid.argtypes = [_i32]
     lib.fg_attn_split_choice.restype = ctypes.c_int
@@ -342,16 +347,82 @@ def copy_groups(src, src_group_stride, src_ld, dst, dst_group_stride, dst_ld, gr
 
 
 _gemm_workspace = {}      # (device, stream) -> scratch for the k-split pieces of a GEMM's last round (one fp32 tile per CU, reused)
+_gemm_sched = {}          # (device, stream) -> the scheduler block of the launches on that stream (fg_gemm_sched_bytes, reset when created)
+_gemm_sched_dirty = set()      # keys whose last launch raised: the block is reset before its next use
+
+
+def _gemm_key(x):
+    return (x.device, torch.cuda.current_stream(x.device).cuda_stream)      # concurrent streams must share neither block nor scratch
+
+
+def gemm_sched_reset(sched):
+    """Put a scheduler block into its initial state, stream-ordered on the current stream of its device (fg_gemm_sched_reset: one
+    asynchronous memset, capturable).  Needed once before a block's first launch, and after a launch that did not run to its end."""
+    _gemm_sched_check("gemm_sched_reset", sched, sched.device if isinstance(sched, torch.Tensor) else None)
+    _call("fg_gemm_sched_reset", _ptr(sched), _stream(sched))
+    return sched
+
+
+def gemm_state(device=None):
+    """(sched, workspace) for GEMM launches that are ordered with respect to each other and owned by the caller — a stream of its own,
+    a captured graph: a fresh scheduler block, reset on the current stream of `device`, and k-split scratch of the matching size.
+    Pass them as gemm_epilogue(..., sched=sched, workspace=workspace).  Concurrent streams need a pair each."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise HipLibraryError(f"gemm_state: expected a HIP device, got {device} (no CPU fallback)")
+    lib = load()
+    sched = torch.empty(lib.fg_gemm_sched_bytes(), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):      # the scratch size is one fp32 tile per CU of THAT device
+        workspace = torch.empty(lib.fg_gemm_workspace_bytes(256, 256, 256), dtype=torch.uint8, device=device)
+    return gemm_sched_reset(sched), workspace
+
+
+def _gemm_sched_check(name, sched, device):
+    if not isinstance(sched, torch.Tensor) or sched.device.type != "cuda" or (device is not None and sched.device != device):
+        raise HipLibraryError(f"{name}: sched must be a tensor on the HIP device of the operands (no CPU fallback)")
+    if not sched.is_contiguous() or sched.numel() * sched.element_size() < load().fg_gemm_sched_bytes():
+        raise HipLibraryError(f"{name}: sched must be a contiguous block of at least {load().fg_gemm_sched_bytes()} bytes (hip.gemm_state)")
+
+
+def _gemm_block(name, x, sched):
+    """(block, key): the caller's block (key None), or the one kept for the current (device, stream)."""
+    if sched is not None:
+        _gemm_sched_check(name, sched, x.device)
+        return sched, None
+    key = _gemm_key(x)
+    block = _gemm_sched.get(key)
+    if block is None:
+        block = _gemm_sched[key] = torch.empty(load().fg_gemm_sched_bytes(), dtype=torch.uint8, device=x.device)
+        _gemm_sched_dirty.add(key)
+    if key in _gemm_sched_dirty:
+        _call("fg_gemm_sched_reset", _ptr(block), _stream(x))
+        _gemm_sched_dirty.discard(key)
+    return block, key
+
+
+def _gemm_launch(name, key, *args):
+    try:
+        _call(name, *args)
+    except HipLibraryError:
+        if key is not None:
+            _gemm_sched_dirty.add(key)
+        raise
 
 
 def _gemm_ws(x, m, n, k_bytes, workspace):
     """The k-split scratch, only where fg_gemm_* would use it: at least 96 k-steps of 128 operand bytes, or at most 8 rounds of tiles per CU
-    (launch_gemm in csrc/dit_gemm.hip; 256 CUs assumed here — a spare allocation on other devices, never a missing one)."""
+    (GemmCall::enqueue in csrc/dit_gemm.hip; 256 CUs assumed here — a spare allocation on other devices, never a missing one).  `workspace`:
+    True (the scratch kept per (device, stream)), False / None (none), or the caller's own scratch tensor (hip.gemm_state)."""
+    if isinstance(workspace, torch.Tensor):
+        if workspace.device != x.device or not workspace.is_contiguous() or \
+                workspace.numel() * workspace.element_size() < load().fg_gemm_workspace_bytes(m, n, k_bytes):
+            raise HipLibraryError("gemm: the workspace tensor must be contiguous, on the operands' device, of fg_gemm_workspace_bytes (hip.gemm_state)")
+        return workspace
     tiles = ((m + 255) // 256) * (n // 256)
     need = load().fg_gemm_workspace_bytes(m, n, k_bytes) if workspace and (k_bytes // 128 >= 96 or tiles <= 8 * 256) else 0
     if need <= 0:
         return None
-    key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)      # concurrent streams must not share scratch
+    key = _gemm_key(x)
     ws = _gemm_workspace.get(key)
     if ws is None or ws.numel() < need:
         ws = _gemm_workspace[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
@@ -380,12 +451,14 @@ def _gemm_mode(name, residual, mod, gate_idx, act, n):
     return (3 if residual else 4 if act else 0), None, 1, n, 0
 
 
-def gemm_epilogue(x, weight, bias, out=None, residual=False, mod=None, gate_idx=None, workspace=True, act=None):
+def gemm_epilogue(x, weight, bias, out=None, residual=False, mod=None, gate_idx=None, workspace=True, act=None, sched=None, workgroups=0):
     """Linear on the persistent MFMA kernel.  residual=False: out = act(x @ weight^T + bias), act None or "gelu_tanh" (applied to the
     bf16-rounded Linear output and rounded again, like nn.Linear followed by nn.GELU).  residual=True: `out` holds the residual
     stream and becomes out + gate * (x @ weight^T + bias) (gate = vector gate_idx of `mod`, or 1 when mod is None), with the
     reference's rounding points (GateModule, models/wan_video_dit.py:188-193).  workspace=False: no k-split of the last round's tiles
-    (every element one k-ordered accumulation, independent of the row count)."""
+    (every element one k-ordered accumulation, independent of the row count); a tensor: the caller's scratch.  sched: a caller-managed
+    scheduler block (hip.gemm_state; default: the block kept for the current (device, stream)); workgroups: how many workgroups to launch
+    (0: one per CU) — same bits for every value.  The launch is fg_gemm_epilogue_bf16_s: nothing but stream-ordered work, capturable."""
     _dev(x, "x"), _dev(weight, "weight"), _dev(bias, "bias")
     k = x.shape[-1]
     n = weight.shape[0]
@@ -398,16 +471,18 @@ def gemm_epilogue(x, weight, bias, out=None, residual=False, mod=None, gate_idx=
     out = _gemm_out("gemm_epilogue", x, m, n, out, residual)
     mode, gate, gate_rows, gate_ld, first = _gemm_mode("gemm_epilogue", residual, mod, gate_idx, act, n)
     ws = _gemm_ws(x, m, n, 2 * k, workspace)
-    _call("fg_gemm_epilogue_bf16", _ptr(x2), lda, _ptr(weight), _ptr(bias), _ptr(out), n, m, n, k, mode, gate, gate_rows, gate_ld, first,
-          _ptr(ws), _stream(x))
+    block, key = _gemm_block("gemm_epilogue", x, sched)
+    _gemm_launch("fg_gemm_epilogue_bf16_s", key, _ptr(x2), lda, _ptr(weight), _ptr(bias), _ptr(out), n, m, n, k, mode, gate, gate_rows, gate_ld, first,
+                 _ptr(ws), _ptr(block), workgroups, _stream(x))
     return out
 
 
-def gemm_fp8(x_fp8, scale_a, weight_fp8, bias, out=None, residual=False, mod=None, gate_idx=None, workspace=True, act=None, lead_shape=None):
+def gemm_fp8(x_fp8, scale_a, weight_fp8, bias, out=None, residual=False, mod=None, gate_idx=None, workspace=True, act=None, lead_shape=None,
+             sched=None, workgroups=0):
     """torch._scaled_mm(x_fp8, weight_fp8.T, scale_a (rows, 1), ones (1, out), bias, out_dtype=bf16) of AutoWrappedLinear.fp8_linear
     (core/vram/layers.py:343-357) on the persistent kernel's e4m3 form, with the epilogues of gemm_epilogue.  x_fp8: (rows, K)
     float8_e4m3fn, scale_a: (rows, 1) fp32 (both from fp8_quant_rows / the fp8-output norm kernels), weight_fp8: (N, K) float8_e4m3fn.
-    Returns (*lead_shape, N) bf16 (default lead_shape: (rows,))."""
+    Returns (*lead_shape, N) bf16 (default lead_shape: (rows,)).  workspace / sched / workgroups as gemm_epilogue (fg_gemm_fp8_bf16_s)."""
     _dev(x_fp8, "x_fp8", torch.float8_e4m3fn), _dev(weight_fp8, "weight_fp8", torch.float8_e4m3fn), _dev(bias, "bias")
     _dev(scale_a, "scale_a", torch.float32)
     if x_fp8.dim() != 2 or x_fp8.stride(1) != 1 or not weight_fp8.is_contiguous() or weight_fp8.dim() != 2:
@@ -421,8 +496,9 @@ def gemm_fp8(x_fp8, scale_a, weight_fp8, bias, out=None, residual=False, mod=Non
     out = _gemm_out("gemm_fp8", x_fp8, m, n, out, residual)
     mode, gate, gate_rows, gate_ld, first = _gemm_mode("gemm_fp8", residual, mod, gate_idx, act, n)
     ws = _gemm_ws(x_fp8, m, n, k, workspace)
-    _call("fg_gemm_fp8_bf16", _ptr(x_fp8), x_fp8.stride(0), _ptr(scale_a), _ptr(weight_fp8), _ptr(bias), _ptr(out), n, m, n, k, mode, gate,
-          gate_rows, gate_ld, first, _ptr(ws), _stream(x_fp8))
+    block, key = _gemm_block("gemm_fp8", x_fp8, sched)
+    _gemm_launch("fg_gemm_fp8_bf16_s", key, _ptr(x_fp8), x_fp8.stride(0), _ptr(scale_a), _ptr(weight_fp8), _ptr(bias), _ptr(out), n, m, n, k, mode, gate,
+                 gate_rows, gate_ld, first, _ptr(ws), _ptr(block), workgroups, _stream(x_fp8))
     return out
 
 

@@ -12,6 +12,10 @@
  *   - no allocation, no ownership transfer, no host synchronisation: the caller passes every buffer,
  *     work is enqueued asynchronously on `stream` (a hipStream_t; NULL = the default stream);
  *   - re-entrant across streams and devices, no mutable global state;
+ *   - the documented exception to the two points above: fg_gemm_epilogue_bf16 and fg_gemm_fp8_bf16 keep the scheduler block of their
+ *     kernel inside the library, per (device, stream) — allocation and a device-wide synchronisation on the first call on a stream, a
+ *     lock on every call, not capturable into a graph before that first call.  fg_gemm_epilogue_bf16_s / fg_gemm_fp8_bf16_s are the
+ *     same launches on a block the caller owns and keep the contract;
  *   - all tensors are contiguous row-major device buffers unless a leading dimension (`ld*`, in
  *     ELEMENTS) is given; bf16 = IEEE bfloat16 bits; pointers must be 16-byte aligned and the channel
  *     counts multiples of 8 (checked, FG_EINVAL);
@@ -34,7 +38,7 @@ extern "C" {
 
 typedef void* fg_stream_t;   /* hipStream_t */
 
-int         fg_version(void);            /* ABI version, currently 5 */
+int         fg_version(void);            /* ABI version, currently 6 */
 const char* fg_last_error(void);         /* thread-local, valid until the next failing call */
 
 /* ------------------------------------------------------------------ DiT token-side kernels (HBM-bound)
@@ -113,6 +117,25 @@ int fg_gemm_epilogue_bf16(const void* a, int64_t lda, const void* w, const void*
                           int64_t M, int64_t N, int64_t K, int mode, const void* gate, int64_t gate_rows, int64_t gate_ld,
                           int64_t first_rows, void* workspace, fg_stream_t stream);
 
+/* Caller-owned scheduler state of the persistent GEMM.  The kernel's per-XCD unit cursors and its done counter live in a block of
+ * fg_gemm_sched_bytes() bytes of device memory (16-byte aligned; the size is a constant, no device needed to ask).  A block must be in
+ * its initial state before its first launch: fg_gemm_sched_reset enqueues that on `stream` (one asynchronous memset: no host
+ * synchronisation, capturable).  Every launch leaves the block in the initial state again (its last workgroup clears it), so launches
+ * need no reset between them; after a launch that did not run to its end (killed, faulted) the block is undefined and
+ * fg_gemm_sched_reset repairs it.  ONE block serves launches that are ordered with respect to each other — one stream, or one captured
+ * graph; launches that may run concurrently (two streams) need a block each, and likewise a `workspace` each.
+ * fg_gemm_epilogue_bf16_s / fg_gemm_fp8_bf16_s: fg_gemm_epilogue_bf16 / fg_gemm_fp8_bf16 with that block as an argument — the same
+ * kernels, plan and bits — and no other state: no allocation, no lock, no table, no host synchronisation, from the first call on a
+ * stream on, so a stream capture can record them (with the reset, if wanted, as the first node).  workgroups: 0 = one per CU (or what
+ * the fg_gemm_debug_grid diagnostic has set for the process); else the number of workgroups to launch, a multiple of the XCD count up
+ * to the CU count — the units are fixed by the shape, the result is bit-identical for every value.  sched NULL or misaligned, or any
+ * other workgroups value: FG_EINVAL. */
+int64_t fg_gemm_sched_bytes(void);
+int fg_gemm_sched_reset(void* sched, fg_stream_t stream);
+int fg_gemm_epilogue_bf16_s(const void* a, int64_t lda, const void* w, const void* bias, void* c, int64_t ldc,
+                            int64_t M, int64_t N, int64_t K, int mode, const void* gate, int64_t gate_rows, int64_t gate_ld,
+                            int64_t first_rows, void* workspace, void* sched, int workgroups, fg_stream_t stream);
+
 /* Hot-loaded (unfused) LoRA adapters of one Linear, AutoWrappedLinear.lora_forward (core/vram/layers.py:417-436: `out = out + x @ A^T @ B^T`
  * per adapter, in the pipeline dtype), for the adapters stacked along the rank and for G column groups that share the input x
  * (G = 3: q | k | v on the fused qkv buffer; else 1), in ONE launch next to fg_gemm_epilogue_bf16:
@@ -130,8 +153,10 @@ int fg_lora_apply_bf16(const void* x, int64_t ldx, const void* a, const void* b,
 
 /* Diagnostics for the persistent GEMM's unit scheduler: launch only `workgroups` workgroups (a multiple of the XCD count, at most one
  * per CU; 0 = one per CU again).  The units of a launch are fixed by the shape; workgroups take them from per-XCD cursors, so the result
- * is bit-identical with any number of workgroups — as when other kernels (RCCL) hold some CUs.  The library keeps 256 bytes of device
- * memory per (device, stream) it has launched a GEMM on (the cursors; cleared by the last workgroup of every launch). */
+ * is bit-identical with any number of workgroups — as when other kernels (RCCL) hold some CUs.  Process-wide (an atomic word): it is
+ * what a launch with workgroups == 0, and every launch of the two entry points without that argument, uses; the per-call `workgroups`
+ * of the _s forms is the re-entrant way.  For those two entry points the library keeps 256 bytes of device memory per (device, stream)
+ * it has launched a GEMM on (the cursors; cleared by the last workgroup of every launch). */
 int fg_gemm_debug_grid(int workgroups);
 
 /* The matmul of AutoWrappedLinear.fp8_linear (core/vram/layers.py:343-357: torch._scaled_mm(x_fp8, w_fp8.T, scale_a (rows, 1),
@@ -143,6 +168,10 @@ int fg_gemm_debug_grid(int workgroups);
 int fg_gemm_fp8_bf16(const void* a_fp8, int64_t lda, const float* scale_a, const void* w_fp8, const void* bias, void* c, int64_t ldc,
                      int64_t M, int64_t N, int64_t K, int mode, const void* gate, int64_t gate_rows, int64_t gate_ld,
                      int64_t first_rows, void* workspace, fg_stream_t stream);
+/* ... on a caller-owned scheduler block: see fg_gemm_sched_bytes. */
+int fg_gemm_fp8_bf16_s(const void* a_fp8, int64_t lda, const float* scale_a, const void* w_fp8, const void* bias, void* c, int64_t ldc,
+                       int64_t M, int64_t N, int64_t K, int mode, const void* gate, int64_t gate_rows, int64_t gate_ld,
+                       int64_t first_rows, void* workspace, void* sched, int workgroups, fg_stream_t stream);
 
 /* RMSNorm over the full row (all heads), * weight, then optional 3-D RoPE on adjacent pairs:
  * RMSNorm.forward models/wan_video_dit.py:99-110 + rope_apply :91-96 (SelfAttention.forward :140-144,
