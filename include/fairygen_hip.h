@@ -18,7 +18,13 @@
  *     same launches on a block the caller owns and keep the contract;
  *   - all tensors are contiguous row-major device buffers unless a leading dimension (`ld*`, in
  *     ELEMENTS) is given; bf16 = IEEE bfloat16 bits; pointers must be 16-byte aligned and the channel
- *     counts multiples of 8 (checked, FG_EINVAL);
+ *     counts multiples of 8 (checked, FG_EINVAL).  Where a function names a weaker alignment, that one is what it checks: 8 bytes for
+ *     the fp8 outputs, bias / gate of the GEMMs and bias / residual / out of fg_conv3d_cl_bf16; 4 bytes for scale_a.  The fp32 scale
+ *     outputs (out_scale, norm_scale, scale) are written one float at a time and no alignment is checked for them.  The kernels that
+ *     access single elements take any element-aligned pointer and check NO alignment (a misaligned pointer is not rejected):
+ *     fg_cfg_euler_bf16, fg_softmax_rows_f32_bf16, fg_softmax_bias_bf16, fg_conv_pack_weight_bf16, fg_vae_latent_to_cl_bf16,
+ *     fg_vae_latent_from_cl_bf16, fg_vae_unpatchify_bf16, fg_vae_patchify_bf16, fg_avgdown3d_add_bf16, fg_video_to_uint8,
+ *     fg_vae_tile_accumulate_bf16, fg_vae_tile_finalize_bf16 (tests/test_buffer_contract.py);
  *   - token tensors are "b s (n d)" exactly like the reference's AttentionModule
  *     (models/wan_video_dit.py:113-120); VAE activations are channels-last (T,H,W,C) inside the
  *     decoder, NCTHW only at fg_vae_* boundary kernels.
