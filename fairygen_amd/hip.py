@@ -136,6 +136,17 @@ def _rows(t, name):
     return t.numel() // t.shape[-1], t.shape[-1]
 
 
+def _rows2d(t, who, cols="C"):
+    """(..., C) with a dense last dim as the 2-D (rows, C) view the fg_* kernels take with a row stride: a contiguous tensor of any rank,
+    a strided 2-D one (a column slice of a wider buffer) or a strided (1, rows, C).  `who` prefixes the error."""
+    if t.stride(-1) != 1:
+        raise HipLibraryError(f"{who}: last dim must be dense")
+    t2 = t.reshape(-1, t.shape[-1]) if t.is_contiguous() else (t.squeeze(0) if t.dim() == 3 else t)
+    if t2.dim() != 2:
+        raise HipLibraryError(f"{who}: strided input must be 2-D (rows, {cols}) or (1, rows, {cols})")
+    return t2
+
+
 class ModTable:
     """AdaLN modulation rows: tensor (mod_rows, K, C) bf16; vector j of row r = table[r, j].
 
@@ -187,38 +198,50 @@ def gate_residual(x, y, mod=None, gate_idx=None, out=None):
     return out
 
 
+def _ln_modulate_args(who, x, mod, gate_idx, shift_idx, scale_idx, norm_mod):
+    """(gate, shift, scale, affine flag, table args) of a residual + modulate(LN) launch."""
+    norm_mod = mod if norm_mod is None else norm_mod
+    if (norm_mod.mod_rows, norm_mod.first_rows, norm_mod.ld) != (mod.mod_rows, mod.first_rows, mod.ld):
+        raise HipLibraryError(f"{who}: gate and norm tables must share rows / first_rows / ld")
+    gate = mod.vec(gate_idx) if gate_idx is not None else None
+    return gate, norm_mod.vec(shift_idx), norm_mod.vec(scale_idx), 0, _mod_args(mod, _rows(x, "x")[0])
+
+
+def _ln_affine_args(x, w, b, mod, gate_idx):
+    """(gate, weight, bias, affine flag, table args) of a residual + affine LN launch."""
+    _dev(w, "w"), _dev(b, "b")
+    if mod is None:
+        return None, _ptr(w), _ptr(b), 1, (1, 0, 0)
+    return mod.vec(gate_idx), _ptr(w), _ptr(b), 1, _mod_args(mod, _rows(x, "x")[0])
+
+
+def _residual_ln(x, y, eps, x_out, norm_out, gate, p1, p2, affine, margs, fp8=False):
+    """x_out = x + gate*y, then LN(x_out) with the operands p1, p2 (shift / scale vectors, or weight / bias with affine = 1): as a bf16
+    row in norm_out (fg_residual_ln_bf16) or, fp8, as (e4m3 rows, scales) (fg_residual_ln_fp8_bf16)."""
+    rows, c = _rows(x, "x")
+    _rows(y, "y")
+    x_out = torch.empty_like(x) if x_out is None else x_out
+    if fp8:
+        q, sc = _fp8_rows_out(x)
+        _call("fg_residual_ln_fp8_bf16", _ptr(x), _ptr(y), gate, _ptr(x_out), p1, p2, _ptr(q), _ptr(sc), affine, rows, c, eps, *margs,
+              FP8_E4M3FN_MAX, _stream(x))
+        return x_out, (q, sc)
+    norm_out = torch.empty_like(x) if norm_out is None else norm_out
+    _call("fg_residual_ln_bf16", _ptr(x), _ptr(y), gate, _ptr(x_out), p1, p2, _ptr(norm_out), affine, rows, c, eps, *margs, _stream(x))
+    return x_out, norm_out
+
+
 def residual_ln_modulate(x, y, mod, gate_idx, shift_idx, scale_idx, eps, x_out=None, norm_out=None, norm_mod=None):
     """x_out = x + gate*y (gate_idx None: x + y); norm_out = modulate(LN(x_out)).
 
     gate comes from `mod`, shift/scale from `norm_mod` (default: `mod`); both tables must have the same
     number of rows, first_rows and leading dimension."""
-    rows, c = _rows(x, "x")
-    _rows(y, "y")
-    norm_mod = mod if norm_mod is None else norm_mod
-    if (norm_mod.mod_rows, norm_mod.first_rows, norm_mod.ld) != (mod.mod_rows, mod.first_rows, mod.ld):
-        raise HipLibraryError("residual_ln_modulate: gate and norm tables must share rows / first_rows / ld")
-    x_out = torch.empty_like(x) if x_out is None else x_out
-    norm_out = torch.empty_like(x) if norm_out is None else norm_out
-    gate = mod.vec(gate_idx) if gate_idx is not None else None
-    _call("fg_residual_ln_bf16", _ptr(x), _ptr(y), gate, _ptr(x_out), norm_mod.vec(shift_idx),
-          norm_mod.vec(scale_idx), _ptr(norm_out), 0, rows, c, eps, *_mod_args(mod, rows), _stream(x))
-    return x_out, norm_out
+    return _residual_ln(x, y, eps, x_out, norm_out, *_ln_modulate_args("residual_ln_modulate", x, mod, gate_idx, shift_idx, scale_idx, norm_mod))
 
 
 def residual_ln_affine(x, y, w, b, eps, mod=None, gate_idx=None, x_out=None, norm_out=None):
     """x_out = x + gate*y (mod None: x + y); norm_out = LN(x_out)*w + b."""
-    rows, c = _rows(x, "x")
-    _rows(y, "y")
-    _dev(w, "w"), _dev(b, "b")
-    x_out = torch.empty_like(x) if x_out is None else x_out
-    norm_out = torch.empty_like(x) if norm_out is None else norm_out
-    if mod is None:
-        gate, margs = None, (1, 0, 0)
-    else:
-        gate, margs = mod.vec(gate_idx), _mod_args(mod, rows)
-    _call("fg_residual_ln_bf16", _ptr(x), _ptr(y), gate, _ptr(x_out), _ptr(w), _ptr(b), _ptr(norm_out), 1, rows, c,
-          eps, *margs, _stream(x))
-    return x_out, norm_out
+    return _residual_ln(x, y, eps, x_out, norm_out, *_ln_affine_args(x, w, b, mod, gate_idx))
 
 
 def _fp8_rows_out(x):
@@ -260,33 +283,12 @@ def ln_affine_dual(x, w, b, eps, out=None):
 
 def residual_ln_modulate_fp8(x, y, mod, gate_idx, shift_idx, scale_idx, eps, x_out=None, norm_mod=None):
     """residual_ln_modulate with the normalised row as (fp8 rows, scales): returns x_out, (x_fp8, scale)."""
-    rows, c = _rows(x, "x")
-    _rows(y, "y")
-    norm_mod = mod if norm_mod is None else norm_mod
-    if (norm_mod.mod_rows, norm_mod.first_rows, norm_mod.ld) != (mod.mod_rows, mod.first_rows, mod.ld):
-        raise HipLibraryError("residual_ln_modulate_fp8: gate and norm tables must share rows / first_rows / ld")
-    x_out = torch.empty_like(x) if x_out is None else x_out
-    q, sc = _fp8_rows_out(x)
-    gate = mod.vec(gate_idx) if gate_idx is not None else None
-    _call("fg_residual_ln_fp8_bf16", _ptr(x), _ptr(y), gate, _ptr(x_out), norm_mod.vec(shift_idx), norm_mod.vec(scale_idx),
-          _ptr(q), _ptr(sc), 0, rows, c, eps, *_mod_args(mod, rows), FP8_E4M3FN_MAX, _stream(x))
-    return x_out, (q, sc)
+    return _residual_ln(x, y, eps, x_out, None, *_ln_modulate_args("residual_ln_modulate_fp8", x, mod, gate_idx, shift_idx, scale_idx, norm_mod), fp8=True)
 
 
 def residual_ln_affine_fp8(x, y, w, b, eps, mod=None, gate_idx=None, x_out=None):
     """residual_ln_affine with the normalised row as (fp8 rows, scales): returns x_out, (x_fp8, scale)."""
-    rows, c = _rows(x, "x")
-    _rows(y, "y")
-    _dev(w, "w"), _dev(b, "b")
-    x_out = torch.empty_like(x) if x_out is None else x_out
-    q, sc = _fp8_rows_out(x)
-    if mod is None:
-        gate, margs = None, (1, 0, 0)
-    else:
-        gate, margs = mod.vec(gate_idx), _mod_args(mod, rows)
-    _call("fg_residual_ln_fp8_bf16", _ptr(x), _ptr(y), gate, _ptr(x_out), _ptr(w), _ptr(b), _ptr(q), _ptr(sc), 1, rows, c,
-          eps, *margs, FP8_E4M3FN_MAX, _stream(x))
-    return x_out, (q, sc)
+    return _residual_ln(x, y, eps, x_out, None, *_ln_affine_args(x, w, b, mod, gate_idx), fp8=True)
 
 
 def rmsnorm_rope(x, weight, num_heads, eps, cos=None, sin=None, out=None, grouped=None):
@@ -299,13 +301,7 @@ def rmsnorm_rope(x, weight, num_heads, eps, cos=None, sin=None, out=None, groupe
     dst[g*group_stride + r*ld : ... + group_cols] instead of a (rows, C) tensor (Ulysses send buffer); returns dst."""
     _dev(x, "x"), _dev(weight, "weight")
     c = x.shape[-1]
-    if x.stride(-1) != 1:
-        raise HipLibraryError("rmsnorm_rope: last dim must be dense")
-    x2 = x.reshape(-1, c) if x.is_contiguous() else x
-    if x2.dim() != 2:
-        x2 = x2.squeeze(0)
-    if x2.dim() != 2:
-        raise HipLibraryError("rmsnorm_rope: strided input must be 2-D (rows, C) or (1, rows, C)")
+    x2 = _rows2d(x, "rmsnorm_rope")
     rows, ld = x2.shape[0], x2.stride(0)
     if grouped is None:
         out = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
@@ -462,11 +458,9 @@ def gemm_epilogue(x, weight, bias, out=None, residual=False, mod=None, gate_idx=
     _dev(x, "x"), _dev(weight, "weight"), _dev(bias, "bias")
     k = x.shape[-1]
     n = weight.shape[0]
-    if weight.shape != (n, k) or not weight.is_contiguous() or bias.shape != (n,) or x.stride(-1) != 1:
-        raise HipLibraryError("gemm_epilogue: weight must be a contiguous (N, K) tensor, bias (N,), x dense in its last dim")
-    x2 = x.reshape(-1, k) if x.is_contiguous() else (x.squeeze(0) if x.dim() == 3 else x)
-    if x2.dim() != 2:
-        raise HipLibraryError("gemm_epilogue: strided input must be 2-D (rows, K) or (1, rows, K)")
+    if weight.shape != (n, k) or not weight.is_contiguous() or bias.shape != (n,):
+        raise HipLibraryError("gemm_epilogue: weight must be a contiguous (N, K) tensor, bias (N,)")
+    x2 = _rows2d(x, "gemm_epilogue", "K")
     m, lda = x2.shape[0], x2.stride(0)
     out = _gemm_out("gemm_epilogue", x, m, n, out, residual)
     mode, gate, gate_rows, gate_ld, first = _gemm_mode("gemm_epilogue", residual, mod, gate_idx, act, n)
@@ -517,12 +511,11 @@ def lora_apply(x, a, b, out, groups=1, mode="add", mod=None, gate_idx=None):
     if mode not in _LORA_MODES:
         raise HipLibraryError(f"lora_apply: mode must be one of {sorted(_LORA_MODES)}")
     k, n = x.shape[-1], out.shape[-1]
-    if x.stride(-1) != 1 or out.stride(-1) != 1 or not a.is_contiguous() or not b.is_contiguous() or a.dim() != 2 or b.dim() != 2:
-        raise HipLibraryError("lora_apply: x and out must be dense in their last dim, a and b contiguous matrices")
-    x2 = x.reshape(-1, k) if x.is_contiguous() else (x.squeeze(0) if x.dim() == 3 else x)
-    o2 = out.view(-1, n) if out.is_contiguous() else (out.squeeze(0) if out.dim() == 3 else out)
-    if x2.dim() != 2 or o2.dim() != 2 or x2.shape[0] != o2.shape[0]:
-        raise HipLibraryError("lora_apply: strided tensors must be 2-D (rows, C) or (1, rows, C), with the same rows in x and out")
+    if not a.is_contiguous() or not b.is_contiguous() or a.dim() != 2 or b.dim() != 2:
+        raise HipLibraryError("lora_apply: a and b must be contiguous matrices")
+    x2, o2 = _rows2d(x, "lora_apply x"), _rows2d(out, "lora_apply out")
+    if x2.shape[0] != o2.shape[0]:
+        raise HipLibraryError("lora_apply: x and out must have the same rows")
     r = b.shape[1]
     if groups < 1 or n % groups or a.shape != (groups * r, k) or b.shape[0] != n:
         raise HipLibraryError(f"lora_apply: a {tuple(a.shape)} / b {tuple(b.shape)} do not fit x (.., {k}) -> out (.., {n}) in {groups} group(s)")
@@ -545,11 +538,7 @@ def fp8_quant_rows(x, act=None):
     scale_a (rows, 1) fp32).  act="gelu_tanh" applies the activation (rounded to bf16) before quantising."""
     _dev(x, "x")
     c = x.shape[-1]
-    if x.stride(-1) != 1:
-        raise HipLibraryError("fp8_quant_rows: last dim must be dense")
-    x2 = x.reshape(-1, c) if x.is_contiguous() else (x.squeeze(0) if x.dim() == 3 else x)
-    if x2.dim() != 2:
-        raise HipLibraryError("fp8_quant_rows: strided input must be 2-D (rows, C) or (1, rows, C)")
+    x2 = _rows2d(x, "fp8_quant_rows")
     rows, ld = x2.shape[0], x2.stride(0)
     out = torch.empty((rows, c), dtype=torch.float8_e4m3fn, device=x.device)
     scale = torch.empty((rows, 1), dtype=torch.float32, device=x.device)

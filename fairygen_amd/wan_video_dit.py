@@ -4,12 +4,15 @@ Mirror of ``diffsynth/models/wan_video_dit.py`` (``WanModel`` :271-336, ``DiTBlo
 ``SelfAttention`` :123-146, ``CrossAttention`` :149-185, ``Head`` :252-268): same constructor kwargs,
 same parameter names and shapes, so reference checkpoints, LoRA files and the key-hash model
 identification (``core/loader/file.py:117-121``) keep working.  The modules hold parameters only; the
-arithmetic is in ``forward_tokens`` below, built from ``fairygen_amd.hip`` kernels plus hipBLASLt GEMMs
-(``F.linear``).  Nothing here runs on CPU tensors — the HIP library raises.
+arithmetic is in ``forward_tokens_steps`` below, built from ``fairygen_amd.hip`` kernels: one block body whose
+Linears go through ``_BlockLinears`` — this repo's persistent MFMA GEMM (bf16 or e4m3, with the residual / gate /
+GELU stores) by default, hipBLASLt (``F.linear``, ``torch._scaled_mm``) where ``FAIRYGEN_GEMM`` / ``FAIRYGEN_FP8_GEMM`` or
+the shape say so — and whose norms hand over an ``Act``.  The embedding and head Linears are ``F.linear``.  Nothing here
+runs on CPU tensors — the HIP library raises.
 """
 import math
-
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -115,6 +118,146 @@ def stack_hot_loras(per_group, shapes, device, dtype):
             b_st[g][:, at:at + a.shape[0]] = b.to(device=device, dtype=dtype)
             at += a.shape[0]
     return a_st.view(-1, shapes[0][0]), torch.cat(b_st, 0).contiguous()
+
+
+class Act(NamedTuple):
+    """What a norm hands to the Linears behind it: the bf16 row, its (e4m3 rows, row scales) pair, or both — _BlockLinears decides which
+    once per forward.  An fp8 Linear that gets the bf16 row only quantises it itself (fg_fp8_quant_rows_bf16)."""
+    bf16: Optional[torch.Tensor] = None
+    q8: Optional[tuple] = None
+
+    @property
+    def rows(self):
+        return self.bf16.shape[-2] if self.bf16 is not None else self.q8[0].shape[0]
+
+
+class _BlockLinears:
+    """How the Linears and norms of the blocks run in ONE forward: the mode decisions (bf16 / fp8 Linears, hot-loaded adapters and their
+    backend, which GEMMs are this repo's own) taken once, the norm kernels that fill the Act fields those Linears read, and the two forms a
+    block Linear has — `plain` and `residual`.  Per Linear, `pack` is WanModel._hot_pack's answer: the stacked operands of
+    fg_lora_apply_bf16, False (its adapters take the reference's torch ops, WanModel._hot) or None (no adapter)."""
+
+    def __init__(self, model, mod_rows):
+        self.model, self.eps = model, model.eps
+        self.fp8 = fp8 = model.fp8_dtype
+        self.hot = hot = bool(model.hot_loras)
+        # adapters on fg_lora_apply_bf16 next to the own GEMMs, bf16 or fp8 (comment on hot_lora_backend, WanVideoPipeline.load_lora)
+        self.hip_hot = hip_hot = hot and model.hot_lora_backend == "hip"
+        # fp8 mode: the norms of a block feed fp8 Linears only, so they write (e4m3 rows, scales) and no bf16 row (FAIRYGEN_FP8_FOLD); an
+        # adapter reads the bf16 row too: both outputs in one pass on the "hip" backend, the bf16 row and a separate quantisation on "torch"
+        self.want_bf16 = fp8 is None or hot or not FP8_FOLD
+        self.want_q8 = fp8 is not None and (hip_hot if hot else FP8_FOLD)
+        # x += gate * Linear(a) can happen in the GEMM's store: gates of one or two time rows, and adapters, if any, on the HIP kernel
+        self.own = mod_rows in (1, 2) and (hip_hot if hot else fp8 is None)
+        # fp8 Linears without HIP adapters: ffn.0 hands on its pre-activation and GELU(tanh) is fused into the quantisation of ffn.2's input
+        self.gelu_in_quant = fp8 is not None and not hip_hot
+
+    # ---- the norms: modulate(LN(x)), LN(x) * w + b, each alone or behind x += gate * y, and the bare x += gate * y
+    def modulate(self, x, mod, shift_idx, scale_idx, out=None):
+        if self.want_bf16 and self.want_q8:
+            return Act(*hip.ln_modulate_dual(x, mod, shift_idx, scale_idx, self.eps, out=out))
+        if self.want_q8:
+            return Act(None, hip.ln_modulate_fp8(x, mod, shift_idx, scale_idx, self.eps))
+        return Act(hip.ln_modulate(x, mod, shift_idx, scale_idx, self.eps, out=out))
+
+    def affine(self, x, norm):
+        """norm3 on its own has no fp8-only kernel: the bf16 row, which the fp8 Linear behind it quantises."""
+        if self.want_bf16 and self.want_q8:
+            return Act(*hip.ln_affine_dual(x, norm.weight, norm.bias, self.eps))
+        return Act(hip.ln_affine(x, norm.weight, norm.bias, self.eps))
+
+    def gate_residual(self, x, y, mod, gate_idx):
+        return hip.gate_residual(x, y, mod if gate_idx is not None else None, gate_idx, out=x)
+
+    def residual_modulate(self, x, y, mod, gate_idx, norm_mod, shift_idx, scale_idx, out=None):
+        if self.want_bf16 and self.want_q8:      # no fused kernel with both outputs
+            x = self.gate_residual(x, y, mod, gate_idx)
+            return x, self.modulate(x, norm_mod, shift_idx, scale_idx, out)
+        if self.want_q8:
+            x, q8 = hip.residual_ln_modulate_fp8(x, y, mod, gate_idx, shift_idx, scale_idx, self.eps, x_out=x, norm_mod=norm_mod)
+            return x, Act(None, q8)
+        x, h = hip.residual_ln_modulate(x, y, mod, gate_idx, shift_idx, scale_idx, self.eps, x_out=x, norm_out=out, norm_mod=norm_mod)
+        return x, Act(h)
+
+    def residual_affine(self, x, y, mod, gate_idx, norm):
+        if self.want_bf16 and self.want_q8:
+            x = self.gate_residual(x, y, mod, gate_idx)
+            return x, self.affine(x, norm)
+        if self.want_q8:
+            x, q8 = hip.residual_ln_affine_fp8(x, y, norm.weight, norm.bias, self.eps, mod, gate_idx, x_out=x)
+            return x, Act(None, q8)
+        x, h = hip.residual_ln_affine(x, y, norm.weight, norm.bias, self.eps, mod, gate_idx, x_out=x)
+        return x, Act(h)
+
+    # ---- the Linears
+    def q8(self, a):
+        return a.q8 if a.q8 is not None else hip.fp8_quant_rows(a.bf16, None)
+
+    def plain(self, a, names, weight, bias, w8, own=False, gelu=False, hip_adapters=True):
+        """Linear (+ the adapters of `names`: the column groups of a fused projection) (+ GELU(tanh)) of the Act `a` -> (1, rows, N) bf16.
+        weight / w8: the bf16 and e4m3 (None in bf16 mode) forms; own: bf16 mode, the own GEMM may take this Linear (FAIRYGEN_GEMM).
+        gelu (ffn.0): the result is nn.GELU's output — except with gelu_in_quant, where it is the pre-activation."""
+        m, fp8 = self.model, self.fp8
+        n, k = weight.shape
+        own = fp8 is None and own and own_gemm_ok(a.rows, n, k)
+        if hip_adapters and self.hip_hot and (fp8 is None or fp8_own_ok(n, k)):
+            pack = m._hot_pack(names)
+        elif gelu:      # an adapter adds to the pre-activation: only a Linear that has one gives up its fused GELU
+            pack = False if any(nm in m.hot_loras for nm in names) else None
+        else:
+            pack = False if self.hot else None
+        if gelu and pack is False:
+            own = False      # the reference's ops for this Linear: library GEMM, adapters, GELU
+        if gelu and pack is None and not self.gelu_in_quant:      # nothing between the Linear and its GELU: into the GEMM's store where one takes it
+            if fp8 is not None and fp8_own_ok(n, k):
+                return hip.gemm_fp8(*a.q8, w8, bias, act="gelu_tanh", lead_shape=(1, a.rows))
+            if own:
+                return gemm_bias_gelu_own(a.bf16, weight, bias)
+            if fp8 is None and m.gelu_epilogue:      # GELU(tanh) in the hipBLASLt epilogue: one pass less over the (n, ffn) tensor
+                return gemm_bias_gelu(a.bf16, weight, bias)
+        if fp8 is not None:
+            y = m._scaled_linear(*self.q8(a), w8, bias)
+        else:
+            y = (gemm_bias_own if own else gemm_bias)(a.bf16, weight, bias)
+        if gelu and pack:      # GELU moves from the GEMM's store into the adapter kernel's
+            return hip.lora_apply(a.bf16, pack[0], pack[1], y, mode="gelu_tanh")
+        m._hot_apply(names, a.bf16, y, pack)
+        return hip.activation(y, "gelu_tanh") if gelu and not self.gelu_in_quant else y
+
+    def residual(self, x, a, name, weight, bias, w8, mod, gate_idx, affine=None, modulate=None, out=None, tuned=False, store_ok=True,
+                 gelu=False):
+        """x (the residual stream, in place) += gate * (Linear(a) + adapters of `name`), gate = vector gate_idx of mod (None: 1), then the
+        norm behind it: affine = the LayerNorm module, or modulate = (table, shift_idx, scale_idx) with `out` an old bf16 row to write
+        into, or neither (last block).  Returns (x, Act or None).  Two forms (AutoWrappedLinear.forward, core/vram/layers.py:429-436, then
+        GateModule; the gate distributes over Linear + adapter): the add in the GEMM's store (fg_gemm_epilogue_bf16 / fg_gemm_fp8_bf16)
+        and in fg_lora_apply_bf16, then the norm alone; or a plain GEMM, the adapters, and the fused residual + norm kernel.
+        a: bf16; gelu: it is ffn.0's pre-activation (gelu_in_quant).  tuned / store_ok: ffn.2's library GEMM comes from the tuning table,
+        and FAIRYGEN_GEMM=fused-ffn2 keeps it there."""
+        m, fp8 = self.model, self.fp8
+        n, k = weight.shape
+        gmod = mod if gate_idx is not None else None
+        pack = m._hot_pack((name,)) if self.hip_hot else False if name in m.hot_loras else None
+        if self.own and store_ok and pack is not False and (own_gemm_ok(a.shape[1], n, k) if fp8 is None else fp8_own_ok(n, k)):
+            if fp8 is None:
+                gemm_residual(x, a, weight, bias, gmod, gate_idx)
+            else:
+                hip.gemm_fp8(*hip.fp8_quant_rows(a), w8, bias, out=x, residual=True, mod=gmod, gate_idx=gate_idx)
+            if pack:
+                hip.lora_apply(a, pack[0], pack[1], x, mode="add" if gmod is None else "gate", mod=gmod, gate_idx=gate_idx)
+            if affine is not None:
+                return x, self.affine(x, affine)
+            return x, self.modulate(x, *modulate, out=out) if modulate is not None else None
+        if fp8 is None:
+            y = (gemm_bias_tuned if tuned else gemm_bias)(a, weight, bias)
+        else:
+            y = m._scaled_linear(*hip.fp8_quant_rows(a, "gelu_tanh" if gelu else None), w8, bias)
+        if pack is not None:      # only then is nn.GELU's bf16 output needed
+            m._hot_apply((name,), hip.activation(a.clone(), "gelu_tanh") if gelu else a, y, pack)
+        if affine is not None:
+            return self.residual_affine(x, y, mod, gate_idx, affine)
+        if modulate is not None:
+            return self.residual_modulate(x, y, mod, gate_idx, *modulate, out=out)
+        return self.gate_residual(x, y, mod, gate_idx), None
 
 
 class RMSNorm(nn.Module):
@@ -246,8 +389,8 @@ class WanModel(nn.Module):
         # hot-loaded (unfused) LoRA adapters: module name -> [(alpha*A (r,in), B (out,r)), ...]; see add_hot_lora
         self.hot_loras = {}
         # how the block Linears evaluate them: "torch" (default): _hot, the reference's arithmetic op by op on library GEMMs; "hip": the
-        # adapters of a Linear stacked (stack_hot_loras) and applied by fg_lora_apply_bf16 next to the own GEMM's fused store (_hot_apply),
-        # the bf16 GEMM's or, in the fp8 Linear mode, fg_gemm_fp8_bf16's (_fp8_hot_residual; the adapter reads the bf16 activation)
+        # adapters of a Linear stacked (stack_hot_loras) and applied by fg_lora_apply_bf16 next to the own GEMM's fused store, the bf16
+        # GEMM's or, in the fp8 Linear mode, fg_gemm_fp8_bf16's (_BlockLinears.plain / .residual; the adapter reads the bf16 activation)
         self.hot_lora_backend = "torch"
         self._hot_packs = {}
         # fp8 Linear mode of the blocks (None = bf16 GEMMs); see enable_fp8_linear
@@ -341,10 +484,9 @@ class WanModel(nn.Module):
             self._hot_packs[names] = pack
         return self._hot_packs[names]
 
-    def _hot_apply(self, names, x, out, use_hip):
-        """out += the adapters of the Linears `names` (column groups of out) applied to x: one fg_lora_apply_bf16 launch when `use_hip`
-        and the kernel takes the pack, else _hot per Linear."""
-        pack = self._hot_pack(names) if use_hip else False
+    def _hot_apply(self, names, x, out, pack):
+        """out += the adapters of the Linears `names` (column groups of out) applied to x.  pack: what _hot_pack(names) gave — one
+        fg_lora_apply_bf16 launch; False — _hot per Linear on its column slice; None — nothing to add."""
         if pack:
             return hip.lora_apply(x, pack[0], pack[1], out, groups=len(names), mode="add")
         if pack is False:
@@ -352,22 +494,6 @@ class WanModel(nn.Module):
             for j, nm in enumerate(names):
                 self._hot(nm, x, out[..., j * c:(j + 1) * c])
         return out
-
-    def _fp8_hot_residual(self, name, t, w8, bias, x, mod, gate_idx):
-        """fp8 Linear mode with hot_lora_backend "hip": x (the residual stream, in place) += gate * (fp8_linear(t) + adapters of `name`
-        on the bf16 t), gate = vector gate_idx of mod or 1 (AutoWrappedLinear.forward, core/vram/layers.py:429-436, then GateModule).
-        The add happens in fg_gemm_fp8_bf16's store and in fg_lora_apply_bf16 (the gate distributes over Linear + adapter) where the own
-        fp8 GEMM takes the shape and the adapter kernel the pack; else the "torch" backend's ops for this Linear and one residual pass."""
-        t8 = hip.fp8_quant_rows(t)
-        pk = self._hot_pack((name,))
-        gmod = mod if gate_idx is not None else None
-        if fp8_own_ok(w8.shape[0], w8.shape[1]) and mod.mod_rows in (1, 2) and pk is not False:
-            hip.gemm_fp8(*t8, w8, bias, out=x, residual=True, mod=gmod, gate_idx=gate_idx)
-            if pk:
-                hip.lora_apply(t, pk[0], pk[1], x, mode="add" if gmod is None else "gate", mod=gmod, gate_idx=gate_idx)
-            return x
-        y = self._hot_apply((name,), t, self._scaled_linear(*t8, w8, bias), True)
-        return hip.gate_residual(x, y, gmod, gate_idx, out=x)
 
     # ------------------------------------------------------------------ host-side tables
     def rope_tables(self, f, h, w, device):
@@ -414,29 +540,16 @@ class WanModel(nn.Module):
         x = x.view(b, f, h, w, px, py, pz, self.out_dim).permute(0, 7, 1, 4, 2, 5, 3, 6)
         return x.reshape(b, self.out_dim, f * px, h * py, w * pz)
 
-    def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, own, lin, hip_hot=False):
-        """Block i's self-attention half (reference :139-146, :225-226): h = modulate(norm1(x)) in; returns the residual stream after
-        x += gate_msa * o(attn(...)) and h = norm3(x).  Yields right after each exchange of a token-sharded run has been started.
-        lin: the fp8 Linear closure of the block (None in bf16 mode).  fp8 mode with hip_hot: h comes and goes as the dual-output norm's
-        (bf16 row, (e4m3 rows, scales)) — the fp8 Linears take the pair, the adapters the bf16 row."""
+    def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, lin, w8):
+        """Block i's self-attention half (reference :139-146, :225-226): h = modulate(norm1(x)) in (an Act); returns the residual stream
+        after x += gate_msa * o(attn(...)) and h = norm3(x).  Yields right after each exchange of a token-sharded run has been started.
+        lin: the _BlockLinears of this forward; w8: the block's e4m3 weights (Nones in bf16 mode)."""
         c, nh, eps = self.dim, self.num_heads, self.eps
-        fp8 = self.fp8_dtype if lin is not None else None
-        hot = bool(self.hot_loras)
         sharded = shard is not None and shard.active
         wqkv, bqkv, _, _ = blk.fused_weights()
         sa = blk.self_attn
-        hot8 = hip_hot and fp8 is not None
-        if hot8:
-            h, h8 = h
-            qkv = lin(h8, 0, bqkv)
-        elif fp8 is not None:
-            qkv = lin(h, 0, bqkv)
-        elif GEMM_BACKEND == "all" and own_gemm_ok(h.shape[1], 3 * c, c):      # a plain Linear: hot adapters add to its output below
-            qkv = gemm_bias_own(h, wqkv, bqkv)
-        else:
-            qkv = gemm_bias(h, wqkv, bqkv)
-        if hot:      # one launch on the fused buffer (hip backend), or per projection on its column slice
-            self._hot_apply(tuple(f"blocks.{i}.self_attn.{nm}" for nm in "qkv"), h, qkv, hip_hot and (not hot8 or fp8_own_ok(3 * c, c)))
+        # one GEMM for q | k | v, and one adapter launch on the fused buffer (hip backend) or one per projection on its column slice
+        qkv = lin.plain(h, tuple(f"blocks.{i}.self_attn.{nm}" for nm in "qkv"), wqkv, bqkv, w8[0], own=GEMM_BACKEND == "all")
         v = qkv[..., 2 * c:]
         # rope tables per operand: fp64 (cos, sin) for both, or the fp32 interleaved tables of k and q (rope_tables)
         rk, rq = ((cos, None), (sin, None)) if cos.dtype == torch.float32 else ((cos, sin), (cos, sin))
@@ -472,60 +585,7 @@ class WanModel(nn.Module):
             k, v = pending.wait()
             a = sa.attn(q, k, v) if scale is None else sa.attn(q, k, v, scale=scale)
         # x += gate_msa*y ; h = norm3(x)  (reference :225-226)
-        if hot8:      # the gated add in the fp8 GEMM's store, then norm3 with both outputs
-            x = self._fp8_hot_residual(f"blocks.{i}.self_attn.o", a, blk.fp8_weights(fp8)[1], sa.o.bias, x, mod, 2)
-            return x, hip.ln_affine_dual(x, blk.norm3.weight, blk.norm3.bias, eps)
-        pk = self._hot_pack((f"blocks.{i}.self_attn.o",)) if hip_hot else None
-        if own and own_gemm_ok(a.shape[1], c, c) and pk is not False:      # the gated add happens in the GEMM's store
-            x = gemm_residual(x, a, sa.o.weight, sa.o.bias, mod, 2)
-            if pk:      # x += gate_msa * l: the gate distributes over Linear + adapter
-                hip.lora_apply(a, pk[0], pk[1], x, mode="gate", mod=mod, gate_idx=2)
-            h = hip.ln_affine(x, blk.norm3.weight, blk.norm3.bias, eps)
-        else:
-            y = gemm_bias(a, sa.o.weight, sa.o.bias) if fp8 is None else lin(a, 1, sa.o.bias)
-            if hot:
-                self._hot_apply((f"blocks.{i}.self_attn.o",), a, y, hip_hot)
-            if fp8 is not None and not hot and FP8_FOLD:
-                x, h = hip.residual_ln_affine_fp8(x, y, blk.norm3.weight, blk.norm3.bias, eps, mod, 2, x_out=x)
-            else:
-                x, h = hip.residual_ln_affine(x, y, blk.norm3.weight, blk.norm3.bias, eps, mod, 2, x_out=x)
-        return x, h
-
-    def _block_tail_fp8_hot(self, i, blk, mod, next_mod, x, h, context, ctx8, lin, kv_cache):
-        """Block i after its self-attention half in the fp8 Linear mode with hot_lora_backend "hip" (reference :170-185, :208-209,
-        :226-228 on AutoWrappedLinear.forward, core/vram/layers.py:429-436): cross-attention, ffn and the next block's norm1 + modulate.
-        h = norm3(x) in, as (bf16 row, (e4m3 rows, scales)); returns x and the next h in the same form (None after the last block)."""
-        c, nh, eps = self.dim, self.num_heads, self.eps
-        ca, w8 = blk.cross_attn, blk.fp8_weights(self.fp8_dtype)
-        _, _, _, bkv_c = blk.fused_weights()
-        h, h8 = h
-        qc = self._hot_apply((f"blocks.{i}.cross_attn.q",), h, lin(h8, 2, ca.q.bias), fp8_own_ok(c, c))
-        qc = hip.rmsnorm_rope(qc, ca.norm_q.weight, nh, eps)
-        if kv_cache is not None and i in kv_cache:
-            kc, vc = kv_cache[i]
-        else:      # 512 context rows, once per denoise loop with a kv_cache: the "torch" backend's ops
-            kvc = self._scaled_linear(*ctx8, w8[3], bkv_c)
-            self._hot(f"blocks.{i}.cross_attn.k", context, kvc[..., :c])
-            self._hot(f"blocks.{i}.cross_attn.v", context, kvc[..., c:])
-            kc, vc = hip.rmsnorm_rope(kvc[..., :c], ca.norm_k.weight, nh, eps), kvc[..., c:]
-            if kv_cache is not None:
-                kv_cache[i] = (kc, vc)
-        ac = ca.attn(qc, kc, vc)
-        # x += y ; h = modulate(norm2(x))  (reference :226-227)
-        x = self._fp8_hot_residual(f"blocks.{i}.cross_attn.o", ac, w8[4], ca.o.bias, x, mod, None)
-        h, h8 = hip.ln_modulate_dual(x, mod, 3, 4, eps, out=h)
-        # --- ffn (reference :208-209,228): the adapter adds to ffn.0's pre-activation, so GELU is the adapter kernel's store (in place: f is
-        # nn.GELU's bf16 output, which ffn.2's adapter reads and its fp8 Linear quantises); without an adapter it is the GEMM's own
-        name, f0, b0 = f"blocks.{i}.ffn.0", w8[5].shape[0], blk.ffn[0].bias
-        pk = self._hot_pack((name,)) if fp8_own_ok(f0, c) else False
-        if pk is None:
-            f = hip.gemm_fp8(*h8, w8[5], b0, act="gelu_tanh", lead_shape=(1, h8[0].shape[0]))
-        elif pk:
-            f = hip.lora_apply(h, pk[0], pk[1], lin(h8, 5, b0), mode="gelu_tanh")
-        else:
-            f = hip.activation(self._hot(name, h, lin(h8, 5, b0)), "gelu_tanh")
-        x = self._fp8_hot_residual(f"blocks.{i}.ffn.2", f, w8[6], blk.ffn[2].bias, x, mod, 5)
-        return x, (hip.ln_modulate_dual(x, next_mod, 0, 1, eps, out=h) if next_mod is not None else None)
+        return lin.residual(x, a, f"blocks.{i}.self_attn.o", sa.o.weight, sa.o.bias, w8[1], mod, 2, affine=blk.norm3)
 
     # ------------------------------------------------------------------ the 30-block token forward
     def forward_tokens(self, x, context, mod_rows_t, t_rows, first_rows, rope, shard=None, shard_total=None, tea_cache=None,
@@ -568,29 +628,16 @@ class WanModel(nn.Module):
         blocks = list(self.blocks)
         if skip_blocks:
             blocks, x = [], tea_cache.update(x)
-        sharded = shard is not None and shard.active
-        hot = bool(self.hot_loras)
         fp8 = self.fp8_dtype
-        # adapters on fg_lora_apply_bf16 next to the own GEMMs, bf16 or fp8 (comment on hot_lora_backend, WanVideoPipeline.load_lora)
-        hip_hot = hot and self.hot_lora_backend == "hip"
-        # fp8 Linears + adapters on the HIP backend: the residual adds move into fg_gemm_fp8_bf16's store, and every norm writes the bf16
-        # row (for the adapter) and the (e4m3 rows, scales) pair (for the GEMM) in one pass: h = (bf16 row, pair)
-        hot8 = hip_hot and fp8 is not None
-        ctx8 = hip.fp8_quant_rows(context) if fp8 is not None else None      # the text context is the same for all blocks
+        lin = _BlockLinears(self, mod_rows_t.shape[0])      # the mode decisions of this forward
+        ctx = Act(context, hip.fp8_quant_rows(context) if fp8 is not None else None)      # the text context is the same for all blocks
         mods = [hip.ModTable((blk.modulation.to(mod_rows_t.dtype) + mod_rows_t).contiguous(), first_rows) for blk in blocks]
-        # fp8 mode: the four norms of a block feed fp8 Linears only, so they hand over (e4m3 rows, row scales) directly;
-        # a hot-loaded adapter needs the bf16 row too: the dual-output norms with the "hip" backend (hot8), else the separate quantisation stays
-        fold8 = fp8 is not None and not hot and FP8_FOLD
-        h = (hip.ln_modulate_dual if hot8 else hip.ln_modulate_fp8 if fold8 else hip.ln_modulate)(x, mods[0], 0, 1, eps) if blocks else None
+        h = lin.modulate(x, mods[0], 0, 1) if blocks else None
         for i, blk in enumerate(blocks):
             mod = mods[i]
-            wqkv, bqkv, wkv_c, bkv_c = blk.fused_weights()
-            sa, ca = blk.self_attn, blk.cross_attn
-            if fp8 is not None:
-                w8 = blk.fp8_weights(fp8)
-                # t: a bf16 tensor (quantised here) or the (fp8 rows, scales) pair a fused norm kernel already produced
-                lin = lambda t, j, bias, act=None: self._scaled_linear(*(t if isinstance(t, tuple) else hip.fp8_quant_rows(t, act)), w8[j], bias)      # noqa: E731
-            own = fp8 is None and (not hot or hip_hot) and mod.mod_rows in (1, 2)
+            _, _, wkv_c, bkv_c = blk.fused_weights()
+            ca, ffn0, ffn2 = blk.cross_attn, blk.ffn[0], blk.ffn[2]
+            w8 = blk.fp8_weights(fp8) if fp8 is not None else (None,) * 7
             if cfg_prefix is not None and i == 0 and "owner" in cfg_prefix:
                 if cfg_prefix.get("taken"):
                     raise RuntimeError("cfg_prefix is shared by exactly two forwards of one step (one computes block 0's self-attention half, "
@@ -604,93 +651,33 @@ class WanModel(nn.Module):
                     yield i
                 x = cfg_prefix.pop("x_sa")
                 cfg_prefix["taken"] = True
-                h = (hip.ln_affine_dual if hot8 else hip.ln_affine)(x, blk.norm3.weight, blk.norm3.bias, eps)
-                reuse = True
+                h = lin.affine(x, blk.norm3)
             else:
-                reuse = False
                 if cfg_prefix is not None and i == 0:
                     cfg_prefix["owner"] = True
-            # --- self attention (reference :139-146)
-            if not reuse:
-                x, h = yield from self._self_attention_steps(i, blk, mod, x, h, cos, sin, shard, shard_total, own, lin if fp8 is not None else None, hip_hot)
+                # --- self attention (reference :139-146)
+                x, h = yield from self._self_attention_steps(i, blk, mod, x, h, cos, sin, shard, shard_total, lin, w8)
                 if cfg_prefix is not None and i == 0:
                     cfg_prefix["x_sa"] = x.clone()
             # --- cross attention (reference :170-185)
-            if hot8:
-                x, h = self._block_tail_fp8_hot(i, blk, mod, mods[i + 1] if i + 1 < len(blocks) else None, x, h, context, ctx8, lin, kv_cache)
-                continue
-            if fp8 is None:
-                qc = gemm_bias_own(h, ca.q.weight, ca.q.bias) if own and own_gemm_ok(h.shape[1], c, c) else gemm_bias(h, ca.q.weight, ca.q.bias)
-            else:
-                qc = lin(h, 2, ca.q.bias)
-            if hot:
-                self._hot_apply((f"blocks.{i}.cross_attn.q",), h, qc, hip_hot)
+            qc = lin.plain(h, (f"blocks.{i}.cross_attn.q",), ca.q.weight, ca.q.bias, w8[2], own=lin.own)
             qc = hip.rmsnorm_rope(qc, ca.norm_q.weight, nh, eps)
             if kv_cache is not None and i in kv_cache:
                 kc, vc = kv_cache[i]
-            else:
-                kvc = gemm_bias(context, wkv_c, bkv_c) if fp8 is None else self._scaled_linear(*ctx8, w8[3], bkv_c)
-                if hot:
-                    self._hot(f"blocks.{i}.cross_attn.k", context, kvc[..., :c])
-                    self._hot(f"blocks.{i}.cross_attn.v", context, kvc[..., c:])
+            else:      # 512 context rows, once per denoise loop with a kv_cache: library GEMM, adapters on the reference's torch ops
+                kvc = lin.plain(ctx, (f"blocks.{i}.cross_attn.k", f"blocks.{i}.cross_attn.v"), wkv_c, bkv_c, w8[3], hip_adapters=False)
                 kc, vc = hip.rmsnorm_rope(kvc[..., :c], ca.norm_k.weight, nh, eps), kvc[..., c:]
                 if kv_cache is not None:
                     kv_cache[i] = (kc, vc)
             ac = ca.attn(qc, kc, vc)
-            # x += y ; h = modulate(norm2(x))  (reference :226-227)
-            pk = self._hot_pack((f"blocks.{i}.cross_attn.o",)) if hip_hot else None
-            if own and own_gemm_ok(ac.shape[1], c, c) and pk is not False:
-                x = gemm_residual(x, ac, ca.o.weight, ca.o.bias)
-                if pk:
-                    hip.lora_apply(ac, pk[0], pk[1], x, mode="add")
-                h = hip.ln_modulate(x, mod, 3, 4, eps)
-            else:
-                y = gemm_bias(ac, ca.o.weight, ca.o.bias) if fp8 is None else lin(ac, 4, ca.o.bias)
-                if hot:
-                    self._hot_apply((f"blocks.{i}.cross_attn.o",), ac, y, hip_hot)
-                if fold8:
-                    x, h = hip.residual_ln_modulate_fp8(x, y, mod, None, 3, 4, eps, x_out=x)
-                else:
-                    x, h = hip.residual_ln_modulate(x, y, mod, None, 3, 4, eps, x_out=x)
-            # --- ffn (reference :208-209,228)
-            if fp8 is not None:      # ffn.0 -> bf16, GELU(tanh) fused into the quantisation of ffn.2's input
-                pre = lin(h, 5, blk.ffn[0].bias)
-                if hot:
-                    self._hot(f"blocks.{i}.ffn.0", h, pre)
-                y = lin(pre, 6, blk.ffn[2].bias, "gelu_tanh")
-                f = None
-            elif hip_hot and self._hot_pack((f"blocks.{i}.ffn.0",)):      # the adapter adds to the pre-activation: GELU moves from the GEMM's store into the adapter kernel's
-                pk = self._hot_pack((f"blocks.{i}.ffn.0",))
-                pre = (gemm_bias_own if GEMM_BACKEND == "all" and own_gemm_ok(h.shape[1], blk.ffn[0].weight.shape[0], c) else gemm_bias)(h, blk.ffn[0].weight, blk.ffn[0].bias)
-                f = hip.lora_apply(h, pk[0], pk[1], pre, mode="gelu_tanh")
-            elif hot and f"blocks.{i}.ffn.0" in self.hot_loras:      # the adapter adds to the pre-activation: no epilogue fusion
-                f = hip.activation(self._hot(f"blocks.{i}.ffn.0", h, gemm_bias(h, blk.ffn[0].weight, blk.ffn[0].bias)), "gelu_tanh")
-            elif GEMM_BACKEND == "all" and own_gemm_ok(h.shape[1], blk.ffn[0].weight.shape[0], c):      # GELU(tanh) in the own GEMM's store
-                f = gemm_bias_gelu_own(h, blk.ffn[0].weight, blk.ffn[0].bias)
-            elif self.gelu_epilogue:      # GELU(tanh) in the hipBLASLt epilogue: one pass less over the (n, ffn) tensor
-                f = gemm_bias_gelu(h, blk.ffn[0].weight, blk.ffn[0].bias)
-            else:
-                f = hip.activation(gemm_bias(h, blk.ffn[0].weight, blk.ffn[0].bias), "gelu_tanh")
-            pk = self._hot_pack((f"blocks.{i}.ffn.2",)) if hip_hot else None
-            if own and GEMM_BACKEND != "fused-ffn2" and own_gemm_ok(f.shape[1], c, f.shape[2]) and pk is not False:      # x += gate_mlp * ffn.2(f) in the store
-                x = gemm_residual(x, f, blk.ffn[2].weight, blk.ffn[2].bias, mod, 5)
-                if pk:
-                    hip.lora_apply(f, pk[0], pk[1], x, mode="gate", mod=mod, gate_idx=5)
-                if i + 1 < len(blocks):
-                    h = hip.ln_modulate(x, mods[i + 1], 0, 1, eps, out=h)
-                continue
-            if fp8 is None:
-                y = gemm_bias_tuned(f, blk.ffn[2].weight, blk.ffn[2].bias)
-            if hot and f"blocks.{i}.ffn.2" in self.hot_loras:
-                if f is None:
-                    f = hip.activation(pre.clone(), "gelu_tanh")
-                self._hot_apply((f"blocks.{i}.ffn.2",), f, y, hip_hot)
-            if i + 1 < len(blocks) and fold8:
-                x, h = hip.residual_ln_modulate_fp8(x, y, mod, 5, 0, 1, eps, x_out=x, norm_mod=mods[i + 1])
-            elif i + 1 < len(blocks):   # x += gate_mlp*y fused with the NEXT block's modulate(norm1(x))
-                x, h = hip.residual_ln_modulate(x, y, mod, 5, 0, 1, eps, x_out=x, norm_out=h, norm_mod=mods[i + 1])
-            else:
-                x = hip.gate_residual(x, y, mod, 5, out=x)
+            # x += y ; h = modulate(norm2(x))  (reference :226-227); with both norm outputs wanted, norm3's bf16 row is written over
+            x, h = lin.residual(x, ac, f"blocks.{i}.cross_attn.o", ca.o.weight, ca.o.bias, w8[4], mod, None, modulate=(mod, 3, 4),
+                                out=h.bf16 if lin.want_q8 else None)
+            # --- ffn (reference :208-209,228); x += gate_mlp*y is followed by the NEXT block's modulate(norm1(x)), written over norm2's row
+            f = lin.plain(h, (f"blocks.{i}.ffn.0",), ffn0.weight, ffn0.bias, w8[5], own=GEMM_BACKEND == "all", gelu=True)
+            x, h = lin.residual(x, f, f"blocks.{i}.ffn.2", ffn2.weight, ffn2.bias, w8[6], mod, 5,
+                                modulate=(mods[i + 1], 0, 1) if i + 1 < len(blocks) else None, out=h.bf16,
+                                tuned=True, store_ok=GEMM_BACKEND != "fused-ffn2", gelu=lin.gelu_in_quant)
         if tea_cache is not None and blocks:
             tea_cache.store(x)
         # --- head (reference :261-268): table (R,2,C) = modulation + t
