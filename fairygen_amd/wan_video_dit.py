@@ -64,6 +64,9 @@ def gemm_bias_tuned(x, weight, bias):
 # library (round 2's default); "fused-ffn2": ffn.2 as well; "lib": everything on hipBLASLt.  Measurements: DESIGN.md §5.
 GEMM_BACKEND = os.environ.get("FAIRYGEN_GEMM", "all")
 GEMM_MIN_TILES = 64      # round 2 asked for two rounds of the CUs (512 tiles); see own_gemm_ok
+# hot_backend="fused": how an adapter is folded into a weight.  "hip" (default): fg_lora_fuse_bf16 where it takes the Linear, torch ops
+# for the others; "torch": the reference's three torch ops on the device for every Linear (the A/B leg of tools/hot_lora_step.py --swap).
+LORA_FUSE = os.environ.get("FAIRYGEN_LORA_FUSE", "hip")
 FP8_FOLD = os.environ.get("FAIRYGEN_FP8_FOLD", "1") != "0"      # fp8 mode: norm kernels emit (e4m3 rows, scales) directly
 FP8_GEMM = os.environ.get("FAIRYGEN_FP8_GEMM", "own")           # fp8 mode: "own" = fg_gemm_fp8_bf16, "lib" = torch._scaled_mm (hipBLASLt)
 
@@ -391,8 +394,12 @@ class WanModel(nn.Module):
         # how the block Linears evaluate them: "torch" (default): _hot, the reference's arithmetic op by op on library GEMMs; "hip": the
         # adapters of a Linear stacked (stack_hot_loras) and applied by fg_lora_apply_bf16 next to the own GEMM's fused store, the bf16
         # GEMM's or, in the fp8 Linear mode, fg_gemm_fp8_bf16's (_BlockLinears.plain / .residual; the adapter reads the bf16 activation)
+        # "fused": the adapters are folded into the weights one at a time (fg_lora_fuse_bf16) and the originals kept, so clear_hot_loras()
+        # can put them back; hot_loras stays empty and the forward is the adapter-free one (add_hot_lora)
         self.hot_lora_backend = "torch"
         self._hot_packs = {}
+        # backend "fused": module name -> the Linear's weight as it was before its first adapter
+        self._fused_stash = {}
         # fp8 Linear mode of the blocks (None = bf16 GEMMs); see enable_fp8_linear
         self.fp8_dtype = None
         self._ones = {}
@@ -406,6 +413,7 @@ class WanModel(nn.Module):
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
         self.invalidate_fused()
+        self._fused_stash = {}      # the new weights are the new originals
         return out
 
     def _apply(self, fn, *args, **kwargs):
@@ -413,6 +421,7 @@ class WanModel(nn.Module):
         self.invalidate_fused()
         self._rope_cache = {}
         self._hot_packs = {}
+        self._fused_stash = {name: fn(w) for name, w in self._fused_stash.items()}
         return out
 
     # ------------------------------------------------------------------ fp8 Linear mode (core/vram/layers.py:312,321-357)
@@ -442,25 +451,97 @@ class WanModel(nn.Module):
                                 out_dtype=torch.bfloat16).unsqueeze(0)
 
     # ------------------------------------------------------------------ hot-loaded LoRA (core/vram/layers.py:417-436)
-    def add_hot_lora(self, name, lora_a, lora_b):
-        """Attach an unfused adapter to Linear `name` ("blocks.3.self_attn.q", ...): its output becomes
-        linear(x) + x @ A^T @ B^T, evaluated left to right in the pipeline dtype like AutoWrappedLinear.lora_forward
-        (`lora_a` already carries alpha, base_pipeline.py:258).  Adapters stack; clear_hot_loras() removes them all."""
-        mod = dict(self.named_modules()).get(name)
+    def check_hot_backend(self, backend):
+        """Adapters of the restorable fused backend and unfused ones do not mix on one module: the stash must stay the adapter-free weight."""
+        if backend == "fused" and self.hot_loras:
+            raise ValueError(f"hot_backend='fused' while unfused ('torch' / 'hip') adapters are attached to {len(self.hot_loras)} Linears: "
+                             "call clear_lora() first")
+        if backend != "fused" and getattr(self, "_fused_stash", None):
+            raise ValueError(f"hot_backend={backend!r} while restorable fused adapters are attached to {len(self._fused_stash)} Linears: "
+                             "call clear_lora() first")
+
+    def add_hot_lora(self, name, lora_a, lora_b, alpha=1.0):
+        """Attach an adapter to Linear `name` ("blocks.3.self_attn.q", ...) so that clear_hot_loras() can remove it again.
+        hot_lora_backend "torch" / "hip": unfused; the Linear's output becomes linear(x) + x @ A^T @ B^T, evaluated left to right in the
+        pipeline dtype like AutoWrappedLinear.lora_forward (`lora_a` already carries alpha, base_pipeline.py:258; `alpha` stays 1).
+        "fused": the weight becomes bf16(w + bf16(alpha * bf16(B A))), fuse_lora_to_base_model's arithmetic (`lora_a` WITHOUT alpha: the
+        reference rounds alpha * (B A) after the product), and the original is kept on the device (_fuse_hot).  Adapters stack."""
+        try:
+            mod = self.get_submodule(name)
+        except AttributeError:
+            mod = None
         if not isinstance(mod, nn.Linear):
             raise KeyError(f"{name} is not a Linear of this model")
         if lora_a.shape[1] != mod.in_features or lora_b.shape[0] != mod.out_features or lora_a.shape[0] != lora_b.shape[1]:
             raise ValueError(f"LoRA shapes {tuple(lora_a.shape)}, {tuple(lora_b.shape)} do not fit {name} "
                              f"({mod.in_features} -> {mod.out_features})")
+        backend = getattr(self, "hot_lora_backend", "torch")
+        self.check_hot_backend(backend)
         w = mod.weight
-        self.hot_loras.setdefault(name, []).append((lora_a.to(device=w.device, dtype=w.dtype).contiguous(),
-                                                    lora_b.to(device=w.device, dtype=w.dtype).contiguous()))
+        lora_a, lora_b = lora_a.to(device=w.device, dtype=w.dtype), lora_b.to(device=w.device, dtype=w.dtype)
         self._hot_packs = {}
+        if backend == "fused":
+            return self._fuse_hot(name, w, lora_a, lora_b, alpha)
+        if alpha != 1.0:
+            raise ValueError("add_hot_lora: on the unfused backends lora_a carries alpha; `alpha` is for hot_lora_backend 'fused'")
+        self.hot_loras.setdefault(name, []).append((lora_a.contiguous(), lora_b.contiguous()))
 
+    def _block_copies(self, name):
+        """The derived copies that hold the weight of block Linear `name`: (block, slot and first row in DiTBlock.fused_weights() or None,
+        slot and first row in DiTBlock.fp8_weights()); None for a Linear outside the blocks, which has no copies."""
+        parts = name.split(".")
+        if parts[0] != "blocks" or len(parts) != 4:
+            return None
+        blk, dim = self.blocks[int(parts[1])], self.dim
+        where = {"self_attn.q": (0, 0, 0, 0), "self_attn.k": (0, dim, 0, dim), "self_attn.v": (0, 2 * dim, 0, 2 * dim), "self_attn.o": (None, 0, 1, 0),
+                 "cross_attn.q": (None, 0, 2, 0), "cross_attn.k": (2, 0, 3, 0), "cross_attn.v": (2, dim, 3, dim), "cross_attn.o": (None, 0, 4, 0),
+                 "ffn.0": (None, 0, 5, 0), "ffn.2": (None, 0, 6, 0)}.get(parts[2] + "." + parts[3])
+        return where and (blk,) + where
+
+    @torch.no_grad()
+    def _fuse_hot(self, name, w, lora_a, lora_b, alpha):
+        """hot_lora_backend "fused": one adapter into the weight `w` of Linear `name`, in place, with the original stashed before the first.
+        fg_lora_fuse_bf16 where it takes the Linear (bf16, features in 64s, rank up to 128), else — and for every Linear with
+        FAIRYGEN_LORA_FUSE=torch — the reference's torch ops on the device.  The block's derived copies follow: the kernel writes the e4m3 copy along with the weight where one exists, the rows in the
+        fused QKV / cross KV weight are copied from the new weight; on the torch-op path the block's copies are dropped and rebuilt by the
+        next forward."""
+        if w.device.type != "cuda":
+            raise hip.HipLibraryError(f"add_hot_lora: hot_backend='fused' rewrites weights on a HIP device, {name} is on {w.device} (no CPU fallback)")
+        if name not in self._fused_stash:
+            self._fused_stash[name] = w.detach().clone()
+        n, k = w.shape
+        rank = lora_a.shape[0]
+        copies = self._block_copies(name)
+        if LORA_FUSE == "hip" and w.dtype == torch.bfloat16 and w.is_contiguous() and hip.lora_fuse_ok(n, k, rank):
+            r = -(-rank // hip.LORA_RANK_TILE) * hip.LORA_RANK_TILE
+            if r == rank:
+                a_t, b = lora_a.T.contiguous(), lora_b.contiguous()
+            else:
+                a_t, b = torch.zeros((k, r), dtype=w.dtype, device=w.device), torch.zeros((n, r), dtype=w.dtype, device=w.device)
+                a_t[:, :rank], b[:, :rank] = lora_a.T, lora_b
+            w8 = None
+            if copies is not None and copies[0]._fp8 is not None:
+                w8 = copies[0]._fp8[1][copies[3]][copies[4]:copies[4] + n]
+            hip.lora_fuse(w.data, a_t, b, alpha, out_fp8=w8)
+            if copies is not None and copies[1] is not None and copies[0]._fused is not None:
+                copies[0]._fused[copies[1]][copies[2]:copies[2] + n].copy_(w)
+        else:
+            w.add_(alpha * torch.mm(lora_b, lora_a))
+            if copies is not None:
+                copies[0]._fused = copies[0]._fp8 = None
+
+    @torch.no_grad()
     def clear_hot_loras(self):
-        n = len(self.hot_loras)
+        """Drop every adapter attached through add_hot_lora: the unfused ones are forgotten, the weights of the "fused" backend get their
+        stashed originals back (bit for bit).  Returns the number of Linears that carried one."""
+        n = len(self.hot_loras) + len(self._fused_stash)
         self.hot_loras = {}
         self._hot_packs = {}
+        if self._fused_stash:
+            for name, w0 in self._fused_stash.items():
+                self.get_submodule(name).weight.copy_(w0)
+            self._fused_stash = {}
+            self.invalidate_fused()
         return n
 
     def _hot(self, name, x, out):

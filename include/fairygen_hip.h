@@ -44,7 +44,7 @@ extern "C" {
 
 typedef void* fg_stream_t;   /* hipStream_t */
 
-int         fg_version(void);            /* ABI version, currently 6 */
+int         fg_version(void);            /* ABI version, currently 7 */
 const char* fg_last_error(void);         /* thread-local, valid until the next failing call */
 
 /* ------------------------------------------------------------------ DiT token-side kernels (HBM-bound)
@@ -156,6 +156,19 @@ int fg_gemm_epilogue_bf16_s(const void* a, int64_t lda, const void* w, const voi
 int fg_lora_apply_bf16(const void* x, int64_t ldx, const void* a, const void* b, void* out, int64_t ldc, int64_t M, int64_t K,
                        int64_t Ng, int64_t R, int64_t G, int mode, const void* gate, int64_t gate_rows, int64_t gate_ld,
                        int64_t first_rows, fg_stream_t stream);
+
+/* One LoRA adapter folded into one Linear's weight, lora/general.py fuse_lora_to_base_model (fairygen_amd/lora.py:38-58 restates it:
+ * `weight + alpha * torch.mm(up, down)` in the pipeline dtype), with the original kept by the caller so the fuse can be undone:
+ *     d = bf16(B[N, R] A[R, K])  (fp32 accumulate over R, one rounding),  d = bf16(alpha * d),  w' = bf16(w_src + d)
+ * w_src (N, K) with leading dimension ld_src; w_dst (N, K) with its own ld_dst: w_src itself (same ld: in place) or memory that does not
+ * overlap it, e.g. the row range of q, k or v in a block's fused QKV weight.  w_dst_fp8 (may be NULL; rows ld_fp8 bytes apart): the same
+ * w' cast to OCP e4m3 with unit scale, the bytes of w'.to(float8_e4m3fn) for every value (like that cast it does not saturate: |w'| up
+ * to 464 rounds to 448, larger values and NaN become the NaN byte with the sign); it must not overlap w_src or w_dst.  a_t is A TRANSPOSED, a contiguous (K, R) matrix, b a contiguous
+ * (N, R) one; R is the rank padded by the host with zero columns to 32, 64, 96 or 128.  N %% 64 == 0, K %% 64 == 0, ld_src %% 8 == 0,
+ * ld_dst %% 8 == 0, ld_fp8 %% 16 == 0, all pointers 16-byte aligned.  Every element of w is read once and written once; nothing else of
+ * size (N, K) exists.  No allocation, no host synchronisation. */
+int fg_lora_fuse_bf16(const void* w_src, int64_t ld_src, void* w_dst, int64_t ld_dst, void* w_dst_fp8, int64_t ld_fp8, const void* a_t,
+                      const void* b, int64_t N, int64_t K, int64_t R, float alpha, fg_stream_t stream);
 
 /* Diagnostics for the persistent GEMM's unit scheduler: launch only `workgroups` workgroups (a multiple of the XCD count, at most one
  * per CU; 0 = one per CU again).  The units of a launch are fixed by the shape; workgroups take them from per-XCD cursors, so the result
