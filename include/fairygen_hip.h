@@ -12,6 +12,9 @@
  *   - no allocation, no ownership transfer, no host synchronisation: the caller passes every buffer,
  *     work is enqueued asynchronously on `stream` (a hipStream_t; NULL = the default stream);
  *   - re-entrant across streams and devices, no mutable global state;
+ *     every launch of an entry point (its second kernel included: the attention combine, the GEMM's reduce) goes to `stream`, the
+ *     first call of a process included, so a call may be recorded by a stream capture (tests/test_stream_contract.py: every entry point
+ *     captured on a side stream and replayed, ordered behind a producer on a side stream, and as the first launch of a process);
  *   - the documented exception to the two points above: fg_gemm_epilogue_bf16 and fg_gemm_fp8_bf16 keep the scheduler block of their
  *     kernel inside the library, per (device, stream) — allocation and a device-wide synchronisation on the first call on a stream, a
  *     lock on every call, not capturable into a graph before that first call.  fg_gemm_epilogue_bf16_s / fg_gemm_fp8_bf16_s are the

@@ -128,10 +128,12 @@ def _recording(wd, trace):
         yield
 
 
-def run_case(case, wd=dit_module):
-    """(trace, outputs) of one case on the WanModel of module `wd`."""
-    from fairygen_amd.wan_video import WanVideoPipeline, model_fn_wan_video
-    cfg, sd, loras, inp = _tiny()
+@contextlib.contextmanager
+def built_model(case, wd=dit_module):
+    """The tiny WanModel of module `wd` in the mode of `case` (weights, fp8 Linears, adapters), on the GPU; the module switches of the case
+    hold inside the block."""
+    from fairygen_amd.wan_video import WanVideoPipeline
+    cfg, sd, loras, _ = _tiny()
     with pytest.MonkeyPatch.context() as mp:
         mp.setattr(wd, "GEMM_BACKEND", case["backend"])
         mp.setattr(wd, "FP8_FOLD", case["fold"])
@@ -147,6 +149,14 @@ def run_case(case, wd=dit_module):
             m.enable_fp8_linear()
         for lo, alpha in loras.get(case["lora"], ()):
             pipe.load_lora(m, state_dict=lo, alpha=alpha, hotload=True, hot_backend=case["hot"])
+        yield m
+
+
+def run_case(case, wd=dit_module):
+    """(trace, outputs) of one case on the WanModel of module `wd`."""
+    from fairygen_amd.wan_video import model_fn_wan_video
+    inp = _tiny()[3]
+    with built_model(case, wd) as m:
         # the TI2V layout: two time rows, the 16 tokens of the first latent frame on row 0; else one row
         kw = dict(latents=inp["lat"], timestep=inp["ts"], fuse_vae_embedding_in_latents=case["ti2v"])
         if case["variant"] == "kv_cache":        # the second call finds every block's cross-attention K / V
