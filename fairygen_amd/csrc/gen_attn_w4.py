@@ -14,7 +14,7 @@ repo's own LDS images and operand maps from attn_fwd_kernel<8,1>):
     address) into two 4-deep rings (K(t+4), V(t+3) issued in step t; one counted vmcnt + one barrier per tile);
   * per tile two phases of 32 MFMAs: S^T(t+1) = K(t+1) Q^T beside the exp2 / row sums / bf16 packs of tile t, then
     O^T += V(t)^T P(t)^T beside the row max of tile t+1 and the K(t+2) fragment reads; every other instruction is dealt to
-    an MFMA gap by the list scheduler below (issue-cost budget per gap; at most one transcendental per gap);
+    an MFMA gap by the list scheduler of asm_emit.py (issue-cost budget per gap; at most one transcendental per gap);
   * deferred rescale (threshold 2^6) as an out-of-line rare path; ragged last tile masked by an out-of-line block.
 --prescale 1: Q^T is multiplied by scale*log2(e) once and -max is the C operand of the first MFMA of every score chain, so the
 exponent argument needs no VALU op (64 v_fma fewer per tile and wave).  The product is re-rounded to bf16, which is EXACT only when
@@ -25,6 +25,8 @@ host arranges a power-of-two scale for self-attention by folding the remaining f
 """
 import argparse
 import sys
+
+from asm_emit import Emitter, Item, schedule, vr, ar, sr, write_inc
 
 THR = 6.0          # deferred rescale threshold (log2 units), same as kDeferLog2 of the HIP kernel
 NVW = 8            # V^T fragment window (slots of 4 VGPRs)
@@ -62,68 +64,6 @@ S = {k: v + SBASE for k, v in dict(
     LDQ=28, LDK=29, LDV=30, OROW=31, QROW0=32, PIECE=33, KDST=34, VDST=35, INVSCALE=36, TMP0=37, TMP1=38, TMP2=39,
     TMP64=40, SAVE64=42, NEXT=44, TENDM2=45, ARGS=48).items()}
 NSREG = 60
-
-def vr(lo, n=1):
-    return f"v{lo}" if n == 1 else f"v[{lo}:{lo + n - 1}]"
-def ar(lo, n=1):
-    return f"a{lo}" if n == 1 else f"a[{lo}:{lo + n - 1}]"
-def sr(lo, n=1):
-    return f"s{lo}" if n == 1 else f"s[{lo}:{lo + n - 1}]"
-
-
-class Emitter:
-    def __init__(self):
-        self.lines = []
-        self.uid = 0
-    def e(self, text):
-        self.lines.append(text)
-    def label(self, stem):
-        self.uid += 1
-        return f"L_w4_{stem}_{self.uid}%="
-    def nops(self, n):
-        while n > 0:
-            k = min(n, 8)
-            self.e(f"s_nop {k - 1}")
-            n -= k
-
-
-# ---------------------------------------------------------------- list scheduler over MFMA gaps
-class Item:
-    def __init__(self, name, lines, cost, earliest=0, deadline=10 ** 9, deps=(), lds=0, trans=False):
-        self.name, self.lines, self.cost = name, lines, cost
-        self.earliest, self.deadline, self.deps = earliest, deadline, list(deps)      # deps: (Item, min gap distance)
-        self.lds, self.trans = lds, trans          # lds: number of LDS return values this item issues (lgkmcnt tracking)
-        self.gap = None
-
-def schedule(items, ngaps, budget=None):
-    budget = GAP_BUDGET if budget is None else budget
-    load = [0] * ngaps
-    ntrans = [0] * ngaps
-    out = [[] for _ in range(ngaps)]
-    order = sorted(range(len(items)), key=lambda i: (items[i].deadline, i))
-    for i in order:
-        it = items[i]
-        g0 = it.earliest
-        for dep, dist in it.deps:
-            assert dep.gap is not None, f"{it.name}: dependency {dep.name} not scheduled yet"
-            g0 = max(g0, dep.gap + dist)
-        hi = min(it.deadline, ngaps - 1)
-        assert g0 <= hi, f"{it.name}: window empty (earliest {g0} > deadline {hi})"
-        pick = None
-        for g in range(g0, hi + 1):
-            if load[g] + it.cost <= budget and not (it.trans and ntrans[g] >= 1):
-                pick = g
-                break
-        if pick is None:        # over budget everywhere in the window: least loaded gap (still obeying one transcendental per gap if possible)
-            cands = [g for g in range(g0, hi + 1) if not (it.trans and ntrans[g] >= 1)] or list(range(g0, hi + 1))
-            pick = min(cands, key=lambda g: (load[g], g))
-        it.gap = pick
-        load[pick] += it.cost
-        ntrans[pick] += int(it.trans)
-        out[pick].append((i, it))
-    for g in range(ngaps):
-        out[g].sort(key=lambda p: p[0])      # program order inside a gap = creation order (dependencies are created in order)
-    return [[it for _, it in gap] for gap in out], load
 
 
 # ---------------------------------------------------------------- pieces of the kernel
@@ -421,7 +361,7 @@ def build_step(E, phase, prescale, cold, flagged):
             add(it)
             prev = it
         add(Item(f"pmax{qi}", pair_max_lines(V_MT + qi * 2 + 1, V_T0), 14, earliest=36, deadline=61, deps=[(prev, 1)]))
-    gaps, load = schedule(items, 64)
+    gaps, load = schedule(items, 64, GAP_BUDGET)
 
     # ---- emission, with lgkmcnt tracking (LDS results return in order)
     lds_issued = 0                # LDS results requested so far in this step (the step starts with none outstanding)
@@ -753,14 +693,8 @@ def main():
     if a.report:
         for p, ld in enumerate(loads):
             print(f"step phase {p}: gap loads {ld} (max {max(ld)}, sum {sum(ld)})", file=sys.stderr)
-    out = ["// GENERATED by gen_attn_w4.py --prescale %d --name %s : do not edit" % (a.prescale, a.name),
-           "#define %s_ASM \\" % a.name]
-    for ln in E.lines:
-        out.append('    "%s\\n\\t" \\' % ln)
-    out.append('    ""')
-    regs = [f'"v{i}"' for i in range(256)] + [f'"a{i}"' for i in range(256)] + [f'"s{i}"' for i in range(SBASE, SBASE + NSREG)]
-    out.append(f"#define {a.name}_CLOBBERS " + ", ".join(regs) + ', "vcc", "scc", "memory"')
-    print("\n".join(out))
+    write_inc(E.lines, a.name, "gen_attn_w4.py --prescale %d --name %s" % (a.prescale, a.name),
+              range(256), range(256), range(SBASE, SBASE + NSREG))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generator of the hand-scheduled body of conv3d_cl_w4_kernel (csrc/vae_conv.hip): the implicit-GEMM causal convolution of the
-VAE38 decoder on the 4-wave / 512-register GEMM core of gen_gemm_w4.py (256 couts x 256 pixels x 64 cin per step, LDS-DMA,
+VAE38 decoder on the 4-wave / 512-register GEMM core of gemm_core_w4.py (256 couts x 256 pixels x 64 cin per step, LDS-DMA,
 fragments read one k-step ahead across the barrier).
 
     python3 gen_conv_w4.py [--stamp] > conv_w4_asm.inc
@@ -13,20 +13,20 @@ changes (8 ds_read_b32 every cin_pad/64 steps) and advances the weight offset by
 -> (+ residual) -> bf16, 8-byte channels-last stores, exactly the arithmetic of conv3d_cl_256_kernel.
 """
 import argparse
-import sys
 
-from gen_attn_w4 import Emitter, vr, ar, sr
-import gen_gemm_w4 as G
+from asm_emit import Emitter, vr, ar, sr, write_inc
+import gemm_core_w4 as G
 
 S = G.S
 TAB = 131072                      # LDS byte address of the offset table (after the two 64 KiB stages)
 OUT_TAB = TAB + 27 * 1024
-# extra SGPRs (beyond gen_gemm_w4.S, which ends at SB+39)
-X = {k: v + G.SB + 40 for k, v in dict(RD=0, KPT=4, NTAPS=5, WTAP=6, CSN=7, TAPN=8, WTB=9, KOFFW=10, KOFFX=11, NKTOT=12, HASRES=13).items()}
-NSREG = 40 + 14
+# extra SGPRs (above the core's)
+X = {k: v + G.SB + G.NSREG for k, v in dict(RD=0, KPT=4, NTAPS=5, WTAP=6, CSN=7, TAPN=8, WTB=9, KOFFW=10, KOFFX=11, NKTOT=12, HASRES=13).items()}
+NSREG = G.NSREG + 14
 V_TAB = 100                       # 8 table addresses (this lane's row of each piece), advanced by 1 KiB per tap
 V_CH = 108                        # 2: source chunk * 16 of even / odd pieces
 V_TT = 110                        # 8 temporaries for the table reads
+BIAS = 0                          # epilogue: v0..63 = bias of this lane's 16 (ni, g) column groups, unpacked to fp32
 
 
 def emit_inputs(E):
@@ -103,12 +103,22 @@ def emit_advance(E):
     E.e(f"s_add_u32 {sr(X['KOFFW'])}, {sr(X['WTB'])}, {sr(X['KOFFX'])}")
 
 
+def emit_acc_bias_bf16(E, ni, mi, g, tb):
+    """The 4 accumulators of column group (ni, g) of pixel block mi -> v[tb:tb+3], + bias, packed to two bf16 words in v[tb+4:tb+5]."""
+    for j in range(4):
+        E.e(f"v_accvgpr_read_b32 {vr(tb + j)}, {ar(G.acc(ni, mi, 4 * g + j))}")
+    E.e("s_nop 0")
+    for j in range(4):
+        E.e(f"v_add_f32 {vr(tb + j)}, {vr(tb + j)}, {vr(BIAS + 4 * (ni * 4 + g) + j)}")
+    E.e(f"v_cvt_pk_bf16_f32 {vr(tb + 4)}, {vr(tb)}, {vr(tb + 1)}")
+    E.e(f"v_cvt_pk_bf16_f32 {vr(tb + 5)}, {vr(tb + 2)}, {vr(tb + 3)}")
+
+
 def emit_epilogue(E):
     """acc + bias -> bf16 -> (+ residual) -> bf16 -> out.  Lane (r, hh) holds for (ni, mi, g): pixel row 128*(wave&1) + 32mi + r of
     the tile, couts 128*(wave>>1) + 32ni + 8g + 4hh + 0..3."""
     L, R, HH, COL, T0 = (G.V_T + 24 + i for i in range(5))            # v120..124
     OUTOFF = G.V_T + 20                                               # v116..119: byte offset of this lane's 4 pixels
-    BIAS = 0
     E.nops(32)
     E.e(f"v_mbcnt_lo_u32_b32 {vr(L)}, -1, 0")
     E.e(f"v_mbcnt_hi_u32_b32 {vr(L)}, -1, {vr(L)}")
@@ -150,13 +160,7 @@ def emit_epilogue(E):
             for g in range(4):
                 q = ni * 4 + g
                 tb = 96 + (q % 2) * 10                # two temporary sets v96..115
-                for j in range(4):
-                    E.e(f"v_accvgpr_read_b32 {vr(tb + j)}, {ar(G.acc(ni, mi, 4 * g + j))}")
-                E.e("s_nop 0")
-                for j in range(4):
-                    E.e(f"v_add_f32 {vr(tb + j)}, {vr(tb + j)}, {vr(BIAS + 4 * q + j)}")
-                E.e(f"v_cvt_pk_bf16_f32 {vr(tb + 4)}, {vr(tb)}, {vr(tb + 1)}")           # rbf(acc + bias)
-                E.e(f"v_cvt_pk_bf16_f32 {vr(tb + 5)}, {vr(tb + 2)}, {vr(tb + 3)}")
+                emit_acc_bias_bf16(E, ni, mi, g, tb)  # rbf(acc + bias)
                 for w, src in ((0, tb + 4), (1, tb + 5)):
                     rw = 64 + 2 * q + w
                     E.e(f"v_lshlrev_b32 {vr(tb)}, 16, {vr(src)}")
@@ -177,14 +181,8 @@ def emit_epilogue(E):
     for mi in range(4):
         for ni in range(4):
             for g in range(4):
-                tb = 64 + (n % 6) * 6
-                for j in range(4):
-                    E.e(f"v_accvgpr_read_b32 {vr(tb + j)}, {ar(G.acc(ni, mi, 4 * g + j))}")
-                E.e("s_nop 0")
-                for j in range(4):
-                    E.e(f"v_add_f32 {vr(tb + j)}, {vr(tb + j)}, {vr(BIAS + 4 * (ni * 4 + g) + j)}")
-                E.e(f"v_cvt_pk_bf16_f32 {vr(tb + 4)}, {vr(tb)}, {vr(tb + 1)}")
-                E.e(f"v_cvt_pk_bf16_f32 {vr(tb + 5)}, {vr(tb + 2)}, {vr(tb + 3)}")
+                tb = 64 + (n % 6) * 6                 # rotating temporaries v64..v99 (6 sets of 6)
+                emit_acc_bias_bf16(E, ni, mi, g, tb)
                 E.e(f"buffer_store_dwordx2 {vr(tb + 4, 2)}, {vr(OUTOFF + mi)}, {sr(S['CD'], 4)}, 0 offen offset:{64 * ni + 16 * g}")
                 n += 1
                 if n % 6 == 0:
@@ -217,13 +215,13 @@ def generate(stamp, budget):
     loop, done = E.label("cloop"), E.label("cdone")
     E.e(f"s_mov_b32 {sr(S['T'])}, 1")
     emit_advance(E)
-    load = G.build_iteration(E, 0, True, budget, X["KOFFW"], X["KOFFX"], advance=False)
+    G.build_iteration(E, 0, True, budget, X["KOFFW"], X["KOFFX"])
     E.e(f"s_cmp_ge_u32 {sr(S['T'])}, {sr(X['NKTOT'])}")
     E.e(f"s_cbranch_scc1 {done}")
     E.e(f"{loop}:")
     for stage in (1, 0):
         emit_advance(E)
-        load = G.build_iteration(E, stage, False, budget, X["KOFFW"], X["KOFFX"], advance=False)
+        G.build_iteration(E, stage, False, budget, X["KOFFW"], X["KOFFX"])
         E.e(f"s_add_u32 {sr(S['T'])}, {sr(S['T'])}, 1")
         E.e(f"s_cmp_ge_u32 {sr(S['T'])}, {sr(X['NKTOT'])}")
         if stage == 1:
@@ -256,7 +254,7 @@ def generate(stamp, budget):
         E.e("s_waitcnt vmcnt(0)")
         E.e("s_mov_b64 exec, -1")
         E.e(f"{skip}:")
-    return E, load
+    return E
 
 
 def main():
@@ -266,14 +264,8 @@ def main():
     ap.add_argument("--dma-every-x2", type=int, default=G.DMA_EVERY_X2)
     a = ap.parse_args()
     G.DMA_EVERY_X2 = a.dma_every_x2
-    E, load = generate(a.stamp, a.budget)
-    out = ["// GENERATED by gen_conv_w4.py : do not edit", "#define FG_CONV_W4_ASM \\"]
-    for ln in E.lines:
-        out.append('    "%s\\n\\t" \\' % ln)
-    out.append('    ""')
-    regs = [f'"v{i}"' for i in range(128)] + [f'"a{i}"' for i in range(256)] + [f'"s{i}"' for i in range(G.SB, G.SB + NSREG)]
-    out.append("#define FG_CONV_W4_CLOBBERS " + ", ".join(regs) + ', "vcc", "scc", "memory"')
-    print("\n".join(out))
+    E = generate(a.stamp, a.budget)
+    write_inc(E.lines, "FG_CONV_W4", "gen_conv_w4.py", range(128), range(256), range(G.SB, G.SB + NSREG))
 
 
 if __name__ == "__main__":

@@ -23,9 +23,8 @@ tiles by LDS-DMA into a ring of LDS stages; fragments read one k-step ahead, acr
 locate the k-step's cost; neither is part of the product library.
 """
 import argparse
-import sys
 
-from gen_attn_w4 import Emitter, Item, schedule, vr, ar, sr
+from asm_emit import Emitter, Item, schedule, vr, ar, sr, write_inc
 
 STAGE, XOFF = 65536, 32768
 TAB = 131072                           # tile records (48 B each) above the two stages
@@ -987,17 +986,10 @@ def main():
     Cfg.dma_step, Cfg.dma_first, Cfg.ablate, Cfg.pf_dist, Cfg.pf_coop = a.dma_step, a.dma_first, a.ablate, a.pf_dist, a.pf_coop
     Cfg.serp = a.serp
     E = generate(a.nb, a.stamp, a.budget, a.tail)
-    name = f"FG_GEMM_{'Q' if FP8 else 'P'}{a.nb}{a.tail or ''}"
-    out = [f"// GENERATED by gen_gemm_p.py --nb {a.nb} --tail {a.tail} --dtype {a.dtype} : do not edit", f"#define {name}_ASM \\"]
-    for ln in E.lines:
-        out.append('    "%s\\n\\t" \\' % ln)
-    out.append('    ""')
     # not used by the body and left to the compiler (it needs a VGPR for SGPR spills; the stamp build keeps values across the asm statement)
     free_v = (251,) if FP8 else (251, 252, 253, 254)
-    regs = [f'"v{i}"' for i in range(256) if i not in free_v] + [f'"a{i}"' for i in range(256)] + \
-           [f'"s{i}"' for i in range(SB, SB + NSREG + (4 if a.stamp else 1 if FP8 else 0))]
-    out.append(f"#define {name}_CLOBBERS " + ", ".join(regs) + ', "vcc", "scc", "memory"')
-    print("\n".join(out))
+    write_inc(E.lines, f"FG_GEMM_{'Q' if FP8 else 'P'}{a.nb}{a.tail or ''}", f"gen_gemm_p.py --nb {a.nb} --tail {a.tail} --dtype {a.dtype}",
+              [i for i in range(256) if i not in free_v], range(256), range(SB, SB + NSREG + (4 if a.stamp else 1 if FP8 else 0)))
 
 
 if __name__ == "__main__":
