@@ -320,7 +320,9 @@ int fg_dupup3d_add_bf16(const void* x, const void* main_path, void* out, int T, 
 }
 
 int fg_softmax_rows_f32_bf16(const float* scores, void* probs, int64_t rows, int64_t cols, float scale, fg_stream_t stream) {
-    FG_CHECK_ARG(scores && probs && rows > 0 && cols > 0 && rows < (1ll << 31), "fg_softmax_rows_f32_bf16: bad arguments");
+    // the kernel takes the row maximum of the unscaled scores: that is the maximum of scores * scale only for scale > 0
+    FG_CHECK_ARG(scores && probs && rows > 0 && cols > 0 && rows < (1ll << 31) && scale > 0.f && scale < INFINITY,
+                 "fg_softmax_rows_f32_bf16: bad arguments");
     hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, scores, (bf16*)probs, cols,
                        scale);
     return fg_launch_status("fg_softmax_rows_f32_bf16");

@@ -305,7 +305,8 @@ int fg_dupup3d_add_bf16(const void* x, const void* main_path, void* out,
                         fg_stream_t stream);
 
 /* Row softmax of fp32 scores * scale -> bf16 probabilities (VAE mid AttentionBlock,
- * models/wan_video_vae.py:331-336; its two GEMMs stay on hipBLASLt). */
+ * models/wan_video_vae.py:331-336; its two GEMMs stay on hipBLASLt).  scale > 0 and finite: the row maximum
+ * is taken of the unscaled scores and subtracted before the multiplication. */
 int fg_softmax_rows_f32_bf16(const float* scores, void* probs, int64_t rows, int64_t cols, float scale,
                              fg_stream_t stream);
 

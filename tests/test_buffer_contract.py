@@ -811,7 +811,8 @@ def _argcheck_specs(P, gemm_ws):
                                  "residual + 4": {3: P() + 4}, "x of 3.75 GiB": {5: 60000, 6: 2048, 7: 2048}})
     a = [P(), P(), P(), 1, 2, 2, 8, 8, 1, 2, 0, None]
     add("fg_dupup3d_add_bf16", a, {"Cout % 8": {7: 12}, "ft": {8: 3}, "Cout * factor % Cin": {6: 24}, "x + 8": {0: a[0] + 8}, "out + 8": {2: a[2] + 8}})
-    add("fg_softmax_rows_f32_bf16", [P(), P(), 5, 8, 1.0, None], {"rows = 0": {2: 0}, "cols = 0": {3: 0}, "null scores": {0: None}})
+    add("fg_softmax_rows_f32_bf16", [P(), P(), 5, 8, 1.0, None], {"rows = 0": {2: 0}, "cols = 0": {3: 0}, "null scores": {0: None},
+                                                                    "scale = 0": {4: 0.0}, "scale < 0": {4: -0.25}, "scale = inf": {4: float("inf")}, "scale = nan": {4: float("nan")}})
     add("fg_vae_latent_to_cl_bf16", [P(), P(), P(), P(), 4, 1, 2, 2, None], {"C = 0": {4: 0}, "null z": {0: None}})
     add("fg_vae_unpatchify_bf16", [P(), P(), 2, 2, 2, 4, 1, 0, None], {"t0 + T > F": {6: 3}, "t0 < 0": {6: -1}, "T = 0": {2: 0}})
     add("fg_vae_tile_accumulate_bf16", [P(), P(), P(), 3, 1, 8, 8, 4, 4, 2, 2, 2, 2, 0, None],
@@ -869,6 +870,8 @@ def test_argument_checks():
             assert rc == -1 and name.removesuffix("_s") in msg, f"{name} with {label}: returned {rc} ({msg!r}), expected FG_EINVAL naming the function"
     if have_dev:
         torch.cuda.synchronize()
+    with pytest.raises(hip.HipLibraryError, match="fg_softmax_rows_f32_bf16"):      # as the wrappers see it: the kernel's row maximum is that of the unscaled scores
+        hip._call("fg_softmax_rows_f32_bf16", ctypes.c_void_p(P()), ctypes.c_void_p(P()), 5, 8, -0.25, None)
     R, S_ = ctypes.c_int(), ctypes.c_int()
     assert lib.fg_attn_split_choice(0, 8, 8, 1, 0, ctypes.byref(R), ctypes.byref(S_)) == -1 and b"fg_attn_split_choice" in lib.fg_last_error()
     assert lib.fg_attn_split_choice(1, 8, 8, 1, 0, None, ctypes.byref(S_)) == -1

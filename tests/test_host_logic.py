@@ -242,6 +242,28 @@ def test_tile_grid_matches_oracle():
     assert len(WanVideoVAE38.tile_tasks(30, 52, (30, 52), (15, 26))) == 1
 
 
+def test_t5_bucket_table_matches_oracle():
+    """T5RelativeEmbedding.bucket_table against the oracle's relative_position_bucket up to the encoder's 512 tokens: the exact buckets
+    (distance < 8), the logarithmic ones from distance 16 on, where the fp32 log decides the index (16, 32 and 64 sit on a boundary),
+    and the clamp at distance >= 128; then the (heads, L, L) bias WanTextEncoder.forward gathers with it against position_bias."""
+    import torch.nn.functional as F
+    from fairygen_amd.wan_video_text_encoder import T5RelativeEmbedding
+    from oracle import wan_text
+    emb = T5RelativeEmbedding(32, 64, bidirectional=True)
+    weight = seeded((32, 64), 130)
+    for L in (1, 17, 129, 512):
+        table = emb.bucket_table(L, L)
+        rel = torch.arange(L).unsqueeze(0) - torch.arange(L).unsqueeze(1)
+        assert table.dtype == torch.int64 and torch.equal(table, wan_text.relative_position_bucket(rel, 32)), L
+        assert table.min() >= 0 and table.max() == min(31, {1: 0, 17: 26}.get(L, 31))
+        bias = F.embedding(table, weight).permute(2, 0, 1).contiguous()
+        assert torch.equal(bias.unsqueeze(0), wan_text.position_bias(weight, L, L)), L
+    row = emb.bucket_table(512, 512)[0]      # query 0, keys to its right: 16 + distance below 8, then 16 + 8 + floor(2 log2(distance / 8))
+    assert row[:8].tolist() == [0] + list(range(17, 24)) and (row[16], row[32], row[64]) == (26, 28, 30)
+    assert row[90] == 30 and (row[91:] == 31).all()          # 8 * 2^3.5 = 90.5: the last bucket starts at 91, below max_dist
+    assert torch.equal(emb.bucket_table(512, 512)[:, 0], row - 16 * (row > 0))      # keys to the left: the same buckets without the 16
+
+
 def test_teacache_rows_form_matches_dense():
     """The product keeps the time modulation as 2 distinct rows; its relative-L1 statistic must equal the reference's
     dense (1, N, 6, dim) computation, and the TeaCache state machine must take the same decisions from either form."""
