@@ -30,7 +30,13 @@
  *     fg_vae_tile_accumulate_bf16, fg_vae_tile_finalize_bf16 (tests/test_buffer_contract.py);
  *   - token tensors are "b s (n d)" exactly like the reference's AttentionModule
  *     (models/wan_video_dit.py:113-120); VAE activations are channels-last (T,H,W,C) inside the
- *     decoder, NCTHW only at fg_vae_* boundary kernels.
+ *     decoder, NCTHW only at fg_vae_* boundary kernels;
+ *   - the DiT token kernels compute every row independently of the other rows of the call: a call on the rows [lo, hi) with row-sliced
+ *     operands, the same tables and first_rows' = clamp(first_rows - lo, 0, hi - lo) (0 and rows included) writes the bits the full
+ *     call writes to those rows — what token sharding rests on (tests/test_token_shard_invariance.py).  The exceptions: the k-split
+ *     pieces of the GEMMs (with a workspace the plan depends on M), the split-KV of fg_attn_fwd_bf16 (with a workspace the plan
+ *     depends on Nq), and the 4-wave attention kernel's deferred rescale, decided per wave: once a row maximum moves by more than
+ *     2^6 between KV tiles a query row's bits may depend on the rows that share its wave.
  */
 #ifndef FAIRYGEN_HIP_H
 #define FAIRYGEN_HIP_H
