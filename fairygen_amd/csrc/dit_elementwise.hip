@@ -363,17 +363,54 @@ __global__ __launch_bounds__(256) void act_kernel(const bf16* __restrict__ x, bf
     }
 }
 
+// One element of the CFG combine + Euler step, with the reference's bf16 rounding points (fg_cfg_euler_bf16, fairygen_hip.h).
+__device__ __forceinline__ float cfg_euler_one(float lat, float p, float ng, bool has_nega, float cfg, float dsigma) {
+    const float pred = has_nega ? rbf(ng + rbf(cfg * rbf(p - ng))) : p;
+    return rbf(lat + rbf(pred * dsigma));
+}
+
 __global__ __launch_bounds__(256) void cfg_euler_kernel(const bf16* __restrict__ lat, const bf16* __restrict__ posi,
                                                         const bf16* __restrict__ nega, bf16* __restrict__ out,
                                                         int64_t n, float cfg, float dsigma) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float p = (float)posi[i];
-        float pred = p;
-        if (nega != nullptr) {
-            const float ng = (float)nega[i];
-            pred = rbf(ng + rbf(cfg * rbf(p - ng)));
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = (bf16)cfg_euler_one((float)lat[i], (float)posi[i], nega != nullptr ? (float)nega[i] : 0.0f, nega != nullptr, cfg, dsigma);
+}
+
+// fg_cfg_euler_dev_bf16: dsigma = dsigma_table[*step], both read here; elements of latent frame 0 (offset < first_n inside their
+// frame_stride-long channel block) take `first` instead.  nvec 8-element vectors (0 when a pointer is not 16-byte aligned), then the
+// n - 8 * nvec elements behind them one at a time.  out may alias lat: every element is read before it is written, by one thread.
+__global__ __launch_bounds__(256) void cfg_euler_dev_kernel(const bf16* lat, const bf16* __restrict__ posi, const bf16* __restrict__ nega,
+                                                            bf16* out, int64_t n, int64_t nvec, float cfg,
+                                                            const float* __restrict__ dsigma_table, const int* __restrict__ step,
+                                                            const bf16* __restrict__ first, int64_t first_n, int64_t frame_stride) {
+    const float dsigma = dsigma_table[*step];
+    const bool has_nega = nega != nullptr;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = tid; i < nvec; i += nthreads) {
+        const bf16x8 l = ld8(lat + i * 8), p = ld8(posi + i * 8);
+        const bf16x8 g = has_nega ? ld8(nega + i * 8) : p;
+        float o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = cfg_euler_one((float)l[j], (float)p[j], (float)g[j], has_nega, cfg, dsigma);
+        if (first != nullptr) {
+            int64_t ch = (i * 8) / frame_stride, r = i * 8 - ch * frame_stride;      // channel block and offset inside it of element 0
+            if (r < first_n || r + 7 >= frame_stride) {      // else: all 8 elements lie behind frame 0 of one channel block
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    if (r < first_n) o[j] = (float)first[ch * first_n + r];
+                    if (++r == frame_stride) { r = 0; ++ch; }
+                }
+            }
         }
-        out[i] = (bf16)((float)lat[i] + rbf(pred * dsigma));
+        st8(out + i * 8, o);
+    }
+    for (int64_t i = nvec * 8 + tid; i < n; i += nthreads) {
+        float o = cfg_euler_one((float)lat[i], (float)posi[i], has_nega ? (float)nega[i] : 0.0f, has_nega, cfg, dsigma);
+        if (first != nullptr) {
+            const int64_t ch = i / frame_stride, r = i - ch * frame_stride;
+            if (r < first_n) o = (float)first[ch * first_n + r];
+        }
+        out[i] = (bf16)o;
     }
 }
 
@@ -602,6 +639,24 @@ int fg_cfg_euler_bf16(const void* latents, const void* posi, const void* nega, v
     hipLaunchKernelGGL(cfg_euler_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)latents,
                        (const bf16*)posi, (const bf16*)nega, (bf16*)out, n, cfg_scale, dsigma);
     return fg_launch_status("fg_cfg_euler_bf16");
+}
+
+int fg_cfg_euler_dev_bf16(const void* latents, const void* posi, const void* nega, void* out, int64_t n, float cfg_scale,
+                          const float* dsigma_table, const int* step, const void* first, int64_t first_n, int64_t frame_stride,
+                          fg_stream_t stream) {
+    FG_CHECK_ARG(latents && posi && out && dsigma_table && step && n >= 0, "fg_cfg_euler_dev_bf16: null pointer");
+    FG_CHECK_ARG((((uintptr_t)dsigma_table) & 3) == 0 && (((uintptr_t)step) & 3) == 0, "fg_cfg_euler_dev_bf16: dsigma_table / step must be 4-byte aligned");
+    FG_CHECK_ARG(first == nullptr || (first_n > 0 && frame_stride >= first_n && n % frame_stride == 0),
+                 "fg_cfg_euler_dev_bf16: with `first`, need 0 < first_n <= frame_stride and n a multiple of frame_stride (got n=%lld first_n=%lld "
+                 "frame_stride=%lld)", (long long)n, (long long)first_n, (long long)frame_stride);
+    if (n == 0) return FG_OK;
+    const bool vec = FG_ALIGNED16(latents) && FG_ALIGNED16(posi) && FG_ALIGNED16(out) && (nega == nullptr || FG_ALIGNED16(nega));
+    const int64_t nvec = vec ? n / 8 : 0;
+    const int64_t work = nvec > n - nvec * 8 ? nvec : n - nvec * 8;
+    const unsigned grid = (unsigned)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
+    hipLaunchKernelGGL(cfg_euler_dev_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)latents, (const bf16*)posi,
+                       (const bf16*)nega, (bf16*)out, n, nvec, cfg_scale, dsigma_table, step, (const bf16*)first, first_n, frame_stride);
+    return fg_launch_status("fg_cfg_euler_dev_bf16");
 }
 
 }  // extern "C"

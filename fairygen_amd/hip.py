@@ -13,7 +13,7 @@ import torch
 _LIB_PATH = os.environ.get("FAIRYGEN_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfairygen_hip.so")
 _lib = None
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _i64, _i32, _f32, _vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
@@ -62,7 +62,12 @@ _SIGNATURES = {
 _LOAD_TIME_SIGNATURES = {
     "fg_lora_fuse_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _f32, _vp],
 }
-EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_LOAD_TIME_SIGNATURES) + ["fg_version", "fg_last_error", "fg_conv_packed_bytes", "fg_attn_workspace_bytes", "fg_attn_split_choice",
+# The entry point of the captured denoise step (ABI 8), in a table of its own for the same reason; its stream and argument checks are in
+# tests/test_graph_step.py.
+_GRAPH_SIGNATURES = {
+    "fg_cfg_euler_dev_bf16": [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _i64, _i64, _vp],
+}
+EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_LOAD_TIME_SIGNATURES) + list(_GRAPH_SIGNATURES) + ["fg_version", "fg_last_error", "fg_conv_packed_bytes", "fg_attn_workspace_bytes", "fg_attn_split_choice",
                                                    "fg_conv_tile_choice", "fg_gemm_workspace_bytes", "fg_gemm_debug_grid", "fg_gemm_sched_bytes"])
 
 
@@ -100,7 +105,7 @@ def load():
     lib.fg_gemm_debug_grid.argtypes = [_i32]
     lib.fg_attn_split_choice.restype = ctypes.c_int
     lib.fg_attn_split_choice.argtypes = [_i32, _i64, _i64, _i32, _i64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    for name, argtypes in {**_SIGNATURES, **_LOAD_TIME_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_LOAD_TIME_SIGNATURES, **_GRAPH_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
         fn.argtypes = argtypes
@@ -411,6 +416,13 @@ def _gemm_launch(name, key, *args):
         raise
 
 
+def gemm_workspace_need(m, n, k_bytes):
+    """Bytes of k-split scratch that workspace=True gives an (m, n) GEMM over k_bytes operand bytes per row; 0: it runs without.  A caller
+    with scratch of its own (hip.gemm_state) that wants the bits of workspace=True passes its tensor where this is positive, False elsewhere."""
+    tiles = ((m + 255) // 256) * (n // 256)
+    return max(load().fg_gemm_workspace_bytes(m, n, k_bytes), 0) if (k_bytes // 128 >= 96 or tiles <= 8 * 256) else 0
+
+
 def _gemm_ws(x, m, n, k_bytes, workspace):
     """The k-split scratch, only where fg_gemm_* would use it: at least 96 k-steps of 128 operand bytes, or at most 8 rounds of tiles per CU
     (GemmCall::enqueue in csrc/dit_gemm.hip; 256 CUs assumed here — a spare allocation on other devices, never a missing one).  `workspace`:
@@ -420,8 +432,7 @@ def _gemm_ws(x, m, n, k_bytes, workspace):
                 workspace.numel() * workspace.element_size() < load().fg_gemm_workspace_bytes(m, n, k_bytes):
             raise HipLibraryError("gemm: the workspace tensor must be contiguous, on the operands' device, of fg_gemm_workspace_bytes (hip.gemm_state)")
         return workspace
-    tiles = ((m + 255) // 256) * (n // 256)
-    need = load().fg_gemm_workspace_bytes(m, n, k_bytes) if workspace and (k_bytes // 128 >= 96 or tiles <= 8 * 256) else 0
+    need = gemm_workspace_need(m, n, k_bytes) if workspace else 0
     if need <= 0:
         return None
     key = _gemm_key(x)
@@ -611,18 +622,26 @@ def pow2_softmax_scale(head_dim):
     return p / math.log2(math.e), sl / p
 
 
-def attention(q, k, v, num_heads, out=None, scale=None):
-    """softmax(scale q k^T) v with scale = 1 / sqrt(d) by default, "b s (n d)" in and out (AttentionModule semantics)."""
+def attention(q, k, v, num_heads, out=None, scale=None, workspace=None):
+    """softmax(scale q k^T) v with scale = 1 / sqrt(d) by default, "b s (n d)" in and out (AttentionModule semantics).  workspace: the
+    caller's split-KV scratch (a list that holds one uint8 tensor or nothing yet: grown here on demand, as the scratch kept per (device,
+    stream) is, which a captured graph must not use — its key outlives the graph); same bits either way."""
     ldq, ldk, ldv = _ld_rows(q, "q"), _ld_rows(k, "k"), _ld_rows(v, "v")
     b, nq, hd = q.shape
     nkv = k.shape[1]
     d = hd // num_heads
     out = torch.empty((b, nq, hd), dtype=q.dtype, device=q.device) if out is None else out
     need = load().fg_attn_workspace_bytes(b, nq, nkv, num_heads)
-    key = (q.device, torch.cuda.current_stream(q.device).cuda_stream)      # concurrent streams must not share scratch
-    ws = _attn_workspace.get(key)
-    if need > 0 and (ws is None or ws.numel() < need):
-        ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
+    if workspace is not None:
+        ws = workspace[0] if workspace else None
+        if need > 0 and (ws is None or ws.numel() < need or ws.device != q.device):
+            ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+            workspace[:] = [ws]
+    else:
+        key = (q.device, torch.cuda.current_stream(q.device).cuda_stream)      # concurrent streams must not share scratch
+        ws = _attn_workspace.get(key)
+        if need > 0 and (ws is None or ws.numel() < need):
+            ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
     _call("fg_attn_fwd_bf16", _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(out), b, nq, nkv, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q))
     return out
@@ -634,6 +653,33 @@ def cfg_euler(latents, posi, nega, cfg_scale, dsigma, out=None):
     out = torch.empty_like(latents) if out is None else out
     _call("fg_cfg_euler_bf16", _ptr(latents), _ptr(posi), _ptr(nega), _ptr(out), latents.numel(), float(cfg_scale),
           float(dsigma), _stream(latents))
+    return out
+
+
+def cfg_euler_dev(latents, posi, nega, cfg_scale, dsigma_table, step, first=None, out=None):
+    """cfg_euler for a step that is captured once and replayed (fg_cfg_euler_dev_bf16): dsigma = dsigma_table[step], read on the device —
+    dsigma_table (steps,) fp32, step one int32 element on the device, 0 <= step < steps (the caller's to keep).  first: the (1, C, 1, H, W)
+    conditioning latent of latents (1, C, T, H, W); the result then has it as frame 0, as latents[:, :, 0:1] = first after cfg_euler."""
+    _dev(latents, "latents"), _dev(posi, "posi"), _dev(dsigma_table, "dsigma_table", torch.float32), _dev(step, "step", torch.int32)
+    out = torch.empty_like(latents) if out is None else _dev(out, "out")
+    if nega is not None:
+        _dev(nega, "nega")
+    if any(t.device != latents.device for t in (posi, dsigma_table, step, out) + (() if nega is None else (nega,)) + (() if first is None else (first,))):
+        raise HipLibraryError("cfg_euler_dev: all operands must be on one HIP device")
+    if any(not t.is_contiguous() or t.shape != latents.shape for t in (latents, posi, out) + (() if nega is None else (nega,))):
+        raise HipLibraryError("cfg_euler_dev: latents, posi, nega and out must be contiguous tensors of one shape")
+    if dsigma_table.dim() != 1 or not dsigma_table.is_contiguous() or dsigma_table.numel() < 1 or step.numel() != 1:
+        raise HipLibraryError("cfg_euler_dev: dsigma_table must be a contiguous (steps,) fp32 tensor and step one int32 element")
+    first_n = frame_stride = 0
+    if first is not None:
+        _dev(first, "first")
+        if latents.dim() != 5 or latents.shape[0] != 1 or first.shape != latents.shape[:2] + (1,) + latents.shape[3:] or not first.is_contiguous():
+            raise HipLibraryError(f"cfg_euler_dev: first must be the contiguous (1, C, 1, H, W) frame of latents (1, C, T, H, W), got {tuple(first.shape)} "
+                                  f"for {tuple(latents.shape)}")
+        first_n = latents.shape[3] * latents.shape[4]
+        frame_stride = latents.shape[2] * first_n
+    _call("fg_cfg_euler_dev_bf16", _ptr(latents), _ptr(posi), _ptr(nega), _ptr(out), latents.numel(), float(cfg_scale), _ptr(dsigma_table),
+          _ptr(step), _ptr(first), first_n, frame_stride, _stream(latents))
     return out
 
 

@@ -12,7 +12,9 @@ Extensions (the only additions to the call surface, both optional):
   * ``prompt`` / ``negative_prompt`` may be pre-embedded context tensors ``(1, L, text_dim)`` (bench / tests: no
     tokenizer assets offline); strings go through ``pipe.tokenizer`` + the umT5 encoder like in the reference;
   * ``first_frame_latents=`` supplies the TI2V conditioning latent directly (bench / tests); ``input_image=`` goes
-    through ``pipe.vae.encode`` (VAE38 encoder on the same HIP kernels) exactly like the reference.
+    through ``pipe.vae.encode`` (VAE38 encoder on the same HIP kernels) exactly like the reference;
+  * ``graph=True`` records one denoise step into a HIP graph and replays it for the other steps (``GraphedStep``): the same
+    latents bit for bit, without the per-launch host cost.  Off by default.
 """
 import numpy as np
 import os
@@ -471,7 +473,7 @@ class WanVideoPipeline(torch.nn.Module):
                  sigma_shift=5.0, denoising_strength=1.0, tiled=True, tile_size=(30, 52), tile_stride=(15, 26),
                  sliding_window_size=None, sliding_window_stride=None, tea_cache_l1_thresh=None, tea_cache_model_id="",
                  progress_bar_cmd=tqdm, output_type="quantized",
-                 first_frame_latents=None, **other):
+                 first_frame_latents=None, graph=False, **other):
         for name, value in other.items():
             if name in _INERT_KWARGS:
                 continue
@@ -500,7 +502,7 @@ class WanVideoPipeline(torch.nn.Module):
             inputs_shared, inputs_posi, inputs_nega = self.unit_runner(unit, self, inputs_shared, inputs_posi, inputs_nega)
 
         # Denoise (reference :283-309)
-        latents = self.denoise(inputs_shared, inputs_posi, inputs_nega, cfg_scale, progress_bar_cmd)
+        latents = self.denoise(inputs_shared, inputs_posi, inputs_nega, cfg_scale, progress_bar_cmd, graph=graph)
         inputs_shared["latents"] = latents
         for unit in self.post_units:
             inputs_shared, _, _ = self.unit_runner(unit, self, inputs_shared, inputs_posi, inputs_nega)
@@ -517,7 +519,7 @@ class WanVideoPipeline(torch.nn.Module):
         return self.vae.decode(latents, device=self.device, tiled=tiled, tile_size=tile_size, tile_stride=tile_stride,
                                shard=shard)
 
-    def denoise(self, inputs_shared, inputs_posi, inputs_nega, cfg_scale, progress_bar_cmd=tqdm):
+    def denoise(self, inputs_shared, inputs_posi, inputs_nega, cfg_scale, progress_bar_cmd=tqdm, graph=False):
         """The hot loop: per step forward(+), forward(-), then CFG combine + Euler step fused in one HIP kernel,
         then the first latent frame re-pinned (TI2V).  How the two forwards of a step are issued depends on the layout:
 
@@ -525,7 +527,10 @@ class WanVideoPipeline(torch.nn.Module):
         * cfg_parallel = 2: this rank's half of the world computes ONE branch, one world all-gather exchanges the predictions;
         * token-sharded, cfg_parallel = 1: the two branches — independent until the combine — are advanced in lockstep on
           ONE stream, each yielding right after it has started an exchange: branch B's GEMMs run while A's tensors cross
-          xGMI, A's attention / FFN while B's do.  Collectives keep one program order on every rank."""
+          xGMI, A's attention / FFN while B's do.  Collectives keep one program order on every rank.
+
+        graph=True (single GPU, no TeaCache / windows / cfg_merge): step 0 runs as above, step 1 is recorded into a HIP graph and the
+        graph is replayed for steps 1 .. n-1 (GraphedStep): the same launches on the same values, so the same latents bit for bit."""
         models = {name: getattr(self, name) for name in self.in_iteration_models}
         shared = {k: v for k, v in inputs_shared.items()
                   if k in ("latents", "fuse_vae_embedding_in_latents", "sliding_window_size", "sliding_window_stride")}
@@ -548,7 +553,14 @@ class WanVideoPipeline(torch.nn.Module):
                  and shared.get("sliding_window_size") is None)
         if CROSS_KV_CACHE and self.model_fn is model_fn_wan_video and shared.get("sliding_window_size") is None:
             shared["kv_cache"] = {}      # lives for this loop only: the prompt embeddings and the weights do not change inside it
+        step = None
+        if graph:
+            self._check_graphable(inputs_shared, inputs_posi, inputs_nega, cfg_merge)
+            step = GraphedStep(self, models, shared, inputs_posi, inputs_nega if cfg_scale != 1.0 else None, cfg_scale, first, share)
         for progress_id, timestep in enumerate(progress_bar_cmd(self.scheduler.timesteps)):
+            if step is not None and progress_id > 0:
+                latents = step.run(latents, progress_id)
+                continue
             ts = timestep.unsqueeze(0).to(dtype=self.torch_dtype)       # bf16 rounding of t (:293), kept on the host
             shared["latents"] = latents
             if share:
@@ -580,7 +592,97 @@ class WanVideoPipeline(torch.nn.Module):
             latents = hip.cfg_euler(latents, posi, nega, cfg_scale, float(sigma_next - sigma))
             if first is not None:
                 latents[:, :, 0:1] = first
+        if step is not None:
+            step.close()      # the graph and its pool go; `latents` was allocated outside it
         return latents
+
+    def _check_graphable(self, inputs_shared, inputs_posi, inputs_nega, cfg_merge):
+        """graph=True covers the single-GPU loop of the stock forward; what needs a host decision, a collective or another driver raises."""
+        dit = self.dit
+        if self.model_fn is not model_fn_wan_video or tuple(self.in_iteration_models) != ("dit",):
+            raise NotImplementedError("graph=True records the stock model_fn_wan_video of `dit`; a replaced model_fn is not known to be capturable")
+        if inputs_posi.get("tea_cache") is not None or inputs_nega.get("tea_cache") is not None:
+            raise NotImplementedError("graph=True with TeaCache: whether a step runs its blocks is decided on the host, step by step")
+        if inputs_shared.get("sliding_window_size") is not None or inputs_shared.get("sliding_window_stride") is not None:
+            raise NotImplementedError("graph=True with sliding windows: the window forwards and their blend are not recorded")
+        if (self.sequence_shard is not None and self.sequence_shard.active) or (self.parallel is not None and (
+                self.parallel.cfg_parallel != 1 or (self.parallel.world is not None and self.parallel.world.active))):
+            raise NotImplementedError("graph=True with an active sequence_shard / parallel layout: the collectives of a step are not recorded")
+        if cfg_merge or inputs_shared.get("cfg_merge"):
+            raise NotImplementedError("graph=True with cfg_merge: the merged call is not recorded; the two CFG forwards already share their prefix")
+        if dit.hot_loras and dit.hot_lora_backend == "torch":
+            raise NotImplementedError("graph=True with hot-loaded adapters on the 'torch' backend: use hot_backend='hip' or 'fused'")
+        from .wan_video_dit import AttentionModule
+        if not all(type(a) is AttentionModule for b in dit.blocks for a in (b.self_attn.attn, b.cross_attn.attn)):
+            raise NotImplementedError("graph=True with a plugged AttentionModule: its scratch is not known to be owned by the step")
+
+
+class GraphedStep:
+    """One denoise step — the CFG forwards, the CFG combine + Euler update and the first-frame re-pin — recorded once and replayed.
+
+    Built before the loop, used from step 1 on (step 0 runs eagerly: it fills kv_cache, the rope tables, the weight copies and the
+    per-process launch setup of the kernels).  What changes from step to step is read from device tables inside the graph, indexed by
+    a step counter on the device that the graph itself advances: the time-embedding rows (time_embedding_rows of every timestep, the same ops
+    on the same inputs as the eager forward runs, stacked) and the fp32 table of sigma' - sigma (fg_cfg_euler_dev_bf16).  `latents`
+    is one buffer, updated in place by that kernel; every intermediate lives in the graph's pool.  The own GEMMs run on a scheduler
+    block and k-split scratch that belong to this object (hip.gemm_state), attention on split-KV scratch from here: the state hip
+    keeps per (device, stream) would be keyed by the capture stream, recorded but never executed, and found again by a later eager
+    launch on a stream of the same address.  One stream, no forks.  close() drops the graph and its pool."""
+
+    def __init__(self, pipe, models, shared, inputs_posi, inputs_nega, cfg_scale, first, share):
+        dit, sched = pipe.dit, pipe.scheduler
+        dev = torch.device(shared["latents"].device)
+        self.models, self.shared, self.cfg_scale, self.first, self.share = models, dict(shared), float(cfg_scale), first, share
+        self.branches = [inputs_posi_ctx(inputs_posi)] + ([inputs_posi_ctx(inputs_nega)] if inputs_nega is not None else [])
+        ti2v = dit.seperated_timestep and bool(shared.get("fuse_vae_embedding_in_latents"))
+        rows = [time_embedding_rows(dit, t.unsqueeze(0).to(dtype=pipe.torch_dtype), ti2v, dev, pipe.torch_dtype) for t in sched.timesteps]
+        self.t_rows = torch.stack([r[0] for r in rows]).contiguous()            # (steps, R, dim)
+        self.mod_rows_t = torch.stack([r[1] for r in rows]).contiguous()        # (steps, R, 6, dim)
+        dsigma = []
+        for t in sched.timesteps:
+            sigma, sigma_next = sched.step_scalars(t)
+            dsigma.append(float(sigma_next - sigma))      # the double the eager loop hands to the by-value float of fg_cfg_euler_bf16
+        self.dsigma = torch.tensor(dsigma, dtype=torch.float64).to(torch.float32).to(dev)
+        self.steps = len(dsigma)
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            self.sched, self.workspace = hip.gemm_state(dev)
+        self.attn_workspace = []
+        self.graph = self.latents = None
+
+    def _issue(self):
+        """The launches of one step, on the current stream, from the static buffers."""
+        t_rows = torch.index_select(self.t_rows, 0, self.step)[0]
+        mod_rows_t = torch.index_select(self.mod_rows_t, 0, self.step)[0]
+        prefix = {} if self.share else None
+        preds = [model_fn_wan_video(**self.models, **self.shared, **ctx, latents=self.latents, time_rows=(t_rows, mod_rows_t), cfg_prefix=prefix,
+                                    owned=self).contiguous() for ctx in self.branches]
+        hip.cfg_euler_dev(self.latents, preds[0], preds[1] if len(preds) > 1 else None, self.cfg_scale, self.dsigma, self.step, first=self.first,
+                          out=self.latents)
+        self.step.add_(1)
+
+    def run(self, latents, progress_id):
+        """Step `progress_id` >= 1 on `latents`; returns the buffer that holds the result (the same one from the second call on)."""
+        if self.graph is None:
+            self.latents = latents.contiguous()
+            self.first = None if self.first is None else self.first.contiguous()
+            self.shared.pop("latents", None)
+            self.shared.pop("cfg_prefix", None)
+            self.step.fill_(progress_id)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.device(self.latents.device), torch.cuda.graph(self.graph, stream=torch.cuda.Stream(self.latents.device)):
+                self._issue()
+        if latents.data_ptr() != self.latents.data_ptr():
+            raise RuntimeError("GraphedStep.run: the loop must hand back the latents buffer of the recorded step")
+        if not 0 < progress_id < self.steps:
+            raise IndexError(f"GraphedStep.run: step {progress_id} outside the schedule of {self.steps} steps")
+        self.graph.replay()
+        return self.latents
+
+    def close(self):
+        self.graph = None
+        self.sched = self.workspace = self.t_rows = self.mod_rows_t = None
+        self.attn_workspace = []
 
 
 CFG_SHARE_PREFIX = os.environ.get("FAIRYGEN_CFG_SHARE", "1") != "0"
@@ -677,15 +779,30 @@ def temporal_tiler_steps(window_fn, latents, sliding_window_size, sliding_window
     return value
 
 
+def time_embedding_rows(dit, timestep, ti2v, dev, dt):
+    """The time-embedding prologue of a forward: (t_rows (R, dim), mod_rows_t (R, 6, dim)) — the distinct rows of the reference's per-token
+    time embedding (R = 2 in TI2V mode: t = 0 for the first latent frame, then t; else R = 1) through time_embedding, and their
+    time_projection.  timestep: (1,) already rounded to the pipeline dtype; the sinusoid is fp64 on the host."""
+    tval = timestep.detach().to("cpu")
+    t_pos = torch.cat([torch.zeros(1, dtype=tval.dtype), tval]) if ti2v else tval
+    emb = sinusoidal_embedding_1d(dit.freq_dim, t_pos).to(device=dev, dtype=dt)         # (R, freq_dim)
+    te = dit.time_embedding
+    t_rows = F.linear(hip.activation(F.linear(emb, te[0].weight, te[0].bias), "silu"), te[2].weight, te[2].bias)
+    proj = dit.time_projection[1]
+    return t_rows, F.linear(hip.activation(t_rows.clone(), "silu"), proj.weight, proj.bias).unflatten(1, (6, dit.dim))
+
+
 def model_fn_wan_video_steps(dit, latents=None, timestep=None, context=None, fuse_vae_embedding_in_latents=False,
                              sequence_shard=None, gather_output=True, tea_cache=None, sliding_window_size=None,
-                             sliding_window_stride=None, cfg_prefix=None, kv_cache=None, **kwargs):
+                             sliding_window_stride=None, cfg_prefix=None, kv_cache=None, time_rows=None, owned=None, **kwargs):
     """Generator form of the forward (yields where WanModel.forward_tokens_steps yields; returns the prediction, or
     with gather_output=False the head output of this rank's tokens (1, n_local, out_dim*prod(patch)) and the grid).
 
     timestep: (1,) tensor already rounded to the pipeline dtype (host or device).  The per-token time embedding of
     the reference (:1219-1228) has only two distinct rows (t=0 for the first latent frame, t elsewhere): both rows
-    go through time_embedding / time_projection once and the kernels index them by token position.
+    go through time_embedding / time_projection once and the kernels index them by token position (time_embedding_rows).
+    time_rows: that pair, made ahead by the caller — a recorded step takes it from a device table and passes no host timestep;
+    owned: the recorded step's scheduler block and scratch (WanModel.forward_tokens_steps).
     """
     assert latents.shape[0] == 1, "one clip per call"
     if context.shape[0] > 1:
@@ -723,14 +840,8 @@ def model_fn_wan_video_steps(dit, latents=None, timestep=None, context=None, fus
         raise ValueError('attn_mode="windows" shards the sliding-window mode: pass sliding_window_size= and '
                          'sliding_window_stride= (the exact path shards with "ulysses" or "allgather")')
     dev, dt = latents.device, latents.dtype
-    tval = timestep.detach().to("cpu")
     ti2v = dit.seperated_timestep and fuse_vae_embedding_in_latents
-    t_pos = torch.cat([torch.zeros(1, dtype=tval.dtype), tval]) if ti2v else tval
-    emb = sinusoidal_embedding_1d(dit.freq_dim, t_pos).to(device=dev, dtype=dt)         # (R, freq_dim)
-    te = dit.time_embedding
-    t_rows = F.linear(hip.activation(F.linear(emb, te[0].weight, te[0].bias), "silu"), te[2].weight, te[2].bias)
-    proj = dit.time_projection[1]
-    mod_rows_t = F.linear(hip.activation(t_rows.clone(), "silu"), proj.weight, proj.bias).unflatten(1, (6, dit.dim))
+    t_rows, mod_rows_t = time_rows if time_rows is not None else time_embedding_rows(dit, timestep, ti2v, dev, dt)
 
     # what depends on the prompt embedding and the weights only — the text_embedding MLP here, the cross-attention K / V of every
     # block in forward_tokens_steps — is kept for the denoise loop that owns kv_cache (keyed by the prompt tensor)
@@ -771,7 +882,7 @@ def model_fn_wan_video_steps(dit, latents=None, timestep=None, context=None, fus
     else:
         skip = tea_cache is not None and tea_cache.check(dit, x, TimeModulation(mod_rows_t, first_rows, n))
         out = yield from dit.forward_tokens_steps(x, ctx, mod_rows_t, t_rows, first_rows, (cos, sin), None, None, tea_cache, skip,
-                                                  cfg_prefix if tea_cache is None else None, kv)
+                                                  cfg_prefix if tea_cache is None else None, kv, owned)
         if not gather_output:
             return out, (f, h, w)
     return dit.unpatchify(out, (f, h, w))

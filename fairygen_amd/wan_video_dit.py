@@ -79,18 +79,20 @@ def own_gemm_ok(rows, n, k):
     return GEMM_BACKEND != "lib" and n % 256 == 0 and k % 128 == 0 and ((rows + 255) // 256) * (n // 256) >= GEMM_MIN_TILES
 
 
-def gemm_bias_own(x, weight, bias):
-    return hip.gemm_epilogue(x, weight, bias)
+# **state: nothing (the scheduler block and scratch hip keeps per (device, stream)), or the sched= / workspace= of a caller that owns
+# them (_BlockLinears.state: a captured denoise step).
+def gemm_bias_own(x, weight, bias, **state):
+    return hip.gemm_epilogue(x, weight, bias, **state)
 
 
-def gemm_bias_gelu_own(x, weight, bias):
+def gemm_bias_gelu_own(x, weight, bias, **state):
     """ffn.0 + nn.GELU(approximate='tanh') (models/wan_video_dit.py:208): GELU on the bf16-rounded Linear output in the GEMM's store."""
-    return hip.gemm_epilogue(x, weight, bias, act="gelu_tanh")
+    return hip.gemm_epilogue(x, weight, bias, act="gelu_tanh", **state)
 
 
-def gemm_fp8_own(xq, scale_a, w8, bias):
+def gemm_fp8_own(xq, scale_a, w8, bias, **state):
     """fp8_linear's matmul on the e4m3 form of the persistent kernel: (rows, K) e4m3 x (N, K) e4m3 -> (1, rows, N) bf16."""
-    return hip.gemm_fp8(xq, scale_a, w8, bias, lead_shape=(1, xq.shape[0]))
+    return hip.gemm_fp8(xq, scale_a, w8, bias, lead_shape=(1, xq.shape[0]), **state)
 
 
 def fp8_own_ok(n, k):
@@ -98,9 +100,9 @@ def fp8_own_ok(n, k):
     return FP8_GEMM == "own" and n % 256 == 0 and k % 256 == 0
 
 
-def gemm_residual(x, a, weight, bias, mod=None, gate_idx=None):
+def gemm_residual(x, a, weight, bias, mod=None, gate_idx=None, **state):
     """x (the residual stream, contiguous, updated in place) += gate * Linear(a); gate = vector gate_idx of mod, or 1."""
-    return hip.gemm_epilogue(a, weight, bias, out=x, residual=True, mod=mod, gate_idx=gate_idx)
+    return hip.gemm_epilogue(a, weight, bias, out=x, residual=True, mod=mod, gate_idx=gate_idx, **state)
 
 
 def stack_hot_loras(per_group, shapes, device, dtype):
@@ -140,8 +142,11 @@ class _BlockLinears:
     block Linear has — `plain` and `residual`.  Per Linear, `pack` is WanModel._hot_pack's answer: the stacked operands of
     fg_lora_apply_bf16, False (its adapters take the reference's torch ops, WanModel._hot) or None (no adapter)."""
 
-    def __init__(self, model, mod_rows):
+    def __init__(self, model, mod_rows, owned=None):
         self.model, self.eps = model, model.eps
+        # None, or what a captured step owns in place of the state hip keeps per (device, stream), which must not be recorded into a graph
+        # (its key outlives the capture stream): .sched / .workspace (hip.gemm_state) for the own GEMMs, .attn_workspace for attention
+        self.owned = owned
         self.fp8 = fp8 = model.fp8_dtype
         self.hot = hot = bool(model.hot_loras)
         # adapters on fg_lora_apply_bf16 next to the own GEMMs, bf16 or fp8 (comment on hot_lora_backend, WanVideoPipeline.load_lora)
@@ -193,6 +198,19 @@ class _BlockLinears:
         return x, Act(h)
 
     # ---- the Linears
+    def state(self, rows, n, k_bytes):
+        """The sched= / workspace= of an own GEMM of (rows, n) over k_bytes operand bytes per row: none in an eager forward; the owner's
+        block, and its scratch exactly where workspace=True would have used hip's (same k-split, same bits)."""
+        if self.owned is None:
+            return {}
+        return {"sched": self.owned.sched, "workspace": self.owned.workspace if hip.gemm_workspace_need(rows, n, k_bytes) > 0 else False}
+
+    def attention(self, attn, q, k, v, scale=None):
+        kw = {} if scale is None else {"scale": scale}
+        if self.owned is not None:
+            kw["workspace"] = self.owned.attn_workspace
+        return attn(q, k, v, **kw)
+
     def q8(self, a):
         return a.q8 if a.q8 is not None else hip.fp8_quant_rows(a.bf16, None)
 
@@ -213,15 +231,15 @@ class _BlockLinears:
             own = False      # the reference's ops for this Linear: library GEMM, adapters, GELU
         if gelu and pack is None and not self.gelu_in_quant:      # nothing between the Linear and its GELU: into the GEMM's store where one takes it
             if fp8 is not None and fp8_own_ok(n, k):
-                return hip.gemm_fp8(*a.q8, w8, bias, act="gelu_tanh", lead_shape=(1, a.rows))
+                return hip.gemm_fp8(*a.q8, w8, bias, act="gelu_tanh", lead_shape=(1, a.rows), **self.state(a.rows, n, k))
             if own:
-                return gemm_bias_gelu_own(a.bf16, weight, bias)
+                return gemm_bias_gelu_own(a.bf16, weight, bias, **self.state(a.rows, n, 2 * k))
             if fp8 is None and m.gelu_epilogue:      # GELU(tanh) in the hipBLASLt epilogue: one pass less over the (n, ffn) tensor
                 return gemm_bias_gelu(a.bf16, weight, bias)
         if fp8 is not None:
-            y = m._scaled_linear(*self.q8(a), w8, bias)
+            y = m._scaled_linear(*self.q8(a), w8, bias, **self.state(a.rows, n, k))
         else:
-            y = (gemm_bias_own if own else gemm_bias)(a.bf16, weight, bias)
+            y = gemm_bias_own(a.bf16, weight, bias, **self.state(a.rows, n, 2 * k)) if own else gemm_bias(a.bf16, weight, bias)
         if gelu and pack:      # GELU moves from the GEMM's store into the adapter kernel's
             return hip.lora_apply(a.bf16, pack[0], pack[1], y, mode="gelu_tanh")
         m._hot_apply(names, a.bf16, y, pack)
@@ -242,9 +260,9 @@ class _BlockLinears:
         pack = m._hot_pack((name,)) if self.hip_hot else False if name in m.hot_loras else None
         if self.own and store_ok and pack is not False and (own_gemm_ok(a.shape[1], n, k) if fp8 is None else fp8_own_ok(n, k)):
             if fp8 is None:
-                gemm_residual(x, a, weight, bias, gmod, gate_idx)
+                gemm_residual(x, a, weight, bias, gmod, gate_idx, **self.state(a.shape[1], n, 2 * k))
             else:
-                hip.gemm_fp8(*hip.fp8_quant_rows(a), w8, bias, out=x, residual=True, mod=gmod, gate_idx=gate_idx)
+                hip.gemm_fp8(*hip.fp8_quant_rows(a), w8, bias, out=x, residual=True, mod=gmod, gate_idx=gate_idx, **self.state(a.shape[1], n, k))
             if pack:
                 hip.lora_apply(a, pack[0], pack[1], x, mode="add" if gmod is None else "gate", mod=gmod, gate_idx=gate_idx)
             if affine is not None:
@@ -253,7 +271,7 @@ class _BlockLinears:
         if fp8 is None:
             y = (gemm_bias_tuned if tuned else gemm_bias)(a, weight, bias)
         else:
-            y = m._scaled_linear(*hip.fp8_quant_rows(a, "gelu_tanh" if gelu else None), w8, bias)
+            y = m._scaled_linear(*hip.fp8_quant_rows(a, "gelu_tanh" if gelu else None), w8, bias, **self.state(a.shape[1], n, k))
         if pack is not None:      # only then is nn.GELU's bf16 output needed
             m._hot_apply((name,), hip.activation(a.clone(), "gelu_tanh") if gelu else a, y, pack)
         if affine is not None:
@@ -277,8 +295,10 @@ class AttentionModule(nn.Module):
         super().__init__()
         self.num_heads = num_heads
 
-    def forward(self, q, k, v, scale=None):
-        return hip.attention(q, k, v, self.num_heads, scale=scale)
+    def forward(self, q, k, v, scale=None, workspace=None):
+        if workspace is None:      # the eager call, as it has always been made: hip.attention is a seam that tools wrap with this signature
+            return hip.attention(q, k, v, self.num_heads, scale=scale)
+        return hip.attention(q, k, v, self.num_heads, scale=scale, workspace=workspace)
 
 
 class SelfAttention(nn.Module):
@@ -438,12 +458,12 @@ class WanModel(nn.Module):
         self.invalidate_fused()
         return self
 
-    def _scaled_linear(self, xq, scale_a, w8, bias):
+    def _scaled_linear(self, xq, scale_a, w8, bias, **state):
         """fp8_linear's matmul (:347-354: torch._scaled_mm with row-wise scale_a, unit scale_b, bf16 bias, bf16 out): on this repo's e4m3
         MFMA kernel (fg_gemm_fp8_bf16), or — FAIRYGEN_FP8_GEMM=lib, and for shapes the kernel does not take — the library call itself."""
         n = w8.shape[0]
         if fp8_own_ok(n, xq.shape[1]):
-            return gemm_fp8_own(xq, scale_a, w8, bias)
+            return gemm_fp8_own(xq, scale_a, w8, bias, **state)
         key = (n, xq.device)
         if key not in self._ones:
             self._ones[key] = torch.ones((1, n), dtype=torch.float32, device=xq.device)
@@ -638,7 +658,7 @@ class WanModel(nn.Module):
         if not sharded:
             k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
             q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)
-            a = sa.attn(q, k, v) if scale is None else sa.attn(q, k, v, scale=scale)
+            a = lin.attention(sa.attn, q, k, v, scale)
         elif shard.attn_mode == "ulysses":
             # token shard -> head shard (all N tokens of 24/P heads), attention, head shard -> token shard.  The
             # norm+RoPE kernels and one strided copy write q | k | v straight into the all-to-all send buffer.
@@ -670,10 +690,10 @@ class WanModel(nn.Module):
 
     # ------------------------------------------------------------------ the 30-block token forward
     def forward_tokens(self, x, context, mod_rows_t, t_rows, first_rows, rope, shard=None, shard_total=None, tea_cache=None,
-                       skip_blocks=False, cfg_prefix=None, kv_cache=None):
+                       skip_blocks=False, cfg_prefix=None, kv_cache=None, owned=None):
         """Run forward_tokens_steps to completion (single branch)."""
         gen = self.forward_tokens_steps(x, context, mod_rows_t, t_rows, first_rows, rope, shard, shard_total, tea_cache, skip_blocks,
-                                        cfg_prefix, kv_cache)
+                                        cfg_prefix, kv_cache, owned)
         while True:
             try:
                 next(gen)
@@ -681,7 +701,7 @@ class WanModel(nn.Module):
                 return done.value
 
     def forward_tokens_steps(self, x, context, mod_rows_t, t_rows, first_rows, rope, shard=None, shard_total=None,
-                             tea_cache=None, skip_blocks=False, cfg_prefix=None, kv_cache=None):
+                             tea_cache=None, skip_blocks=False, cfg_prefix=None, kv_cache=None, owned=None):
         """Generator form of the 30-block forward: yields right after each of a block's exchanges has been STARTED
         (token-sharded runs only: the K/V all-gather, or the two Ulysses all-to-alls), so a driver can interleave two
         independent forwards (the CFG branches) and let one branch's compute hide the other's xGMI traffic.
@@ -702,7 +722,8 @@ class WanModel(nn.Module):
         interleave) yields until the copy is there.
         kv_cache: a dict that lives as long as `context` and the weights stay what they are (one denoise loop): block i's
         cross-attention keys (after norm_k) and values depend on nothing else, so they are computed at the first step and read
-        back at the others (reference :172-177 recomputes them every step)."""
+        back at the others (reference :172-177 recomputes them every step).
+        owned: the scheduler block and scratch of a caller that records this forward into a graph (_BlockLinears.owned; same bits)."""
         c, nh, eps = self.dim, self.num_heads, self.eps
         cos, sin = rope
         x = x.contiguous()
@@ -710,7 +731,7 @@ class WanModel(nn.Module):
         if skip_blocks:
             blocks, x = [], tea_cache.update(x)
         fp8 = self.fp8_dtype
-        lin = _BlockLinears(self, mod_rows_t.shape[0])      # the mode decisions of this forward
+        lin = _BlockLinears(self, mod_rows_t.shape[0], owned)      # the mode decisions of this forward
         ctx = Act(context, hip.fp8_quant_rows(context) if fp8 is not None else None)      # the text context is the same for all blocks
         mods = [hip.ModTable((blk.modulation.to(mod_rows_t.dtype) + mod_rows_t).contiguous(), first_rows) for blk in blocks]
         h = lin.modulate(x, mods[0], 0, 1) if blocks else None
@@ -750,7 +771,7 @@ class WanModel(nn.Module):
                 kc, vc = hip.rmsnorm_rope(kvc[..., :c], ca.norm_k.weight, nh, eps), kvc[..., c:]
                 if kv_cache is not None:
                     kv_cache[i] = (kc, vc)
-            ac = ca.attn(qc, kc, vc)
+            ac = lin.attention(ca.attn, qc, kc, vc)
             # x += y ; h = modulate(norm2(x))  (reference :226-227); with both norm outputs wanted, norm3's bf16 row is written over
             x, h = lin.residual(x, ac, f"blocks.{i}.cross_attn.o", ca.o.weight, ca.o.bias, w8[4], mod, None, modulate=(mod, 3, 4),
                                 out=h.bf16 if lin.want_q8 else None)

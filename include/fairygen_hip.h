@@ -14,7 +14,8 @@
  *   - re-entrant across streams and devices, no mutable global state;
  *     every launch of an entry point (its second kernel included: the attention combine, the GEMM's reduce) goes to `stream`, the
  *     first call of a process included, so a call may be recorded by a stream capture (tests/test_stream_contract.py: every entry point
- *     captured on a side stream and replayed, ordered behind a producer on a side stream, and as the first launch of a process);
+ *     captured on a side stream and replayed, ordered behind a producer on a side stream, and as the first launch of a process;
+ *     fg_cfg_euler_dev_bf16, the entry point of ABI 8: tests/test_graph_step.py);
  *   - the documented exception to the two points above: fg_gemm_epilogue_bf16 and fg_gemm_fp8_bf16 keep the scheduler block of their
  *     kernel inside the library, per (device, stream) — allocation and a device-wide synchronisation on the first call on a stream, a
  *     lock on every call, not capturable into a graph before that first call.  fg_gemm_epilogue_bf16_s / fg_gemm_fp8_bf16_s are the
@@ -25,7 +26,7 @@
  *     the fp8 outputs, bias / gate of the GEMMs and bias / residual / out of fg_conv3d_cl_bf16; 4 bytes for scale_a.  The fp32 scale
  *     outputs (out_scale, norm_scale, scale) are written one float at a time and no alignment is checked for them.  The kernels that
  *     access single elements take any element-aligned pointer and check NO alignment (a misaligned pointer is not rejected):
- *     fg_cfg_euler_bf16, fg_softmax_rows_f32_bf16, fg_softmax_bias_bf16, fg_conv_pack_weight_bf16, fg_vae_latent_to_cl_bf16,
+ *     fg_cfg_euler_bf16, fg_cfg_euler_dev_bf16 (vector accesses when every pointer is 16-byte aligned), fg_softmax_rows_f32_bf16, fg_softmax_bias_bf16, fg_conv_pack_weight_bf16, fg_vae_latent_to_cl_bf16,
  *     fg_vae_latent_from_cl_bf16, fg_vae_unpatchify_bf16, fg_vae_patchify_bf16, fg_avgdown3d_add_bf16, fg_video_to_uint8,
  *     fg_vae_tile_accumulate_bf16, fg_vae_tile_finalize_bf16 (tests/test_buffer_contract.py);
  *   - token tensors are "b s (n d)" exactly like the reference's AttentionModule
@@ -53,7 +54,7 @@ extern "C" {
 
 typedef void* fg_stream_t;   /* hipStream_t */
 
-int         fg_version(void);            /* ABI version, currently 7 */
+int         fg_version(void);            /* ABI version, currently 8 */
 const char* fg_last_error(void);         /* thread-local, valid until the next failing call */
 
 /* ------------------------------------------------------------------ DiT token-side kernels (HBM-bound)
@@ -270,6 +271,18 @@ int fg_attn_fwd_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, con
  * out may alias latents. */
 int fg_cfg_euler_bf16(const void* latents, const void* posi, const void* nega, void* out,
                       int64_t n, float cfg_scale, float dsigma, fg_stream_t stream);
+
+/* fg_cfg_euler_bf16 for a step that is recorded once and replayed (a captured graph freezes by-value arguments): the same arithmetic with
+ * the same rounding points, with dsigma = dsigma_table[*step] read by the kernel — dsigma_table: fp32 device memory, one entry per step
+ * of the schedule; step: one int32 in device memory, 0 <= *step < entries (not checked: the host owns both) and advanced by the host's
+ * own stream-ordered work, not here.  first != NULL also re-pins latent frame 0 in the same pass (latents[:, :, 0:1] = first of the
+ * TI2V loop, pipelines/wan_video.py:304-305): with out laid out (C, T, H, W), frame_stride = T*H*W and first_n = H*W, element i of out
+ * with i % frame_stride < first_n takes first[(i / frame_stride) * first_n + i % frame_stride] (first: (C, 1, H, W) contiguous bf16)
+ * instead; n must be a multiple of frame_stride.  nega == NULL as above.  out may alias latents.  8-element vector accesses when
+ * latents, posi, nega and out are all 16-byte aligned, single elements otherwise and for the n % 8 elements at the end. */
+int fg_cfg_euler_dev_bf16(const void* latents, const void* posi, const void* nega, void* out,
+                          int64_t n, float cfg_scale, const float* dsigma_table, const int* step,
+                          const void* first, int64_t first_n, int64_t frame_stride, fg_stream_t stream);
 
 /* ------------------------------------------------------------------------------- VAE decode kernels
  * Channels-last activations: (T,H,W,C) bf16.  */
