@@ -1,0 +1,139 @@
+// e4m3 operands of the opt-in 8-bit Q K^T self-attention (fg_attn_fwd_qk8_bf16), for gfx950.
+//
+// The reference's flash_attention calls sageattn(q, k, v) when that package is present (models/wan_video_dit.py:48-52): 8-bit Q K^T with K
+// mean-smoothing, P V in 16 bits.  The recipe here, per head, q and k (N, 128) bf16 after RMSNorm and RoPE:
+//   kbar = mean over the N keys of k (per channel; the fp64 sum rounded once to fp32),  k' = k - kbar  (q . kbar is constant along a
+//          softmax row, so the softmax is unchanged),
+//   sk   = max(max|k'| / 448, 2^-20)  one scale per head,          k8 = e4m3(k' / sk)   round-to-nearest-even, saturating,
+//   sq[r] = max(max|q[r]| / 448, 2^-20)  one per row and head,     q8 = e4m3(q / sq[r]).
+// Two stream-ordered launches: the column mean and |k'| maximum of every head (one workgroup per head: the maximum needs the finished
+// mean), then the quantise pass over 16 rows x 1 head per workgroup.  HBM-bound: q and k are read once by the second pass and k twice
+// more by the first, 1.5 bytes written per 4 read.
+#include "common.h"
+#include "../../include/fairygen_hip_qk8.h"
+
+namespace {
+
+constexpr int kD = 128;
+constexpr float kE4M3Max = 448.0f;
+constexpr float kScaleFloor = 0x1p-20f;
+
+__device__ __forceinline__ uint32_t cvt2_e4m3(float a, float b) {      // v_cvt_pk_fp8_f32: RNE, OCP e4m3fn on gfx950
+    a = fminf(fmaxf(a, -kE4M3Max), kE4M3Max);
+    b = fminf(fmaxf(b, -kE4M3Max), kE4M3Max);
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xffffu;
+}
+
+// One workgroup of 1024 per head.  Thread t: 16-byte chunk t & 15 of the rows (t >> 4) + 64 i.
+__global__ __launch_bounds__(1024) void attn_k_stats_kernel(const bf16* __restrict__ k, int64_t ldk, float* __restrict__ kbar,
+                                                            float* __restrict__ sk, int64_t N) {
+    __shared__ double red[16][kD];
+    __shared__ float mean_s[kD];
+    __shared__ float amax_s[16];
+    const int h = blockIdx.x, tid = threadIdx.x, c = tid & 15, rl = tid >> 4, wave = tid >> 6, lane = tid & 63;
+    const bf16* kp = k + (int64_t)h * kD + c * 8;
+    double acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.0;
+    for (int64_t row = rl; row < N; row += 64) {
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(kp + row * ldk);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += (double)(float)v[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        acc[j] += __shfl_xor(acc[j], 16, 64);
+        acc[j] += __shfl_xor(acc[j], 32, 64);
+    }
+    if (lane < 16) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[wave][c * 8 + j] = acc[j];
+    }
+    __syncthreads();
+    if (tid < kD) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) s += red[w][tid];
+        const float m = (float)(s / (double)N);
+        mean_s[tid] = m;
+        kbar[h * kD + tid] = m;
+    }
+    __syncthreads();
+    float m[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m[j] = mean_s[c * 8 + j];
+    float amax = 0.f;
+    for (int64_t row = rl; row < N; row += 64) {
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(kp + row * ldk);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)v[j] - m[j]));
+    }
+    amax = wave_max(amax);
+    if (lane == 0) amax_s[wave] = amax;
+    __syncthreads();
+    if (tid == 0) {
+        float a = amax_s[0];
+#pragma unroll
+        for (int w = 1; w < 16; ++w) a = fmaxf(a, amax_s[w]);
+        sk[h] = fmaxf(a / kE4M3Max, kScaleFloor);
+    }
+}
+
+// 16 rows of one head per workgroup of 256: 16 lanes x 8 channels cover a row.
+__global__ __launch_bounds__(256) void attn_quant_qk_kernel(const bf16* __restrict__ q, int64_t ldq, const bf16* __restrict__ k, int64_t ldk,
+                                                            const float* __restrict__ kbar, const float* __restrict__ sk,
+                                                            uint8_t* __restrict__ q8, uint8_t* __restrict__ k8, float* __restrict__ sq,
+                                                            int64_t N, int H) {
+    const int h = blockIdx.y, tid = threadIdx.x, c = tid & 15;
+    const int64_t row = (int64_t)blockIdx.x * 16 + (tid >> 4);
+    const bool valid = row < N;
+    const int64_t rr = valid ? row : N - 1;
+    const bf16x8 qv = *reinterpret_cast<const bf16x8*>(q + rr * ldq + (int64_t)h * kD + c * 8);
+    const bf16x8 kv = *reinterpret_cast<const bf16x8*>(k + rr * ldk + (int64_t)h * kD + c * 8);
+    const f32x4 m0 = *reinterpret_cast<const f32x4*>(kbar + h * kD + c * 8), m1 = *reinterpret_cast<const f32x4*>(kbar + h * kD + c * 8 + 4);
+    const float s_k = sk[h];
+    float qf[8], kf[8], amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        qf[j] = (float)qv[j];
+        kf[j] = (float)kv[j] - (j < 4 ? m0[j & 3] : m1[j & 3]);
+        amax = fmaxf(amax, fabsf(qf[j]));
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    const float s_q = fmaxf(amax / kE4M3Max, kScaleFloor);
+    if (!valid) return;
+    u32x2 wq, wk;
+    wq[0] = cvt2_e4m3(qf[0] / s_q, qf[1] / s_q) | (cvt2_e4m3(qf[2] / s_q, qf[3] / s_q) << 16);
+    wq[1] = cvt2_e4m3(qf[4] / s_q, qf[5] / s_q) | (cvt2_e4m3(qf[6] / s_q, qf[7] / s_q) << 16);
+    wk[0] = cvt2_e4m3(kf[0] / s_k, kf[1] / s_k) | (cvt2_e4m3(kf[2] / s_k, kf[3] / s_k) << 16);
+    wk[1] = cvt2_e4m3(kf[4] / s_k, kf[5] / s_k) | (cvt2_e4m3(kf[6] / s_k, kf[7] / s_k) << 16);
+    const int64_t o = (row * H + h) * kD + c * 8;
+    *reinterpret_cast<u32x2*>(q8 + o) = wq;
+    *reinterpret_cast<u32x2*>(k8 + o) = wk;
+    if (c == 0) sq[row * H + h] = s_q;
+}
+
+}  // namespace
+
+extern "C" int fg_attn_qk8_version(void) { return 1; }
+
+extern "C" int fg_attn_quant_qk_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, void* q8, void* k8, float* sq, float* sk,
+                                     void* scratch, int64_t scratch_bytes, int64_t N, int H, int D, fg_stream_t stream) {
+    FG_CHECK_ARG(q && k && q8 && k8 && sq && sk && scratch, "fg_attn_quant_qk_bf16: null pointer");
+    FG_CHECK_ARG(D == kD, "fg_attn_quant_qk_bf16: only head_dim 128 is supported (got %d)", D);
+    FG_CHECK_ARG(N > 0 && H > 0 && H <= 65535, "fg_attn_quant_qk_bf16: N must be positive, H in 1..65535");
+    const int64_t hd = (int64_t)H * D;
+    FG_CHECK_ARG(ldq >= hd && ldk >= hd && ldq % 8 == 0 && ldk % 8 == 0, "fg_attn_quant_qk_bf16: leading dimensions must be >= H*D and multiples of 8");
+    FG_CHECK_ARG(FG_ALIGNED16(q) && FG_ALIGNED16(k) && FG_ALIGNED16(scratch) && (((uintptr_t)q8 | (uintptr_t)k8) & 7) == 0 &&
+                     (((uintptr_t)sq | (uintptr_t)sk) & 3) == 0,
+                 "fg_attn_quant_qk_bf16: q, k, scratch must be 16-byte aligned (q8, k8: 8; sq, sk: 4)");
+    FG_CHECK_ARG(scratch_bytes >= hd * 4, "fg_attn_quant_qk_bf16: scratch must hold H*D floats (%lld bytes, got %lld)", (long long)(hd * 4),
+                 (long long)scratch_bytes);
+    FG_CHECK_ARG((N + 15) / 16 < (1ll << 31), "fg_attn_quant_qk_bf16: grid too large");
+    hipLaunchKernelGGL(attn_k_stats_kernel, dim3((unsigned)H), dim3(1024), 0, (hipStream_t)stream, (const bf16*)k, ldk, (float*)scratch, sk, N);
+    if (int e = fg_launch_status("fg_attn_quant_qk_bf16 (k statistics)")) return e;
+    hipLaunchKernelGGL(attn_quant_qk_kernel, dim3((unsigned)((N + 15) / 16), (unsigned)H), dim3(256), 0, (hipStream_t)stream, (const bf16*)q, ldq,
+                       (const bf16*)k, ldk, (const float*)scratch, (const float*)sk, (uint8_t*)q8, (uint8_t*)k8, sq, N, H);
+    return fg_launch_status("fg_attn_quant_qk_bf16");
+}

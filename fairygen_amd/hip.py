@@ -67,8 +67,17 @@ _LOAD_TIME_SIGNATURES = {
 _GRAPH_SIGNATURES = {
     "fg_cfg_euler_dev_bf16": [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _i64, _i64, _vp],
 }
+# The entry points of the e4m3 Q K^T self-attention: an extension with a header (include/fairygen_hip_qk8.h) and a version of its own
+# (fg_attn_qk8_version), so the base ABI, its version and EXPORTED_SYMBOLS stay what the older tests pin; their stream, capture and argument
+# checks are in tests/test_attention_qk8.py.
+QK8_ABI_VERSION = 1
+_QK8_SIGNATURES = {
+    "fg_attn_quant_qk_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
+    "fg_attn_fwd_qk8_bf16": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _i64, _vp],
+}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_LOAD_TIME_SIGNATURES) + list(_GRAPH_SIGNATURES) + ["fg_version", "fg_last_error", "fg_conv_packed_bytes", "fg_attn_workspace_bytes", "fg_attn_split_choice",
                                                    "fg_conv_tile_choice", "fg_gemm_workspace_bytes", "fg_gemm_debug_grid", "fg_gemm_sched_bytes"])
+QK8_EXPORTED_SYMBOLS = sorted(list(_QK8_SIGNATURES) + ["fg_attn_qk8_version"])      # what include/fairygen_hip_qk8.h declares
 
 
 class HipLibraryError(RuntimeError):
@@ -105,12 +114,16 @@ def load():
     lib.fg_gemm_debug_grid.argtypes = [_i32]
     lib.fg_attn_split_choice.restype = ctypes.c_int
     lib.fg_attn_split_choice.argtypes = [_i32, _i64, _i64, _i32, _i64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    for name, argtypes in {**_SIGNATURES, **_LOAD_TIME_SIGNATURES, **_GRAPH_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_LOAD_TIME_SIGNATURES, **_GRAPH_SIGNATURES, **_QK8_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
         fn.argtypes = argtypes
     if lib.fg_version() != ABI_VERSION:
         raise HipLibraryError(f"ABI mismatch: library {lib.fg_version()} != binding {ABI_VERSION}")
+    lib.fg_attn_qk8_version.restype = ctypes.c_int
+    lib.fg_attn_qk8_version.argtypes = []
+    if lib.fg_attn_qk8_version() != QK8_ABI_VERSION:
+        raise HipLibraryError(f"ABI mismatch (e4m3 Q K^T extension): library {lib.fg_attn_qk8_version()} != binding {QK8_ABI_VERSION}")
     _lib = lib
     return lib
 
@@ -643,6 +656,57 @@ def attention(q, k, v, num_heads, out=None, scale=None, workspace=None):
         if need > 0 and (ws is None or ws.numel() < need):
             ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
     _call("fg_attn_fwd_bf16", _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(out), b, nq, nkv, num_heads, d,
+          float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q))
+    return out
+
+
+def attention_qk8_scratch(n, num_heads, head_dim, device):
+    """The buffers fg_attn_quant_qk_bf16 fills for (n, num_heads * head_dim) q and k: (q8, k8, sq, sk, kbar scratch)."""
+    hd = num_heads * head_dim
+    return (torch.empty((n, hd), dtype=torch.float8_e4m3fn, device=device), torch.empty((n, hd), dtype=torch.float8_e4m3fn, device=device),
+            torch.empty((n, num_heads), dtype=torch.float32, device=device), torch.empty(num_heads, dtype=torch.float32, device=device),
+            torch.empty(hd, dtype=torch.float32, device=device))
+
+
+def attn_quant_qk(q, k, num_heads, bufs=None):
+    """The e4m3 operands of attention_qk8 from q, k (1, N, H*128) bf16 (column slices with a leading dimension are fine): K mean-smoothed with
+    one scale per head, Q with one scale per row and head (include/fairygen_hip.h).  bufs: attention_qk8_scratch's tuple, else allocated."""
+    ldq, ldk = _ld_rows(q, "q"), _ld_rows(k, "k")
+    b, n, hd = q.shape
+    if b != 1 or k.shape != q.shape:
+        raise HipLibraryError(f"attn_quant_qk: q and k must both be (1, N, H*D), got {tuple(q.shape)} and {tuple(k.shape)}")
+    bufs = attention_qk8_scratch(n, num_heads, hd // num_heads, q.device) if bufs is None else bufs
+    q8, k8, sq, sk, kbar = bufs
+    if q8.shape != (n, hd) or k8.shape != (n, hd) or sq.shape != (n, num_heads) or sk.numel() != num_heads or kbar.numel() < hd:
+        raise HipLibraryError("attn_quant_qk: bufs do not match (N, H*D)")
+    _call("fg_attn_quant_qk_bf16", _ptr(q), ldq, _ptr(k), ldk, _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(kbar), kbar.numel() * 4, n,
+          num_heads, hd // num_heads, _stream(q))
+    return bufs
+
+
+def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs=None):
+    """attention() for self-attention of one batch element with the e4m3 Q K^T product (the reference's sageattn branch,
+    models/wan_video_dit.py:48-52): fg_attn_quant_qk_bf16, then fg_attn_fwd_qk8_bf16.  workspace as in attention(); bufs: the quantised
+    operands' buffers when the caller owns them (a captured step), else allocated per call."""
+    ldv = _ld_rows(v, "v")
+    b, n, hd = q.shape
+    if v.shape != q.shape:
+        raise HipLibraryError(f"attention_qk8: self-attention only, q, k, v of one shape (got v {tuple(v.shape)})")
+    d = hd // num_heads
+    q8, k8, sq, sk, _ = attn_quant_qk(q, k, num_heads, bufs)
+    out = torch.empty((b, n, hd), dtype=q.dtype, device=q.device) if out is None else out
+    need = load().fg_attn_workspace_bytes(1, n, n, num_heads)
+    if workspace is not None:
+        ws = workspace[0] if workspace else None
+        if need > 0 and (ws is None or ws.numel() < need or ws.device != q.device):
+            ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+            workspace[:] = [ws]
+    else:
+        key = (q.device, torch.cuda.current_stream(q.device).cuda_stream)
+        ws = _attn_workspace.get(key)
+        if need > 0 and (ws is None or ws.numel() < need):
+            ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
+    _call("fg_attn_fwd_qk8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v), ldv, _ptr(out), n, n, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q))
     return out
 

@@ -33,6 +33,8 @@ class ModelConfig:
     preparing_dtype: Optional[torch.dtype] = None
     computation_device: Optional[Union[str, torch.device]] = None
     computation_dtype: Optional[torch.dtype] = None
+    # torch.float8_e4m3fn: the DiT's self-attention with the e4m3 Q K^T product (WanModel.enable_qk8_attention); None: bf16
+    attention_dtype: Optional[torch.dtype] = None
     clear_parameters: bool = False
 
     def check_input(self):
@@ -52,7 +54,7 @@ class ModelConfig:
     def vram_config(self):
         return {k: getattr(self, k) for k in (
             "offload_device", "offload_dtype", "onload_device", "onload_dtype",
-            "preparing_device", "preparing_dtype", "computation_device", "computation_dtype")}
+            "preparing_device", "preparing_dtype", "computation_device", "computation_dtype", "attention_dtype")}
 
 
 # --------------------------------------------------------------------------------- state-dict files
@@ -206,6 +208,13 @@ class ModelPool:
                 if not hasattr(model, "enable_fp8_linear"):
                     raise NotImplementedError(f"fp8 computation is only built for the DiT Linears, not for {cfg['model_name']}")
                 model.enable_fp8_linear(comp)
+            attn = vram_config.get("attention_dtype")
+            if attn is not None:
+                if attn != torch.float8_e4m3fn:
+                    raise NotImplementedError(f"attention_dtype={attn}: the 8-bit Q K^T self-attention is built for torch.float8_e4m3fn only")
+                if not hasattr(model, "enable_qk8_attention"):
+                    raise NotImplementedError(f"attention_dtype is only built for the DiT's self-attention, not for {cfg['model_name']}")
+                model.enable_qk8_attention()
             self.model.append(model)
             self.model_name.append(cfg["model_name"])
             self.model_path.append(path)

@@ -648,6 +648,7 @@ class GraphedStep:
         with torch.cuda.device(dev):
             self.sched, self.workspace = hip.gemm_state(dev)
         self.attn_workspace = []
+        self.attn_qk8_bufs = {}      # enable_qk8_attention(): (N, heads, head_dim, device) -> the e4m3 q / k, their scales, the key-mean scratch
         self.graph = self.latents = None
 
     def _issue(self):
@@ -683,6 +684,7 @@ class GraphedStep:
         self.graph = None
         self.sched = self.workspace = self.t_rows = self.mod_rows_t = None
         self.attn_workspace = []
+        self.attn_qk8_bufs = {}
 
 
 CFG_SHARE_PREFIX = os.environ.get("FAIRYGEN_CFG_SHARE", "1") != "0"

@@ -205,10 +205,18 @@ class _BlockLinears:
             return {}
         return {"sched": self.owned.sched, "workspace": self.owned.workspace if hip.gemm_workspace_need(rows, n, k_bytes) > 0 else False}
 
-    def attention(self, attn, q, k, v, scale=None):
+    def attention(self, attn, q, k, v, scale=None, self_attn=False):
         kw = {} if scale is None else {"scale": scale}
         if self.owned is not None:
             kw["workspace"] = self.owned.attn_workspace
+        if self_attn and self.model.qk8_attention and type(attn) is AttentionModule and k.shape[1] > QK8_MIN_KV and q.shape[0] == 1:
+            # the e4m3 Q K^T form (enable_qk8_attention); a captured step owns the quantised operands' buffers as it owns the split-KV scratch
+            if self.owned is not None:
+                key = (q.shape[1], attn.num_heads, q.shape[2] // attn.num_heads, q.device)
+                if key not in self.owned.attn_qk8_bufs:
+                    self.owned.attn_qk8_bufs[key] = hip.attention_qk8_scratch(*key)
+                kw["bufs"] = self.owned.attn_qk8_bufs[key]
+            return hip.attention_qk8(q, k, v, attn.num_heads, **kw)
         return attn(q, k, v, **kw)
 
     def q8(self, a):
@@ -279,6 +287,11 @@ class _BlockLinears:
         if modulate is not None:
             return self.residual_modulate(x, y, mod, gate_idx, *modulate, out=out)
         return self.gate_residual(x, y, mod, gate_idx), None
+
+
+# enable_qk8_attention(): self-attention over more keys than this runs the e4m3 Q K^T kernel; at or below it (where fg_attn_fwd_bf16 itself
+# leaves its 4-wave kernel) the bf16 kernel runs
+QK8_MIN_KV = 1024
 
 
 class RMSNorm(nn.Module):
@@ -423,6 +436,8 @@ class WanModel(nn.Module):
         # fp8 Linear mode of the blocks (None = bf16 GEMMs); see enable_fp8_linear
         self.fp8_dtype = None
         self._ones = {}
+        # e4m3 Q K^T in self-attention (False = bf16); see enable_qk8_attention
+        self.qk8_attention = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -457,6 +472,22 @@ class WanModel(nn.Module):
         self.fp8_dtype = dtype
         self.invalidate_fused()
         return self
+
+    # ------------------------------------------------------------------ e4m3 Q K^T self-attention (models/wan_video_dit.py:48-52)
+    def enable_qk8_attention(self, flag=True):
+        """Run self-attention of every block like the reference's flash_attention does when the sageattention package is present
+        (sageattn(q, k, v)): Q K^T from e4m3 operands — K mean-smoothed with one scale per head, Q with one scale per row and head
+        (fg_attn_quant_qk_bf16) — on fg_attn_fwd_qk8_bf16; softmax and P V as before, v in bf16.  Only the stock AttentionModule of
+        self-attention over more than QK8_MIN_KV keys takes it; cross-attention (512 keys, 1.9 % of the attention FLOPs) stays bf16.
+        q is then rounded as the reference rounds it (attn_scale: no factor folded into its RoPE table).  Composes with
+        enable_fp8_linear, hot adapters and graph=True; token-sharded layouts raise (kbar and sk would need a collective)."""
+        self.qk8_attention = bool(flag)
+        return self
+
+    def check_qk8_layout(self, shard):
+        if self.qk8_attention and shard is not None and shard.active:
+            raise NotImplementedError("enable_qk8_attention() with a token-sharded layout: the key mean and the per-head key scale of the e4m3 "
+                                      "Q K^T form span all ranks' tokens and would need a collective")
 
     def _scaled_linear(self, xq, scale_a, w8, bias, **state):
         """fp8_linear's matmul (:347-354: torch._scaled_mm with row-wise scale_a, unit scale_b, bf16 bias, bf16 out): on this repo's e4m3
@@ -619,6 +650,8 @@ class WanModel(nn.Module):
 
     def attn_scale(self):
         """(scale passed to self-attention or None for 1/sqrt(d), factor folded into q's RoPE table)."""
+        if self.qk8_attention:      # the fold is a device of the bf16 kernel's pre-multiplied form: plain q, 1/sqrt(d) said out loud
+            return float(self.dim // self.num_heads) ** -0.5, 1.0
         if self.fold_attn_scale and self.rope_mode == "f32" and all(type(b.self_attn.attn) is AttentionModule for b in self.blocks):
             return hip.pow2_softmax_scale(self.dim // self.num_heads)
         return None, 1.0
@@ -658,7 +691,7 @@ class WanModel(nn.Module):
         if not sharded:
             k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
             q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)
-            a = lin.attention(sa.attn, q, k, v, scale)
+            a = lin.attention(sa.attn, q, k, v, scale, self_attn=True)
         elif shard.attn_mode == "ulysses":
             # token shard -> head shard (all N tokens of 24/P heads), attention, head shard -> token shard.  The
             # norm+RoPE kernels and one strided copy write q | k | v straight into the all-to-all send buffer.
@@ -731,6 +764,7 @@ class WanModel(nn.Module):
         if skip_blocks:
             blocks, x = [], tea_cache.update(x)
         fp8 = self.fp8_dtype
+        self.check_qk8_layout(shard)
         lin = _BlockLinears(self, mod_rows_t.shape[0], owned)      # the mode decisions of this forward
         ctx = Act(context, hip.fp8_quant_rows(context) if fp8 is not None else None)      # the text context is the same for all blocks
         mods = [hip.ModTable((blk.modulation.to(mod_rows_t.dtype) + mod_rows_t).contiguous(), first_rows) for blk in blocks]

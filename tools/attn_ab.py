@@ -55,6 +55,8 @@ def main():
     ap.add_argument("--check-rows", type=int, default=192)
     ap.add_argument("--stamp", default="", help="comma list of libraries built with gen_attn_w4.py --stamp: decode their cycle stamps")
     ap.add_argument("--spike", action="store_true", help="also check an input that forces the deferred-rescale branch")
+    ap.add_argument("--qk8", action="store_true", help="also time the e4m3 Q K^T form of the package's own library in the same rounds: "
+                    "'qk8' = fg_attn_quant_qk_bf16 + fg_attn_fwd_qk8_bf16, 'qk8-attn' = the attention launch alone (nq == nkv)")
     a = ap.parse_args()
     dev = "cuda"
     g = torch.Generator(dev).manual_seed(0)
@@ -110,6 +112,15 @@ def main():
               f"(loop total {cyc.median().item():.0f})", flush=True)
     out = torch.empty((1, a.nq, c), dtype=torch.bfloat16, device=dev)
     fns = [(n, runner(lib, q, k, v, a.heads, out)) for n, lib in libs]
+    if a.qk8:
+        bufs, ws = hip.attention_qk8_scratch(a.nq, a.heads, 128, q.device), []
+        need = hip.load().fg_attn_workspace_bytes(1, a.nq, a.nq, a.heads)
+        wsb = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+
+        def attn_only():
+            hip._call("fg_attn_fwd_qk8_bf16", *[hip._ptr(t) for t in bufs[:4]], hip._ptr(v), v.stride(1), hip._ptr(out), a.nq, a.nq, a.heads, 128,
+                      128 ** -0.5, hip._ptr(wsb) if need else None, need, hip._stream(out))
+        fns += [("qk8", lambda: hip.attention_qk8(q, k, v, a.heads, out=out, workspace=ws, bufs=bufs)), ("qk8-attn", attn_only)]
     for _, fn in fns:
         for _ in range(2):
             fn()
