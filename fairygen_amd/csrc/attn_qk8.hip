@@ -10,19 +10,10 @@
 // mean), then the quantise pass over 16 rows x 1 head per workgroup.  HBM-bound: q and k are read once by the second pass and k twice
 // more by the first, 1.5 bytes written per 4 read.
 #include "common.h"
+#include "attn_qk8_quant.h"
 #include "../../include/fairygen_hip_qk8.h"
 
 namespace {
-
-constexpr int kD = 128;
-constexpr float kE4M3Max = 448.0f;
-constexpr float kScaleFloor = 0x1p-20f;
-
-__device__ __forceinline__ uint32_t cvt2_e4m3(float a, float b) {      // v_cvt_pk_fp8_f32: RNE, OCP e4m3fn on gfx950
-    a = fminf(fmaxf(a, -kE4M3Max), kE4M3Max);
-    b = fminf(fmaxf(b, -kE4M3Max), kE4M3Max);
-    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xffffu;
-}
 
 // One workgroup of 1024 per head.  Thread t: 16-byte chunk t & 15 of the rows (t >> 4) + 64 i.
 __global__ __launch_bounds__(1024) void attn_k_stats_kernel(const bf16* __restrict__ k, int64_t ldk, float* __restrict__ kbar,
@@ -103,11 +94,7 @@ __global__ __launch_bounds__(256) void attn_quant_qk_kernel(const bf16* __restri
     for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
     const float s_q = fmaxf(amax / kE4M3Max, kScaleFloor);
     if (!valid) return;
-    u32x2 wq, wk;
-    wq[0] = cvt2_e4m3(qf[0] / s_q, qf[1] / s_q) | (cvt2_e4m3(qf[2] / s_q, qf[3] / s_q) << 16);
-    wq[1] = cvt2_e4m3(qf[4] / s_q, qf[5] / s_q) | (cvt2_e4m3(qf[6] / s_q, qf[7] / s_q) << 16);
-    wk[0] = cvt2_e4m3(kf[0] / s_k, kf[1] / s_k) | (cvt2_e4m3(kf[2] / s_k, kf[3] / s_k) << 16);
-    wk[1] = cvt2_e4m3(kf[4] / s_k, kf[5] / s_k) | (cvt2_e4m3(kf[6] / s_k, kf[7] / s_k) << 16);
+    const u32x2 wq = quant8_e4m3(qf, s_q), wk = quant8_e4m3(kf, s_k);
     const int64_t o = (row * H + h) * kD + c * 8;
     *reinterpret_cast<u32x2*>(q8 + o) = wq;
     *reinterpret_cast<u32x2*>(k8 + o) = wk;

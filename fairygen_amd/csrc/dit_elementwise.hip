@@ -4,6 +4,7 @@
 // barrier) and touches every byte exactly once with 16-byte coalesced accesses.
 // Rounding points mirror the reference's bf16 tensor arithmetic op by op (see include/fairygen_hip.h).
 #include "common.h"
+#include "rmsnorm_rope_row.h"      // Row, load_row, ld8, st8 and the RMSNorm+RoPE row arithmetic
 
 // Row kernels (one wave per token row held in registers): second launch-bound = minimum waves per SIMD the register
 // allocation must allow (FG_ROW_MIN_WAVES; measured in tools/microbench.py elementwise).
@@ -13,37 +14,6 @@
 #define FG_ROW_BOUNDS __launch_bounds__(256, FG_ROW_MIN_WAVES)
 
 namespace {
-
-constexpr int kMaxVec = 8;            // 8 lanes-vectors * 64 lanes * 8 elems = 4096 channels max
-constexpr int kRowsPerBlock = 4;      // 4 waves per 256-thread workgroup
-
-struct Row {
-    float v[kMaxVec][8];
-};
-
-__device__ __forceinline__ void load_row(const bf16* p, int C, int lane, Row& r) {
-    const int nvec = C >> 3;
-#pragma unroll
-    for (int i = 0; i < kMaxVec; ++i) {
-        const int vi = lane + i * 64;
-        if (vi < nvec) {
-            bf16x8 t = *reinterpret_cast<const bf16x8*>(p + (int64_t)vi * 8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r.v[i][j] = (float)t[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r.v[i][j] = 0.f;
-        }
-    }
-}
-
-__device__ __forceinline__ bf16x8 ld8(const bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ void st8(bf16* p, const float* f) {
-    bf16x8 t;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t[j] = (bf16)f[j];
-    *reinterpret_cast<bf16x8*>(p) = t;
-}
 
 // mean / rstd of a row held in registers (two-pass, fp32).
 __device__ __forceinline__ void row_moments(const Row& r, int C, int lane, float eps, float& mean, float& rstd) {
@@ -255,13 +225,9 @@ __global__ FG_ROW_BOUNDS void residual_kernel(const bf16* __restrict__ x, const 
     if (MODE == 1) norm_store<1>(r, C, lane, eps, p0, p1, norm_out + row * C);
 }
 
-// RMSNorm over the whole row, * weight, then RoPE on adjacent pairs.  F32TAB false: fp64 cos / sin tables and an fp64
-// rotation, the reference's arithmetic (43 us of fp64 VALU + 16-byte table loads per pair on top of the 77 us the
-// HBM-bound norm takes at N = 27 280).  F32TAB true: `ct` is ONE interleaved fp32 table (rows, head_dim/2, {cos, sin}) =
-// the fp64 table rounded once, rotation as two fp32 FMAs: the bf16 result differs from the fp64 one only where the
-// exact value lies within ~2e-7 relative of a bf16 rounding boundary (measured in tests/test_hip_kernels.py).
-// PLAIN: plain rows (group_cols == C) and head_dim a power of two — the runtime `/ group_cols` and `% head_dim` (an integer division
-// each, per vector: about as many VALU instructions as the norm itself) become a constant and a mask.
+// RMSNorm over the whole row, * weight, then RoPE on adjacent pairs: the arithmetic and its table modes are rope_begin's and
+// rope_vec's (rmsnorm_rope_row.h).  PLAIN: plain rows (group_cols == C) and head_dim a power of two — the runtime `/ group_cols` and `% head_dim`
+// (an integer division each, per vector: about as many VALU instructions as the norm itself) become a constant and a mask.
 template <bool F32TAB, bool PLAIN = false>
 __global__ FG_ROW_BOUNDS void rmsnorm_rope_kernel(const bf16* __restrict__ x, int64_t ldx,
                                                            const bf16* __restrict__ w, const void* __restrict__ ctv,
@@ -271,63 +237,16 @@ __global__ FG_ROW_BOUNDS void rmsnorm_rope_kernel(const bf16* __restrict__ x, in
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const int nvec = C >> 3;
     Row r;
     load_row(x + row * ldx, C, lane, r);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < kMaxVec; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) q += r.v[i][j] * r.v[i][j];
-    const float ms = wave_sum(q) / (float)C;
-    const float rinv = 1.0f / sqrtf(ms + eps);
-    const int half = head_dim >> 1;
-    // fp32 table: a lane's vectors are 512 channels apart, so when head_dim divides 512 (128 here) every vector of the lane
-    // sits at the same channel offset inside its head and needs the SAME four (cos, sin) pairs: loaded once per row
-    const bool hoist = F32TAB && ctv != nullptr && (512 % head_dim) == 0;
-    f32x4 h0 = {0.f, 0.f, 0.f, 0.f}, h1 = {0.f, 0.f, 0.f, 0.f};
-    if (hoist) {
-        const int d_lane = PLAIN ? ((lane * 8) & (head_dim - 1)) : ((lane * 8) % head_dim);
-        const f32x4* tp = reinterpret_cast<const f32x4*>(static_cast<const float*>(ctv) + (row * half + (d_lane >> 1)) * 2);
-        h0 = tp[0];
-        h1 = tp[1];
-    }
+    const int nvec = C >> 3;
+    const RopeRow rr = rope_begin<F32TAB, PLAIN>(r, ctv, row, C, head_dim, eps, lane);
 #pragma unroll
     for (int i = 0; i < kMaxVec; ++i) {
         const int vi = lane + i * 64;
         if (vi < nvec) {
-            const bf16x8 wv = ld8(w + (int64_t)vi * 8);
             float o[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = rbf(rbf(r.v[i][j] * rinv) * (float)wv[j]);
-            if (ctv != nullptr) {
-                const int d0 = PLAIN ? ((vi * 8) & (head_dim - 1)) : ((vi * 8) % head_dim);          // channel within the head, multiple of 8
-                if (F32TAB) {
-                    f32x4 t0 = h0, t1 = h1;                  // (c0,s0,c1,s1) (c2,s2,c3,s3)
-                    if (!hoist) {
-                        const f32x4* tp = reinterpret_cast<const f32x4*>(static_cast<const float*>(ctv) + (row * half + (d0 >> 1)) * 2);
-                        t0 = tp[0];
-                        t1 = tp[1];
-                    }
-                    const float cs[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float a = o[2 * j], b = o[2 * j + 1], c = cs[2 * j], sn = cs[2 * j + 1];
-                        o[2 * j] = rbf(__builtin_fmaf(a, c, -(b * sn)));
-                        o[2 * j + 1] = rbf(__builtin_fmaf(a, sn, b * c));
-                    }
-                } else {
-                    const double* cp = static_cast<const double*>(ctv) + row * half + (d0 >> 1);
-                    const double* sp = static_cast<const double*>(stv) + row * half + (d0 >> 1);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const double a = (double)o[2 * j], b = (double)o[2 * j + 1];
-                        const double c = cp[j], sn = sp[j];
-                        o[2 * j] = (float)(bf16)(a * c - b * sn);
-                        o[2 * j + 1] = (float)(bf16)(a * sn + b * c);
-                    }
-                }
-            }
+            rope_vec<F32TAB, PLAIN>(rr, r.v[i], ld8(w + (int64_t)vi * 8), ctv, stv, row, head_dim, vi, o);
             // column block g = col / group_cols goes to its own (rows, out_ld) plane (group_cols == C: plain rows)
             const int col = vi * 8, g = PLAIN ? 0 : col / group_cols;
             st8(out + g * out_group_stride + row * out_ld + (col - g * group_cols), o);

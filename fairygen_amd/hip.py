@@ -78,6 +78,15 @@ _QK8_SIGNATURES = {
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_LOAD_TIME_SIGNATURES) + list(_GRAPH_SIGNATURES) + ["fg_version", "fg_last_error", "fg_conv_packed_bytes", "fg_attn_workspace_bytes", "fg_attn_split_choice",
                                                    "fg_conv_tile_choice", "fg_gemm_workspace_bytes", "fg_gemm_debug_grid", "fg_gemm_sched_bytes"])
 QK8_EXPORTED_SYMBOLS = sorted(list(_QK8_SIGNATURES) + ["fg_attn_qk8_version"])      # what include/fairygen_hip_qk8.h declares
+# The e4m3 operands written by the RMSNorm+RoPE pass: a second extension (include/fairygen_hip_qk8_fused.h, fg_attn_qk8_fused_version), so
+# the two tables above stay what their tests pin; its checks are in tests/test_attention_qk8_fused.py.
+QK8F_ABI_VERSION = 1
+_QK8F_SIGNATURES = {
+    "fg_rmsnorm_rope_q8_bf16": [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _f32, _vp],
+    "fg_rmsnorm_rope_kstats_bf16": [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp],
+    "fg_attn_quant_k_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
+}
+QK8F_EXPORTED_SYMBOLS = sorted(list(_QK8F_SIGNATURES) + ["fg_attn_qk8_fused_version", "fg_attn_qk8_fused_scratch_bytes"])
 
 
 class HipLibraryError(RuntimeError):
@@ -114,7 +123,7 @@ def load():
     lib.fg_gemm_debug_grid.argtypes = [_i32]
     lib.fg_attn_split_choice.restype = ctypes.c_int
     lib.fg_attn_split_choice.argtypes = [_i32, _i64, _i64, _i32, _i64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    for name, argtypes in {**_SIGNATURES, **_LOAD_TIME_SIGNATURES, **_GRAPH_SIGNATURES, **_QK8_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_LOAD_TIME_SIGNATURES, **_GRAPH_SIGNATURES, **_QK8_SIGNATURES, **_QK8F_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
         fn.argtypes = argtypes
@@ -124,6 +133,12 @@ def load():
     lib.fg_attn_qk8_version.argtypes = []
     if lib.fg_attn_qk8_version() != QK8_ABI_VERSION:
         raise HipLibraryError(f"ABI mismatch (e4m3 Q K^T extension): library {lib.fg_attn_qk8_version()} != binding {QK8_ABI_VERSION}")
+    lib.fg_attn_qk8_fused_version.restype = ctypes.c_int
+    lib.fg_attn_qk8_fused_version.argtypes = []
+    if lib.fg_attn_qk8_fused_version() != QK8F_ABI_VERSION:
+        raise HipLibraryError(f"ABI mismatch (fused e4m3 producers): library {lib.fg_attn_qk8_fused_version()} != binding {QK8F_ABI_VERSION}")
+    lib.fg_attn_qk8_fused_scratch_bytes.restype = ctypes.c_int64
+    lib.fg_attn_qk8_fused_scratch_bytes.argtypes = [_i64, _i32]
     _lib = lib
     return lib
 
@@ -684,31 +699,116 @@ def attn_quant_qk(q, k, num_heads, bufs=None):
     return bufs
 
 
+def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, workspace=None):
+    """fg_attn_fwd_qk8_bf16 on operands that are quantised already (attn_quant_qk's, or the fused producers'): q8, k8 (N, H*128) e4m3, sq
+    (N, H), sk (H), v (1, N, H*128) bf16.  workspace as in attention()."""
+    ldv = _ld_rows(v, "v")
+    b, n, hd = v.shape
+    d = hd // num_heads
+    if b != 1 or q8.shape != (n, hd) or k8.shape != (n, hd) or sq.shape != (n, num_heads) or sk.numel() != num_heads:
+        raise HipLibraryError(f"attention_qk8_pre: self-attention of one batch element, operands for v {tuple(v.shape)}")
+    out = torch.empty((b, n, hd), dtype=v.dtype, device=v.device) if out is None else out
+    need = load().fg_attn_workspace_bytes(1, n, n, num_heads)
+    if workspace is not None:
+        ws = workspace[0] if workspace else None
+        if need > 0 and (ws is None or ws.numel() < need or ws.device != v.device):
+            ws = torch.empty(need, dtype=torch.uint8, device=v.device)
+            workspace[:] = [ws]
+    else:
+        key = (v.device, torch.cuda.current_stream(v.device).cuda_stream)
+        ws = _attn_workspace.get(key)
+        if need > 0 and (ws is None or ws.numel() < need):
+            ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=v.device)
+    _call("fg_attn_fwd_qk8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v), ldv, _ptr(out), n, n, num_heads, d,
+          float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
+    return out
+
+
 def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs=None):
     """attention() for self-attention of one batch element with the e4m3 Q K^T product (the reference's sageattn branch,
     models/wan_video_dit.py:48-52): fg_attn_quant_qk_bf16, then fg_attn_fwd_qk8_bf16.  workspace as in attention(); bufs: the quantised
     operands' buffers when the caller owns them (a captured step), else allocated per call."""
-    ldv = _ld_rows(v, "v")
-    b, n, hd = q.shape
     if v.shape != q.shape:
         raise HipLibraryError(f"attention_qk8: self-attention only, q, k, v of one shape (got v {tuple(v.shape)})")
-    d = hd // num_heads
     q8, k8, sq, sk, _ = attn_quant_qk(q, k, num_heads, bufs)
-    out = torch.empty((b, n, hd), dtype=q.dtype, device=q.device) if out is None else out
-    need = load().fg_attn_workspace_bytes(1, n, n, num_heads)
-    if workspace is not None:
-        ws = workspace[0] if workspace else None
-        if need > 0 and (ws is None or ws.numel() < need or ws.device != q.device):
-            ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-            workspace[:] = [ws]
-    else:
-        key = (q.device, torch.cuda.current_stream(q.device).cuda_stream)
-        ws = _attn_workspace.get(key)
-        if need > 0 and (ws is None or ws.numel() < need):
-            ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
-    _call("fg_attn_fwd_qk8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v), ldv, _ptr(out), n, n, num_heads, d,
-          float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q))
-    return out
+    return attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=out, scale=scale, workspace=workspace)
+
+
+def attention_qk8_fused_scratch(n, num_heads, head_dim, device):
+    """The buffers of the fused producers for (n, num_heads * head_dim) q and k: attention_qk8_scratch's five (q8, k8, sq, sk, the key
+    mean) and the key-statistics partials rmsnorm_rope_kstats hands to attn_quant_k."""
+    need = load().fg_attn_qk8_fused_scratch_bytes(n, num_heads * head_dim)
+    if need < 0:
+        raise HipLibraryError(f"attention_qk8_fused_scratch: {load().fg_last_error().decode()}")
+    return attention_qk8_scratch(n, num_heads, head_dim, device) + (torch.empty(need, dtype=torch.uint8, device=device),)
+
+
+def _rope_tables(who, cos, sin, rows, half):
+    """fg_rmsnorm_rope_bf16's table modes: (cos, sin, table_f32) checked against the row count."""
+    if cos is not None and sin is None:
+        _dev(cos, "rope table", torch.float32)
+        if cos.shape != (rows, half, 2) or not cos.is_contiguous():
+            raise HipLibraryError(f"{who}: the fp32 rope table must be ({rows}, {half}, 2) contiguous")
+        return 1
+    if cos is not None:
+        _dev(cos, "cos", torch.float64), _dev(sin, "sin", torch.float64)
+        if cos.shape != (rows, half) or not cos.is_contiguous() or sin.shape != (rows, half) or not sin.is_contiguous():
+            raise HipLibraryError(f"{who}: rope tables must be ({rows}, {half}) contiguous")
+    return 0
+
+
+def rmsnorm_rope_q8(x, weight, num_heads, eps, cos=None, sin=None, q8=None, sq=None):
+    """rmsnorm_rope (head_dim 128, plain rows) whose row leaves as the e4m3 q operand of attention_qk8_pre: (q8 (rows, C), sq (rows,
+    num_heads)), the bytes attn_quant_qk makes of rmsnorm_rope's output, which is never written."""
+    _dev(x, "x"), _dev(weight, "weight")
+    c = x.shape[-1]
+    x2 = _rows2d(x, "rmsnorm_rope_q8")
+    rows, ld = x2.shape[0], x2.stride(0)
+    f32tab = _rope_tables("rmsnorm_rope_q8", cos, sin, rows, c // num_heads // 2)
+    q8 = torch.empty((rows, c), dtype=torch.float8_e4m3fn, device=x.device) if q8 is None else q8
+    sq = torch.empty((rows, num_heads), dtype=torch.float32, device=x.device) if sq is None else sq
+    if q8.shape != (rows, c) or sq.shape != (rows, num_heads) or not q8.is_contiguous() or not sq.is_contiguous():
+        raise HipLibraryError("rmsnorm_rope_q8: q8 must be (rows, C), sq (rows, num_heads), contiguous")
+    _call("fg_rmsnorm_rope_q8_bf16", _ptr(x2), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(q8), _ptr(sq), rows, c, num_heads, eps,
+          _stream(x))
+    return q8, sq
+
+
+def rmsnorm_rope_kstats(x, weight, num_heads, eps, cos=None, sin=None, out=None, partials=None):
+    """rmsnorm_rope (head_dim 128, plain rows) that also leaves the key statistics of the rows it wrote: (k, partials), k rmsnorm_rope's
+    bytes, partials (attention_qk8_fused_scratch's last buffer, else allocated) for attn_quant_k."""
+    _dev(x, "x"), _dev(weight, "weight")
+    c = x.shape[-1]
+    x2 = _rows2d(x, "rmsnorm_rope_kstats")
+    rows, ld = x2.shape[0], x2.stride(0)
+    f32tab = _rope_tables("rmsnorm_rope_kstats", cos, sin, rows, c // num_heads // 2)
+    out = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    if out.shape != x.shape or not out.is_contiguous():
+        raise HipLibraryError("rmsnorm_rope_kstats: out must be contiguous and of x's shape")
+    if partials is None:
+        need = load().fg_attn_qk8_fused_scratch_bytes(rows, c)
+        if need < 0:
+            raise HipLibraryError(f"rmsnorm_rope_kstats: {load().fg_last_error().decode()}")
+        partials = torch.empty(need, dtype=torch.uint8, device=x.device)
+    _call("fg_rmsnorm_rope_kstats_bf16", _ptr(x2), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(out), _ptr(partials),
+          partials.numel(), rows, c, num_heads, eps, _stream(x))
+    return out, partials
+
+
+def attn_quant_k(k, partials, num_heads, k8=None, sk=None, kbar=None):
+    """The e4m3 k operand from rmsnorm_rope_kstats's pair: k (1, N, H*128) bf16 -> (k8 (N, H*128), sk (H), the key mean (H*128))."""
+    ldk = _ld_rows(k, "k")
+    b, n, hd = k.shape
+    if b != 1:
+        raise HipLibraryError(f"attn_quant_k: k must be (1, N, H*D), got {tuple(k.shape)}")
+    k8 = torch.empty((n, hd), dtype=torch.float8_e4m3fn, device=k.device) if k8 is None else k8
+    sk = torch.empty(num_heads, dtype=torch.float32, device=k.device) if sk is None else sk
+    kbar = torch.empty(hd, dtype=torch.float32, device=k.device) if kbar is None else kbar
+    if k8.shape != (n, hd) or sk.numel() != num_heads or kbar.numel() < hd:
+        raise HipLibraryError("attn_quant_k: k8, sk, kbar do not match (N, H*D)")
+    _call("fg_attn_quant_k_bf16", _ptr(k), ldk, _ptr(partials), partials.numel(), _ptr(k8), _ptr(sk), _ptr(kbar), n, num_heads,
+          hd // num_heads, _stream(k))
+    return k8, sk, kbar
 
 
 def cfg_euler(latents, posi, nega, cfg_scale, dsigma, out=None):

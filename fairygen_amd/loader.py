@@ -215,6 +215,7 @@ class ModelPool:
                 if not hasattr(model, "enable_qk8_attention"):
                     raise NotImplementedError(f"attention_dtype is only built for the DiT's self-attention, not for {cfg['model_name']}")
                 model.enable_qk8_attention()
+                model.qk8_fused_producer = True      # the operands from the RMSNorm+RoPE pass itself: the same bits, k read once
             self.model.append(model)
             self.model_name.append(cfg["model_name"])
             self.model_path.append(path)

@@ -648,7 +648,7 @@ class GraphedStep:
         with torch.cuda.device(dev):
             self.sched, self.workspace = hip.gemm_state(dev)
         self.attn_workspace = []
-        self.attn_qk8_bufs = {}      # enable_qk8_attention(): (N, heads, head_dim, device) -> the e4m3 q / k, their scales, the key-mean scratch
+        self.attn_qk8_bufs = {}      # enable_qk8_attention(): (N, heads, head_dim, device) -> the e4m3 q / k, their scales, the key-mean scratch (+ "fused": and the key-statistics partials)
         self.graph = self.latents = None
 
     def _issue(self):

@@ -209,15 +209,37 @@ class _BlockLinears:
         kw = {} if scale is None else {"scale": scale}
         if self.owned is not None:
             kw["workspace"] = self.owned.attn_workspace
-        if self_attn and self.model.qk8_attention and type(attn) is AttentionModule and k.shape[1] > QK8_MIN_KV and q.shape[0] == 1:
+        if self_attn and takes_qk8_attention(self.model, attn, k.shape[1], q.shape[0]):
             # the e4m3 Q K^T form (enable_qk8_attention); a captured step owns the quantised operands' buffers as it owns the split-KV scratch
             if self.owned is not None:
-                key = (q.shape[1], attn.num_heads, q.shape[2] // attn.num_heads, q.device)
-                if key not in self.owned.attn_qk8_bufs:
-                    self.owned.attn_qk8_bufs[key] = hip.attention_qk8_scratch(*key)
-                kw["bufs"] = self.owned.attn_qk8_bufs[key]
+                kw["bufs"] = self.qk8_bufs(q.shape[1], attn.num_heads, q.shape[2] // attn.num_heads, q.device, False)
             return hip.attention_qk8(q, k, v, attn.num_heads, **kw)
         return attn(q, k, v, **kw)
+
+    def qk8_bufs(self, n, num_heads, head_dim, device, fused):
+        """The e4m3 operands' buffers: a captured step's own, made once per shape (fused: with the key-statistics partials); None in an
+        eager forward, where the binding allocates."""
+        if self.owned is None:
+            return None
+        key = (n, num_heads, head_dim, device) + (("fused",) if fused else ())
+        if key not in self.owned.attn_qk8_bufs:
+            self.owned.attn_qk8_bufs[key] = (hip.attention_qk8_fused_scratch if fused else hip.attention_qk8_scratch)(*key[:4])
+        return self.owned.attn_qk8_bufs[key]
+
+    def attention_qk8_fused(self, sa, qkv, rq, rk, scale):
+        """Self-attention in the e4m3 Q K^T form straight from the q | k | v buffer (enable_qk8_attention(fused_producer=True)): the
+        RMSNorm+RoPE pass of q writes the e4m3 rows and their scales and no bf16 q, that of k writes bf16 k and the key statistics, one
+        pass converts k.  The bytes of rmsnorm_rope x 2 -> attention_qk8 (tests/test_attention_qk8_fused.py)."""
+        nh, eps = sa.attn.num_heads, self.model.eps
+        c = qkv.shape[-1] // 3
+        n = qkv.shape[1]
+        bufs = self.qk8_bufs(n, nh, c // nh, qkv.device, True) or hip.attention_qk8_fused_scratch(n, nh, c // nh, qkv.device)
+        q8, k8, sq, sk, kbar, parts = bufs
+        k, _ = hip.rmsnorm_rope_kstats(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, partials=parts)
+        hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, q8=q8, sq=sq)
+        hip.attn_quant_k(k, parts, nh, k8, sk, kbar)
+        kw = {} if self.owned is None else {"workspace": self.owned.attn_workspace}
+        return hip.attention_qk8_pre(q8, k8, sq, sk, qkv[..., 2 * c:], nh, scale=scale, **kw)
 
     def q8(self, a):
         return a.q8 if a.q8 is not None else hip.fp8_quant_rows(a.bf16, None)
@@ -292,6 +314,12 @@ class _BlockLinears:
 # enable_qk8_attention(): self-attention over more keys than this runs the e4m3 Q K^T kernel; at or below it (where fg_attn_fwd_bf16 itself
 # leaves its 4-wave kernel) the bf16 kernel runs
 QK8_MIN_KV = 1024
+
+
+def takes_qk8_attention(model, attn, n_kv, batch):
+    """Whether a block's self-attention over n_kv keys runs the e4m3 Q K^T kernel: the mode on, the stock AttentionModule, more than
+    QK8_MIN_KV keys, one batch element.  The one predicate of _BlockLinears.attention and of the fused producers in front of it."""
+    return bool(model.qk8_attention) and type(attn) is AttentionModule and n_kv > QK8_MIN_KV and batch == 1
 
 
 class RMSNorm(nn.Module):
@@ -438,6 +466,8 @@ class WanModel(nn.Module):
         self._ones = {}
         # e4m3 Q K^T in self-attention (False = bf16); see enable_qk8_attention
         self.qk8_attention = False
+        # ... with its operands written by the RMSNorm+RoPE pass (True) or by the quantise pass behind it (False); the same bits
+        self.qk8_fused_producer = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -474,14 +504,19 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ e4m3 Q K^T self-attention (models/wan_video_dit.py:48-52)
-    def enable_qk8_attention(self, flag=True):
+    def enable_qk8_attention(self, flag=True, fused_producer=False):
         """Run self-attention of every block like the reference's flash_attention does when the sageattention package is present
         (sageattn(q, k, v)): Q K^T from e4m3 operands — K mean-smoothed with one scale per head, Q with one scale per row and head
         (fg_attn_quant_qk_bf16) — on fg_attn_fwd_qk8_bf16; softmax and P V as before, v in bf16.  Only the stock AttentionModule of
         self-attention over more than QK8_MIN_KV keys takes it; cross-attention (512 keys, 1.9 % of the attention FLOPs) stays bf16.
         q is then rounded as the reference rounds it (attn_scale: no factor folded into its RoPE table).  Composes with
-        enable_fp8_linear, hot adapters and graph=True; token-sharded layouts raise (kbar and sk would need a collective)."""
+        enable_fp8_linear, hot adapters and graph=True; token-sharded layouts raise (kbar and sk would need a collective).
+        fused_producer: the RMSNorm+RoPE pass itself writes the operands (fg_rmsnorm_rope_q8_bf16, fg_rmsnorm_rope_kstats_bf16,
+        fg_attn_quant_k_bf16: q never exists as bf16, k is read once, not three times); False keeps the quantise pass behind the two
+        norms, the form a plain call has always had and tests/test_attention_qk8.py pins to the oracle by its launches.  Both write the
+        same bytes, so the forward does not depend on it; ModelConfig(attention_dtype=...) asks for the fused producers."""
         self.qk8_attention = bool(flag)
+        self.qk8_fused_producer = bool(flag) and bool(fused_producer)
         return self
 
     def check_qk8_layout(self, shard):
@@ -688,7 +723,9 @@ class WanModel(nn.Module):
         # rope tables per operand: fp64 (cos, sin) for both, or the fp32 interleaved tables of k and q (rope_tables)
         rk, rq = ((cos, None), (sin, None)) if cos.dtype == torch.float32 else ((cos, sin), (cos, sin))
         scale = self.attn_scale()[0]      # None (1/sqrt(d)), or the power-of-two form that goes with the pre-multiplied q table
-        if not sharded:
+        if not sharded and self.qk8_fused_producer and takes_qk8_attention(self, sa.attn, qkv.shape[1], qkv.shape[0]):
+            a = lin.attention_qk8_fused(sa, qkv, rq, rk, scale)
+        elif not sharded:
             k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
             q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)
             a = lin.attention(sa.attn, q, k, v, scale, self_attn=True)

@@ -57,6 +57,11 @@ def main():
     ap.add_argument("--spike", action="store_true", help="also check an input that forces the deferred-rescale branch")
     ap.add_argument("--qk8", action="store_true", help="also time the e4m3 Q K^T form of the package's own library in the same rounds: "
                     "'qk8' = fg_attn_quant_qk_bf16 + fg_attn_fwd_qk8_bf16, 'qk8-attn' = the attention launch alone (nq == nkv)")
+    ap.add_argument("--qk8-fused", action="store_true", help="time the whole chain from the q | k | v buffer of the qkv GEMM to the attention "
+                    "output (nq == nkv), in three forms: 'chain-bf16' = RMSNorm+RoPE of q and k + fg_attn_fwd_bf16 (the default path, its "
+                    "pre-multiplied form), 'chain-qk8' = the same two norms + fg_attn_quant_qk_bf16 + fg_attn_fwd_qk8_bf16, 'chain-qk8-fused' = "
+                    "the fused producers (fg_rmsnorm_rope_kstats_bf16, fg_rmsnorm_rope_q8_bf16, fg_attn_quant_k_bf16) + fg_attn_fwd_qk8_bf16; "
+                    "and the producers of each form alone ('prod-*').  The two e4m3 chains are first checked to be the same bytes")
     a = ap.parse_args()
     dev = "cuda"
     g = torch.Generator(dev).manual_seed(0)
@@ -121,6 +126,51 @@ def main():
             hip._call("fg_attn_fwd_qk8_bf16", *[hip._ptr(t) for t in bufs[:4]], hip._ptr(v), v.stride(1), hip._ptr(out), a.nq, a.nq, a.heads, 128,
                       128 ** -0.5, hip._ptr(wsb) if need else None, need, hip._stream(out))
         fns += [("qk8", lambda: hip.attention_qk8(q, k, v, a.heads, out=out, workspace=ws, bufs=bufs)), ("qk8-attn", attn_only)]
+    if a.qk8_fused:
+        n, nh = a.nq, a.heads
+        qkv = rnd(1, n, 3 * c)
+        wq, wk = (1 + 0.1 * rnd(c).float()).to(torch.bfloat16), (1 + 0.1 * rnd(c).float()).to(torch.bfloat16)
+        ang = torch.rand((n, 64), generator=g, device=dev, dtype=torch.float64) * 6.283185307179586
+        tab = torch.stack([ang.cos(), ang.sin()], -1).float().contiguous()
+        xq, xk, xv = qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:]
+        q16, k16 = torch.empty((1, n, c), dtype=torch.bfloat16, device=dev), torch.empty((1, n, c), dtype=torch.bfloat16, device=dev)
+        b2, bf = hip.attention_qk8_scratch(n, nh, 128, dev), hip.attention_qk8_fused_scratch(n, nh, 128, dev)
+        ws16, ws2, wsf = [], [], []
+        scale16 = hip.pow2_softmax_scale(128)[0]
+        o16, o2, of = (torch.empty((1, n, c), dtype=torch.bfloat16, device=dev) for _ in range(3))
+
+        def norms():
+            hip.rmsnorm_rope(xk, wk, nh, 1e-6, tab, None, out=k16)
+            hip.rmsnorm_rope(xq, wq, nh, 1e-6, tab, None, out=q16)
+
+        def prod_two():
+            norms()
+            hip.attn_quant_qk(q16, k16, nh, b2)
+
+        def prod_fused():
+            hip.rmsnorm_rope_kstats(xk, wk, nh, 1e-6, tab, None, out=k16, partials=bf[5])
+            hip.rmsnorm_rope_q8(xq, wq, nh, 1e-6, tab, None, q8=bf[0], sq=bf[2])
+            hip.attn_quant_k(k16, bf[5], nh, bf[1], bf[3], bf[4])
+
+        def chain_bf16():
+            norms()
+            hip.attention(q16, k16, xv, nh, out=o16, scale=scale16, workspace=ws16)
+
+        def chain_two():
+            prod_two()
+            hip.attention_qk8_pre(*b2[:4], xv, nh, out=o2, workspace=ws2)
+
+        def chain_fused():
+            prod_fused()
+            hip.attention_qk8_pre(*bf[:4], xv, nh, out=of, workspace=wsf)
+        chain_two(), chain_fused()
+        torch.cuda.synchronize()
+        same = all(torch.equal(x.view(torch.uint8) if x.dtype == torch.float8_e4m3fn else x, y.view(torch.uint8) if y.dtype == torch.float8_e4m3fn else y)
+                   for x, y in zip(b2, bf[:5])) and torch.equal(o2, of)
+        print(f"check[chain] the fused producers and the two-step path: q8, k8, sq, sk, key mean and the attention output "
+              f"{'are the same bytes  OK' if same else 'DIFFER  FAIL'}", flush=True)
+        fns += [("chain-bf16", chain_bf16), ("chain-qk8", chain_two), ("chain-qk8-fused", chain_fused), ("prod-bf16", norms), ("prod-qk8", prod_two),
+                ("prod-qk8-fused", prod_fused)]
     for _, fn in fns:
         for _ in range(2):
             fn()
@@ -139,6 +189,11 @@ def main():
     for n, ts in times.items():
         ts = sorted(ts)
         med, mn = ts[len(ts) // 2], ts[0]
+        if n.startswith(("chain-", "prod-")):      # several launches: the mean and the spread of the repeated runs, no FLOP rate
+            mean = sum(ts) / len(ts)
+            sd = (sum((t - mean) ** 2 for t in ts) / max(len(ts) - 1, 1)) ** 0.5
+            print(f"{n}: N={a.nq} H={a.heads}: mean {mean:.4f} ms, sd {sd:.4f}, median {med:.4f}, min {mn:.4f}, max {ts[-1]:.4f} ({len(ts)} runs)", flush=True)
+            continue
         print(f"{n}: nq={a.nq} nkv={a.nkv} H={a.heads}: median {med:.3f} ms = {fl / med / 1e9:.1f} TFLOP/s, min {mn:.3f} ms = {fl / mn / 1e9:.1f}", flush=True)
 
 

@@ -75,6 +75,8 @@ def main():
     ap.add_argument("--sizes", default="config1,config2,shard8,headline")
     ap.add_argument("--dtypes", default="bf16,fp8")
     ap.add_argument("--modes", default="eager,graph,eager,graph", help="legs per size and dtype, in this order (repeats show the run-to-run spread)")
+    ap.add_argument("--attn", default="bf16", help="self-attention forms, legs in this order: bf16, qk8 (enable_qk8_attention(), the two-step "
+                    "producers), qk8-fused (fused_producer=True); the latents of a qk8-fused leg are compared with the first qk8 leg's")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--layers", type=int, default=0, help="debug: fewer DiT layers")
@@ -89,13 +91,17 @@ def main():
         pipe.dit.enable_fp8_linear(torch.float8_e4m3fn if dtype == "fp8" else None)
         for size in a.sizes.split(","):
             first = {}
-            for mode in a.modes.split(","):
+            for attn, mode in ((at, md) for at in a.attn.split(",") for md in a.modes.split(",")):
+                pipe.dit.enable_qk8_attention(attn != "bf16", fused_producer=attn == "qk8-fused")
                 ms, out = leg(pipe, SIZES[size], mode, a.warmup, a.steps, dev)
-                ref = first.setdefault("out", out)
+                ref = first.setdefault(attn.split("-")[0], out)
                 n = SIZES[size][2] * (SIZES[size][3] // 2) * (SIZES[size][4] // 2)
-                rows.append({"size": size, "tokens": n, "dtype": dtype, "mode": mode, "ms_per_step": round(ms, 3), "same_bits": bool(torch.equal(out, ref))})
-                print(f"{size:9s} N={n:6d} {dtype:4s} {mode:6s}: {ms:9.3f} ms/step over {a.steps} steps; latents equal the first leg's: {rows[-1]['same_bits']}", flush=True)
+                rows.append({"size": size, "tokens": n, "dtype": dtype, "attn": attn, "mode": mode, "ms_per_step": round(ms, 3),
+                             "same_bits": bool(torch.equal(out, ref))})
+                print(f"{size:9s} N={n:6d} {dtype:4s} {attn:9s} {mode:6s}: {ms:9.3f} ms/step over {a.steps} steps; latents equal the first "
+                      f"{attn.split('-')[0]} leg's: {rows[-1]['same_bits']}", flush=True)
                 del out
+            pipe.dit.enable_qk8_attention(False)
             del first, ref
             gc.collect()
             torch.cuda.empty_cache()
