@@ -700,15 +700,16 @@ def attn_quant_qk(q, k, num_heads, bufs=None):
 
 
 def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, workspace=None):
-    """fg_attn_fwd_qk8_bf16 on operands that are quantised already (attn_quant_qk's, or the fused producers'): q8, k8 (N, H*128) e4m3, sq
-    (N, H), sk (H), v (1, N, H*128) bf16.  workspace as in attention()."""
+    """fg_attn_fwd_qk8_bf16 on operands that are quantised already (attn_quant_qk's, or the fused producers'): q8 (Nq, H*128), k8 (Nkv,
+    H*128) e4m3, sq (Nq, H), sk (H), v (1, Nkv, H*128) bf16 -> (1, Nq, H*128); the model calls it with Nq = Nkv.  workspace as in
+    attention()."""
     ldv = _ld_rows(v, "v")
-    b, n, hd = v.shape
-    d = hd // num_heads
-    if b != 1 or q8.shape != (n, hd) or k8.shape != (n, hd) or sq.shape != (n, num_heads) or sk.numel() != num_heads:
-        raise HipLibraryError(f"attention_qk8_pre: self-attention of one batch element, operands for v {tuple(v.shape)}")
-    out = torch.empty((b, n, hd), dtype=v.dtype, device=v.device) if out is None else out
-    need = load().fg_attn_workspace_bytes(1, n, n, num_heads)
+    b, nkv, hd = v.shape
+    nq, d = q8.shape[0], hd // num_heads
+    if b != 1 or q8.shape != (nq, hd) or k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads:
+        raise HipLibraryError(f"attention_qk8_pre: one batch element, k8 and sk for v {tuple(v.shape)}, sq for q8 {tuple(q8.shape)}")
+    out = torch.empty((b, nq, hd), dtype=v.dtype, device=v.device) if out is None else out
+    need = load().fg_attn_workspace_bytes(1, nq, nkv, num_heads)
     if workspace is not None:
         ws = workspace[0] if workspace else None
         if need > 0 and (ws is None or ws.numel() < need or ws.device != v.device):
@@ -719,7 +720,7 @@ def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, worksp
         ws = _attn_workspace.get(key)
         if need > 0 and (ws is None or ws.numel() < need):
             ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=v.device)
-    _call("fg_attn_fwd_qk8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v), ldv, _ptr(out), n, n, num_heads, d,
+    _call("fg_attn_fwd_qk8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v), ldv, _ptr(out), nq, nkv, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
     return out
 

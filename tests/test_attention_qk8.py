@@ -35,16 +35,17 @@ HEADS = 2
 
 # ------------------------------------------------------------------------------------------------------------------ the recipe
 def quant_emu(q, k, heads):
-    """q, k (N, heads*128) bf16 -> q8, k8 (N, heads*128) e4m3, sq (N, heads), sk (heads) fp32, and the fp32 quotients that were rounded."""
-    n = q.shape[0]
-    qf, kf = q.float().view(n, heads, 128), k.float().view(n, heads, 128)
+    """q (Nq, heads*128), k (N, heads*128) bf16 -> q8, k8 e4m3 of those shapes, sq (Nq, heads), sk (heads) fp32, and the fp32 quotients
+    that were rounded.  (Nq = N in self-attention; the two halves of the recipe do not meet before the attention kernel.)"""
+    nq, n = q.shape[0], k.shape[0]
+    qf, kf = q.float().view(nq, heads, 128), k.float().view(n, heads, 128)
     kbar = (k.double().view(n, heads, 128).sum(0) / n).float()               # the fp64 sum, divided by N, rounded once to fp32
     kp = kf - kbar
     sk = torch.clamp(kp.abs().amax((0, 2)) / 448.0, min=FLOOR_SCALE)
     sq = torch.clamp(qf.abs().amax(2) / 448.0, min=FLOOR_SCALE)
     xq, xk = qf / sq.unsqueeze(-1), kp / sk.view(1, heads, 1)
     q8, k8 = xq.clamp(-448, 448).to(F8), xk.clamp(-448, 448).to(F8)           # round-to-nearest-even, saturating
-    return q8.view(n, -1), k8.view(n, -1), sq, sk, xq.view(n, -1), xk.view(n, -1)
+    return q8.view(nq, -1), k8.view(n, -1), sq, sk, xq.view(nq, -1), xk.view(n, -1)
 
 
 def attn_emu(q8, k8, sq, sk, v, heads, scale=128 ** -0.5):
@@ -72,11 +73,11 @@ def near_tie(x):
 
 
 @functools.lru_cache(maxsize=None)
-def quant_case(n):
+def quant_case(n, heads=HEADS):
     """q | k | v column slices of one (n, 3*H*128) row-major buffer, as the qkv GEMM leaves them."""
-    qkv = seeded((n, 3 * HEADS * 128), 900 + n)
-    c = HEADS * 128
-    return qkv, quant_emu(qkv[:, :c], qkv[:, c:2 * c], HEADS)
+    qkv = seeded((n, 3 * heads * 128), 900 + n + 1000 * (heads - HEADS))
+    c = heads * 128
+    return qkv, quant_emu(qkv[:, :c], qkv[:, c:2 * c], heads)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. the recipe's properties
@@ -123,20 +124,27 @@ def test_recipe_tie_exemption_is_rare():
     at all are more (0, 107 and 1 509: bf16 inputs over a bf16 maximum / 448 hit ties exactly, e.g. every 16th element of a row whose
     maximum is 448 * 2^k / 128); IEEE division rounds those the same way everywhere, and the GPU run reports how many bytes differed."""
     for n in QUANT_N:
-        qkv, (q8, k8, sq, sk, xq, xk) = quant_case(n)
-        c = HEADS * 128
-        qf = qkv[:, :c].float().view(n, HEADS, 128)
-        kp = qkv[:, c:2 * c].float().view(n, HEADS, 128) - (qkv[:, c:2 * c].double().view(n, HEADS, 128).sum(0) / n).float()
-        alt_q = (qf * (1.0 / sq).unsqueeze(-1)).clamp(-448, 448).to(F8).view(n, -1)
-        alt_k = (kp * (1.0 / sk).view(1, HEADS, 1)).clamp(-448, 448).to(F8).view(n, -1)
-        used = 0
-        for alt, w8, x in ((alt_q, q8, xq), (alt_k, k8, xk)):
-            diff = alt.view(torch.uint8) != w8.view(torch.uint8)
-            assert not (diff & ~near_tie(x)).any(), "a one-ulp change of the quotient moved a byte away from a tie"
-            used += diff.sum().item()
-        near = near_tie(xq).sum().item() + near_tie(xk).sum().item()
-        print(f"N = {n}: {used} of {xq.numel() + xk.numel()} bytes differ under x * (1 / s); {near} quotients within one ulp of an e4m3 tie")
-        assert used < 1e-3 * (xq.numel() + xk.numel())
+        check_tie_exemption(n)
+
+
+def check_tie_exemption(n, heads=HEADS):
+    """test_recipe_tie_exemption_is_rare for one quant_case; returns the bytes that differ."""
+    qkv, (q8, k8, sq, sk, xq, xk) = quant_case(n, heads)
+    c = heads * 128
+    qf = qkv[:, :c].float().view(n, heads, 128)
+    kp = qkv[:, c:2 * c].float().view(n, heads, 128) - (qkv[:, c:2 * c].double().view(n, heads, 128).sum(0) / n).float()
+    alt_q = (qf * (1.0 / sq).unsqueeze(-1)).clamp(-448, 448).to(F8).view(n, -1)
+    alt_k = (kp * (1.0 / sk).view(1, heads, 1)).clamp(-448, 448).to(F8).view(n, -1)
+    used = 0
+    for alt, w8, x in ((alt_q, q8, xq), (alt_k, k8, xk)):
+        diff = alt.view(torch.uint8) != w8.view(torch.uint8)
+        assert not (diff & ~near_tie(x)).any(), "a one-ulp change of the quotient moved a byte away from a tie"
+        used += diff.sum().item()
+    near = near_tie(xq).sum().item() + near_tie(xk).sum().item()
+    print(f"N = {n}, {heads} heads: {used} of {xq.numel() + xk.numel()} bytes differ under x * (1 / s); {near} quotients within one ulp of "
+          f"an e4m3 tie")
+    assert used < 1e-3 * (xq.numel() + xk.numel())
+    return used
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2. the ABI and the switch
@@ -269,16 +277,21 @@ def guards_intact(full):
 @gpu
 @pytest.mark.parametrize("n", QUANT_N)
 def test_quant_qk_against_the_recipe(hip, n):
-    qkv, (q8, k8, sq, sk, xq, xk) = quant_case(n)
-    c = HEADS * 128
+    check_quant_qk(hip, n)
+
+
+def check_quant_qk(hip, n, heads=HEADS):
+    """fg_attn_quant_qk_bf16 on quant_case(n, heads) against quant_emu; returns the bytes that used the tie exemption."""
+    qkv, (q8, k8, sq, sk, xq, xk) = quant_case(n, heads)
+    c = heads * 128
     # the rows live between guard rows of NaN, and the v slice (inside the leading dimension, never read) is NaN too
     src = torch.full((n + 2, 3 * c), float("nan"), dtype=BF16)
     src[1:-1, :2 * c] = qkv[:, :2 * c]
     d = src.cuda()[1:-1].unsqueeze(0)
-    fulls, bufs = zip(*[guarded(s, t) for s, t in (((n, c), F8), ((n, c), F8), ((n, HEADS), torch.float32), ((1, HEADS), torch.float32),
+    fulls, bufs = zip(*[guarded(s, t) for s, t in (((n, c), F8), ((n, c), F8), ((n, heads), torch.float32), ((1, heads), torch.float32),
                                                    ((1, c), torch.float32))])
-    bufs = (bufs[0], bufs[1], bufs[2], bufs[3].view(HEADS), bufs[4].view(c))
-    got = hip.attn_quant_qk(d[..., :c], d[..., c:2 * c], HEADS, bufs)
+    bufs = (bufs[0], bufs[1], bufs[2], bufs[3].view(heads), bufs[4].view(c))
+    got = hip.attn_quant_qk(d[..., :c], d[..., c:2 * c], heads, bufs)
     torch.cuda.synchronize()
     assert all(guards_intact(f) for f in fulls), "a guard row of an output was written"
     g_q8, g_k8, g_sq, g_sk = (t.cpu() for t in got[:4])
@@ -290,12 +303,13 @@ def test_quant_qk_against_the_recipe(hip, n):
     for name, g8, w8, x in (("q8", g_q8, q8, xq), ("k8", g_k8, k8, xk)):
         diff = g8.view(torch.uint8) != w8.view(torch.uint8)
         tie = near_tie(x)
-        print(f"N = {n}, {name}: {diff.sum().item()} bytes differ, {tie.sum().item()} quotients within one ulp of a tie")
+        print(f"N = {n}, {heads} heads, {name}: {diff.sum().item()} bytes differ, {tie.sum().item()} quotients within one ulp of a tie")
         assert not (diff & ~tie).any(), f"{name}: {(diff & ~tie).sum().item()} bytes differ away from a rounding tie"
         # a byte that differs at a tie is the other neighbour, not anything else
         assert (g8.float()[diff] - w8.float()[diff]).abs().le((x[diff].abs() / 8).clamp(min=2.0 ** -9)).all()
         exempt += diff.sum().item()
     assert exempt <= 1e-3 * 2 * n * c, f"{exempt} of {2 * n * c} elements used the tie exemption"
+    return exempt
 
 
 # ------------------------------------------------------------------------------------------------------------------ 4. fg_attn_fwd_qk8_bf16
@@ -361,42 +375,60 @@ def test_attention_qk8_against_the_recipe(hip, n, data, split):
 
 
 @functools.lru_cache(maxsize=None)
-def exact_case(n):
+def exact_case(n, nkv=None, heads=HEADS, must=()):
     """Small-integer q and k and one-hot v for which every step of the recipe and of the kernel is exact.  Keys are +-4 in every channel
     and come in (k, -k) pairs (an odd n ends on a zero row), so every column sums to 0: kbar = 0, sk = 4 / 448 and k8 = +-448 exactly.
     Query r is 16 x sign(key sel(r)): sq = 16 / 448, q8 = +-448.  Every score is 448^2 x an integer below 2^15 — exact in fp32 in any
     summation order.  The logit of the selected key is 16 * 4 * 128 / sqrt(128) = 724 nats; the gap to every other key is asserted
-    to be > 150 nats, so every other probability underflows to 0 in fp32 and out[r] = v[sel(r)] = e_(sel(r) mod 128), exactly."""
-    g = torch.Generator("cpu").manual_seed(8000 + n)
-    half = n // 2
-    signs = (torch.randint(0, 2, (half, HEADS, 128), generator=g) * 2 - 1).float()
-    k = torch.zeros((n, HEADS, 128))
-    k[0:2 * half:2], k[1:2 * half:2] = 4 * signs, -4 * signs
+    to be > 150 nats, so every other probability underflows to 0 in fp32 and out[r] = v[sel(r)] = e_(sel(r) mod 128), exactly.
+    nkv: the number of keys where it is not n (the n queries then draw from them); must: keys that queries 0, 1, .. select in every head
+    whatever the draw — when the last key of an odd nkv is among them, the zero row is key nkv // 2 instead."""
+    nkv = n if nkv is None else nkv
+    g = torch.Generator("cpu").manual_seed(8000 + n + (0 if nkv == n else 3 * nkv))
+    half = nkv // 2
+    signs = (torch.randint(0, 2, (half, heads, 128), generator=g) * 2 - 1).float()
+    zero = nkv - 1 if nkv - 1 not in must else nkv // 2                  # of an odd nkv
+    assert nkv % 2 == 0 or zero not in must
+    rows = torch.tensor([i for i in range(nkv) if nkv % 2 == 0 or i != zero])
+    k = torch.zeros((nkv, heads, 128))
+    k[rows[0::2]], k[rows[1::2]] = 4 * signs, -4 * signs
     live = 2 * half                                                      # the zero row of an odd n is selected by nobody
-    sel = torch.stack([torch.randperm(live, generator=g)[torch.arange(n) % live] for _ in range(HEADS)], 1)      # (n, H)
-    q = 4 * k[sel, torch.arange(HEADS)]                                  # 16 x sign
-    v = torch.zeros((n, HEADS, 128))
-    v[torch.arange(n), :, torch.arange(n) % 128] = 1.0
-    want = v[sel, torch.arange(HEADS)]
+    sel = torch.stack([rows[torch.randperm(live, generator=g)[torch.arange(n) % live]] for _ in range(heads)], 1)      # (n, H)
+    for i, key in enumerate(must):
+        sel[i] = key
+    q = 4 * k[sel, torch.arange(heads)]                                  # 16 x sign
+    v = torch.zeros((nkv, heads, 128))
+    v[torch.arange(nkv), :, torch.arange(nkv) % 128] = 1.0
+    want = v[sel, torch.arange(heads)]
     gap = float("inf")
-    for h in range(HEADS):
+    for h in range(heads):
         logits = (q[:, h].double() @ k[:, h].double().T) * 128 ** -0.5
         top = logits.gather(1, sel[:, h:h + 1])
         assert (top == 16 * 4 * 128 * 128 ** -0.5).all()
         gap = min(gap, (top - logits.scatter(1, sel[:, h:h + 1], float("-inf")).amax(1, keepdim=True)).min().item())
-    return q.view(n, -1).to(BF16), k.view(n, -1).to(BF16), v.view(n, -1).to(BF16), want.view(n, -1).to(BF16), gap
+    return q.view(n, -1).to(BF16), k.view(nkv, -1).to(BF16), v.view(nkv, -1).to(BF16), want.view(n, -1).to(BF16), gap
 
 
 @pytest.mark.parametrize("n", ATTN_N)
 def test_exact_case_construction(n):
-    q, k, v, want, gap = exact_case(n)
-    print(f"exact case N = {n}: smallest logit gap {gap:.1f} nats")
+    check_exact_case(n)
+
+
+def check_exact_case(n, nkv=None, heads=HEADS, must=()):
+    """The conditions exact_case rests on, for one of its cases (nkv None: n keys, the zero row of an odd n the last)."""
+    q, k, v, want, gap = exact_case(n, nkv, heads, must)
+    nkv = n if nkv is None else nkv
+    print(f"exact case Nq = {n}, Nkv = {nkv}, {heads} heads: smallest logit gap {gap:.1f} nats")
     assert gap > 150
-    q8, k8, sq, sk, _, _ = quant_emu(q, k, HEADS)
+    q8, k8, sq, sk, _, _ = quant_emu(q, k, heads)
     assert (sk == 4 / 448).all() and (sq == 16 / 448).all() and (q8.float().abs() == 448).all()
-    assert (k8.float().abs()[: 2 * (n // 2)] == 448).all() and (k8.float()[2 * (n // 2):] == 0).all()
-    emu = attn_emu(q8, k8, sq, sk, v, HEADS)      # fp64 does not underflow where fp32 does: e^-150 is what is left of the other keys
+    zero = [] if nkv % 2 == 0 else [nkv - 1 if nkv - 1 not in must else nkv // 2]
+    live = [i for i in range(nkv) if i not in zero]
+    assert (k8.float().abs()[live] == 448).all() and (k8.float()[zero] == 0).all()
+    emu = attn_emu(q8, k8, sq, sk, v, heads)      # fp64 does not underflow where fp32 does: e^-150 is what is left of the other keys
     assert torch.equal(emu.to(BF16), want) and (emu - want.double()).abs().max().item() < 1e-60
+    for i, key in enumerate(must):                # the keys a case names are selected, in every head
+        assert (want[i].view(heads, 128).argmax(1) == key % 128).all() and (want[i].view(heads, 128).sum(1) == 1).all()
 
 
 @gpu

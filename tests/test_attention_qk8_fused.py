@@ -131,11 +131,15 @@ def test_gpu_inputs_lie_where_the_sum_is_exact():
     for where its rounding is not the kernel's (the GPU test repeats the count on the kernel's own bf16 keys)."""
     for (n, heads) in SHAPES:
         for variant in VARIANTS:
-            qkv, _, wk, ang = case(n, heads, variant)
-            c = heads * 128
-            for a in (ang, None):
-                bits = exact_sum_bits(norm_rope_emu(qkv[0, :, c:2 * c], wk, a), n)
-                assert bits <= 50, f"N = {n}, {heads} heads, {variant}: an exact sum needs {bits} bits"
+            check_sum_is_exact(n, heads, variant)
+
+
+def check_sum_is_exact(n, heads, variant):
+    qkv, _, wk, ang = case(n, heads, variant)
+    c = heads * 128
+    for a in (ang, None):
+        bits = exact_sum_bits(norm_rope_emu(qkv[0, :, c:2 * c], wk, a), n)
+        assert bits <= 50, f"N = {n}, {heads} heads, {variant}: an exact sum needs {bits} bits"
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2. the ABI and the switch
@@ -318,9 +322,14 @@ def poisoned(g, shape, dtype):
 @pytest.mark.parametrize("mode", TABLES)
 @pytest.mark.parametrize("n,heads", SHAPES)
 def test_producers_equal_the_two_step_path(hip, n, heads, mode):
+    check_producers(hip, n, heads, mode)
+
+
+def check_producers(hip, n, heads, mode, variants=VARIANTS):
+    """The three producers on case(n, heads, variant) against reference(...), byte for byte, on poisoned and guarded buffers."""
     from test_buffer_contract import Guards
     c = heads * 128
-    for variant in VARIANTS:
+    for variant in variants:
         qkv, wq, wk, ang = case(n, heads, variant)
         k_ref, q8_ref, k8_ref, sq_ref, sk_ref, kbar_ref = reference(n, heads, variant, mode)
         bits = exact_sum_bits(k_ref.cpu(), n)
@@ -357,7 +366,11 @@ def test_producers_equal_the_two_step_path(hip, n, heads, mode):
 
 @gpu
 def test_composed_attention_equals_the_two_step_path(hip):
-    n, heads, c = 1030, 2, 256
+    check_composed_attention(hip, 1030, 2)
+
+
+def check_composed_attention(hip, n, heads):
+    c = heads * 128
     qkv, wq, wk, ang = case(n, heads, "normal")
     d, cs = qkv.cuda(), tables(ang, "f32", "cuda")
     q = hip.rmsnorm_rope(d[..., :c], wq.cuda(), heads, EPS, *cs)
