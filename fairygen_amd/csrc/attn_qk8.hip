@@ -11,7 +11,6 @@
 // more by the first, 1.5 bytes written per 4 read.
 #include "common.h"
 #include "attn_qk8_quant.h"
-#include "../../include/fairygen_hip_qk8.h"
 
 namespace {
 

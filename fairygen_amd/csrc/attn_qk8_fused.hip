@@ -1,4 +1,4 @@
-// The e4m3 operands of fg_attn_fwd_qk8_bf16 written by the RMSNorm+RoPE pass (include/fairygen_hip_qk8_fused.h), for gfx950.
+// The e4m3 operands of fg_attn_fwd_qk8_bf16 written by the RMSNorm+RoPE pass (include/fairygen_hip.h), for gfx950.
 //
 // rmsnorm_rope_kernel (dit_elementwise.hip) holds every post-RoPE q and k row in registers, one wave per row; with head_dim 128 a head
 // is 16 adjacent lanes of one vector slot.  The stand-alone quantise pass (attn_qk8.hip) reads that kernel's bf16 k twice for the key
@@ -13,7 +13,6 @@
 #include "common.h"
 #include "rmsnorm_rope_row.h"
 #include "attn_qk8_quant.h"
-#include "../../include/fairygen_hip_qk8_fused.h"
 
 #include <math.h>
 

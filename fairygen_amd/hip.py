@@ -14,10 +14,12 @@ _LIB_PATH = os.environ.get("FAIRYGEN_HIP_LIB") or os.path.join(os.path.dirname(o
 _lib = None
 
 ABI_VERSION = 8
+QK8_ABI_VERSION = 1       # fg_attn_qk8_version: the e4m3 Q K^T self-attention
+QK8F_ABI_VERSION = 1      # fg_attn_qk8_fused_version: its operands written by the RMSNorm+RoPE pass
 
 _i64, _i32, _f32, _vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
-# name -> argtypes; every function returns int except where noted.  Mirrors include/fairygen_hip.h.
+# The entry points that take a stream and return int: name -> argtypes.  With _QUERIES, what include/fairygen_hip.h declares.
 _SIGNATURES = {
     "fg_ln_modulate_bf16": [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _i64, _i64, _i64, _vp],
     "fg_ln_affine_bf16": [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
@@ -55,38 +57,30 @@ _SIGNATURES = {
     "fg_video_to_uint8": [_vp, _vp, _i32, _i32, _i32, _vp],
     "fg_softmax_bias_bf16": [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "fg_gated_gelu_bf16": [_vp, _vp, _vp, _i64, _vp],
-}
-# Entry points added after tests/test_buffer_contract.py was written.  That test asserts that every key of _SIGNATURES has an
-# argument-check spec in it, and a change that adds an entry point does not edit existing tests, so the new name is listed here and its
-# argument checks are tested in tests/test_lora_fuse_kernel.py; to be folded into _SIGNATURES together with a spec in that test.
-_LOAD_TIME_SIGNATURES = {
     "fg_lora_fuse_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _f32, _vp],
-}
-# The entry point of the captured denoise step (ABI 8), in a table of its own for the same reason; its stream and argument checks are in
-# tests/test_graph_step.py.
-_GRAPH_SIGNATURES = {
     "fg_cfg_euler_dev_bf16": [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _i64, _i64, _vp],
-}
-# The entry points of the e4m3 Q K^T self-attention: an extension with a header (include/fairygen_hip_qk8.h) and a version of its own
-# (fg_attn_qk8_version), so the base ABI, its version and EXPORTED_SYMBOLS stay what the older tests pin; their stream, capture and argument
-# checks are in tests/test_attention_qk8.py.
-QK8_ABI_VERSION = 1
-_QK8_SIGNATURES = {
     "fg_attn_quant_qk_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
     "fg_attn_fwd_qk8_bf16": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _i64, _vp],
-}
-EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_LOAD_TIME_SIGNATURES) + list(_GRAPH_SIGNATURES) + ["fg_version", "fg_last_error", "fg_conv_packed_bytes", "fg_attn_workspace_bytes", "fg_attn_split_choice",
-                                                   "fg_conv_tile_choice", "fg_gemm_workspace_bytes", "fg_gemm_debug_grid", "fg_gemm_sched_bytes"])
-QK8_EXPORTED_SYMBOLS = sorted(list(_QK8_SIGNATURES) + ["fg_attn_qk8_version"])      # what include/fairygen_hip_qk8.h declares
-# The e4m3 operands written by the RMSNorm+RoPE pass: a second extension (include/fairygen_hip_qk8_fused.h, fg_attn_qk8_fused_version), so
-# the two tables above stay what their tests pin; its checks are in tests/test_attention_qk8_fused.py.
-QK8F_ABI_VERSION = 1
-_QK8F_SIGNATURES = {
     "fg_rmsnorm_rope_q8_bf16": [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _f32, _vp],
     "fg_rmsnorm_rope_kstats_bf16": [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp],
     "fg_attn_quant_k_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
 }
-QK8F_EXPORTED_SYMBOLS = sorted(list(_QK8F_SIGNATURES) + ["fg_attn_qk8_fused_version", "fg_attn_qk8_fused_scratch_bytes"])
+# The host-only functions (no stream, nothing launched): name -> (restype, argtypes).
+_QUERIES = {
+    "fg_version": (_i32, []),
+    "fg_last_error": (ctypes.c_char_p, []),
+    "fg_conv_packed_bytes": (_i64, [_i32] * 5),
+    "fg_attn_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32]),
+    "fg_attn_split_choice": (_i32, [_i32, _i64, _i64, _i32, _i64, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "fg_conv_tile_choice": (_i32, [_i32] * 4),
+    "fg_gemm_workspace_bytes": (_i64, [_i64] * 3),
+    "fg_gemm_debug_grid": (_i32, [_i32]),
+    "fg_gemm_sched_bytes": (_i64, []),
+    "fg_attn_qk8_version": (_i32, []),
+    "fg_attn_qk8_fused_version": (_i32, []),
+    "fg_attn_qk8_fused_scratch_bytes": (_i64, [_i64, _i32]),
+}
+EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_QUERIES))      # what include/fairygen_hip.h declares
 
 
 class HipLibraryError(RuntimeError):
@@ -107,38 +101,14 @@ def load():
             f"{_LIB_PATH} not found: build it with `make -C fairygen_amd/csrc` (or __graft_entry__.build()). "
             "fairygen_amd has no CPU / PyTorch fallback for its kernels.")
     lib = ctypes.CDLL(_LIB_PATH)
-    lib.fg_version.restype = ctypes.c_int
-    lib.fg_last_error.restype = ctypes.c_char_p
-    lib.fg_conv_packed_bytes.restype = ctypes.c_int64
-    lib.fg_conv_packed_bytes.argtypes = [_i32] * 5
-    lib.fg_attn_workspace_bytes.restype = ctypes.c_int64
-    lib.fg_attn_workspace_bytes.argtypes = [_i32, _i64, _i64, _i32]
-    lib.fg_conv_tile_choice.restype = ctypes.c_int
-    lib.fg_conv_tile_choice.argtypes = [_i32] * 4
-    lib.fg_gemm_workspace_bytes.restype = ctypes.c_int64
-    lib.fg_gemm_workspace_bytes.argtypes = [_i64] * 3
-    lib.fg_gemm_sched_bytes.restype = ctypes.c_int64
-    lib.fg_gemm_sched_bytes.argtypes = []
-    lib.fg_gemm_debug_grid.restype = ctypes.c_int
-    lib.fg_gemm_debug_grid.argtypes = [_i32]
-    lib.fg_attn_split_choice.restype = ctypes.c_int
-    lib.fg_attn_split_choice.argtypes = [_i32, _i64, _i64, _i32, _i64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    for name, argtypes in {**_SIGNATURES, **_LOAD_TIME_SIGNATURES, **_GRAPH_SIGNATURES, **_QK8_SIGNATURES, **_QK8F_SIGNATURES}.items():
-        fn = getattr(lib, name)
-        fn.restype = ctypes.c_int
-        fn.argtypes = argtypes
-    if lib.fg_version() != ABI_VERSION:
-        raise HipLibraryError(f"ABI mismatch: library {lib.fg_version()} != binding {ABI_VERSION}")
-    lib.fg_attn_qk8_version.restype = ctypes.c_int
-    lib.fg_attn_qk8_version.argtypes = []
-    if lib.fg_attn_qk8_version() != QK8_ABI_VERSION:
-        raise HipLibraryError(f"ABI mismatch (e4m3 Q K^T extension): library {lib.fg_attn_qk8_version()} != binding {QK8_ABI_VERSION}")
-    lib.fg_attn_qk8_fused_version.restype = ctypes.c_int
-    lib.fg_attn_qk8_fused_version.argtypes = []
-    if lib.fg_attn_qk8_fused_version() != QK8F_ABI_VERSION:
-        raise HipLibraryError(f"ABI mismatch (fused e4m3 producers): library {lib.fg_attn_qk8_fused_version()} != binding {QK8F_ABI_VERSION}")
-    lib.fg_attn_qk8_fused_scratch_bytes.restype = ctypes.c_int64
-    lib.fg_attn_qk8_fused_scratch_bytes.argtypes = [_i64, _i32]
+    for name, argtypes in _SIGNATURES.items():
+        getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
+    for name, (restype, argtypes) in _QUERIES.items():
+        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
+    for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
+                                 ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)")):
+        if getattr(lib, name)() != expected:
+            raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
     return lib
 
@@ -283,10 +253,13 @@ def residual_ln_affine(x, y, w, b, eps, mod=None, gate_idx=None, x_out=None, nor
     return _residual_ln(x, y, eps, x_out, norm_out, *_ln_affine_args(x, w, b, mod, gate_idx))
 
 
+def _fp8_pair(rows, c, device):
+    return (torch.empty((rows, c), dtype=torch.float8_e4m3fn, device=device),
+            torch.empty((rows, 1), dtype=torch.float32, device=device))
+
+
 def _fp8_rows_out(x):
-    rows, c = _rows(x, "x")
-    return (torch.empty((rows, c), dtype=torch.float8_e4m3fn, device=x.device),
-            torch.empty((rows, 1), dtype=torch.float32, device=x.device))
+    return _fp8_pair(*_rows(x, "x"), x.device)
 
 
 def ln_modulate_fp8(x, mod, shift_idx, scale_idx, eps):
@@ -330,6 +303,20 @@ def residual_ln_affine_fp8(x, y, w, b, eps, mod=None, gate_idx=None, x_out=None)
     return _residual_ln(x, y, eps, x_out, None, *_ln_affine_args(x, w, b, mod, gate_idx), fp8=True)
 
 
+def _rope_tables(who, cos, sin, rows, half):
+    """fg_rmsnorm_rope_bf16's table modes: (cos, sin, table_f32) checked against the row count."""
+    if cos is not None and sin is None:
+        _dev(cos, "rope table", torch.float32)
+        if cos.shape != (rows, half, 2) or not cos.is_contiguous():
+            raise HipLibraryError(f"{who}: the fp32 rope table must be ({rows}, {half}, 2) contiguous")
+        return 1
+    if cos is not None:
+        _dev(cos, "cos", torch.float64), _dev(sin, "sin", torch.float64)
+        if cos.shape != (rows, half) or not cos.is_contiguous() or sin.shape != (rows, half) or not sin.is_contiguous():
+            raise HipLibraryError(f"{who}: rope tables must be ({rows}, {half}) contiguous")
+    return 0
+
+
 def rmsnorm_rope(x, weight, num_heads, eps, cos=None, sin=None, out=None, grouped=None):
     """x: (..., C) possibly a column slice of a wider row-major buffer (stride(-2) = ld).
 
@@ -344,16 +331,7 @@ def rmsnorm_rope(x, weight, num_heads, eps, cos=None, sin=None, out=None, groupe
     rows, ld = x2.shape[0], x2.stride(0)
     if grouped is None:
         out = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
-    f32tab = 0
-    if cos is not None and sin is None:
-        f32tab = 1
-        _dev(cos, "rope table", torch.float32)
-        if cos.shape != (rows, c // num_heads // 2, 2) or not cos.is_contiguous():
-            raise HipLibraryError(f"rmsnorm_rope: the fp32 rope table must be ({rows}, {c // num_heads // 2}, 2) contiguous")
-    elif cos is not None:
-        _dev(cos, "cos", torch.float64), _dev(sin, "sin", torch.float64)
-        if cos.shape != (rows, c // num_heads // 2) or not cos.is_contiguous() or not sin.is_contiguous():
-            raise HipLibraryError(f"rmsnorm_rope: rope tables must be ({rows}, {c // num_heads // 2}) contiguous")
+    f32tab = _rope_tables("rmsnorm_rope", cos, sin, rows, c // num_heads // 2)
     if grouped is not None:
         dst, group_cols, group_stride, out_ld = grouped
         _dev(dst, "grouped dst")
@@ -611,8 +589,7 @@ def fp8_quant_rows(x, act=None):
     c = x.shape[-1]
     x2 = _rows2d(x, "fp8_quant_rows")
     rows, ld = x2.shape[0], x2.stride(0)
-    out = torch.empty((rows, c), dtype=torch.float8_e4m3fn, device=x.device)
-    scale = torch.empty((rows, 1), dtype=torch.float32, device=x.device)
+    out, scale = _fp8_pair(rows, c, x.device)
     _call("fg_fp8_quant_rows_bf16", _ptr(x2), ld, _ptr(out), _ptr(scale), None, rows, c,
           {None: 0, "gelu_tanh": 1}[act], FP8_E4M3FN_MAX, _stream(x))
     return out, scale
@@ -641,6 +618,23 @@ def _ld_rows(t, name):
 _attn_workspace = {}      # (device, stream) -> scratch tensor for the split-KV partials (grown on demand, reused)
 
 
+def _attn_ws(device, b, nq, nkv, num_heads, workspace):
+    """(ws, need): the split-KV scratch of an attention launch and the bytes it wants (0: none).  ws is the tensor of the caller's list
+    `workspace`, or with None the one kept for (device, current stream); either is grown here when it is smaller than need."""
+    need = load().fg_attn_workspace_bytes(b, nq, nkv, num_heads)
+    if workspace is not None:
+        ws = workspace[0] if workspace else None
+        if need > 0 and (ws is None or ws.numel() < need or ws.device != device):
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+            workspace[:] = [ws]
+    else:
+        key = (device, torch.cuda.current_stream(device).cuda_stream)      # concurrent streams must not share scratch
+        ws = _attn_workspace.get(key)
+        if need > 0 and (ws is None or ws.numel() < need):
+            ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws, need
+
+
 def pow2_softmax_scale(head_dim):
     """(scale', f) with scale' * log2(e) = the power of two next to head_dim^-0.5 * log2(e) and f = their ratio (1.0201 for d = 128):
     softmax(scale' (f q) k^T) = softmax(q k^T / sqrt(d)), and fg_attn_fwd_bf16 runs its pre-multiplied form exactly for scale'."""
@@ -659,17 +653,7 @@ def attention(q, k, v, num_heads, out=None, scale=None, workspace=None):
     nkv = k.shape[1]
     d = hd // num_heads
     out = torch.empty((b, nq, hd), dtype=q.dtype, device=q.device) if out is None else out
-    need = load().fg_attn_workspace_bytes(b, nq, nkv, num_heads)
-    if workspace is not None:
-        ws = workspace[0] if workspace else None
-        if need > 0 and (ws is None or ws.numel() < need or ws.device != q.device):
-            ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-            workspace[:] = [ws]
-    else:
-        key = (q.device, torch.cuda.current_stream(q.device).cuda_stream)      # concurrent streams must not share scratch
-        ws = _attn_workspace.get(key)
-        if need > 0 and (ws is None or ws.numel() < need):
-            ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws, need = _attn_ws(q.device, b, nq, nkv, num_heads, workspace)
     _call("fg_attn_fwd_bf16", _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(out), b, nq, nkv, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q))
     return out
@@ -709,17 +693,7 @@ def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, worksp
     if b != 1 or q8.shape != (nq, hd) or k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads:
         raise HipLibraryError(f"attention_qk8_pre: one batch element, k8 and sk for v {tuple(v.shape)}, sq for q8 {tuple(q8.shape)}")
     out = torch.empty((b, nq, hd), dtype=v.dtype, device=v.device) if out is None else out
-    need = load().fg_attn_workspace_bytes(1, nq, nkv, num_heads)
-    if workspace is not None:
-        ws = workspace[0] if workspace else None
-        if need > 0 and (ws is None or ws.numel() < need or ws.device != v.device):
-            ws = torch.empty(need, dtype=torch.uint8, device=v.device)
-            workspace[:] = [ws]
-    else:
-        key = (v.device, torch.cuda.current_stream(v.device).cuda_stream)
-        ws = _attn_workspace.get(key)
-        if need > 0 and (ws is None or ws.numel() < need):
-            ws = _attn_workspace[key] = torch.empty(need, dtype=torch.uint8, device=v.device)
+    ws, need = _attn_ws(v.device, 1, nq, nkv, num_heads, workspace)
     _call("fg_attn_fwd_qk8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v), ldv, _ptr(out), nq, nkv, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
     return out
@@ -742,20 +716,6 @@ def attention_qk8_fused_scratch(n, num_heads, head_dim, device):
     if need < 0:
         raise HipLibraryError(f"attention_qk8_fused_scratch: {load().fg_last_error().decode()}")
     return attention_qk8_scratch(n, num_heads, head_dim, device) + (torch.empty(need, dtype=torch.uint8, device=device),)
-
-
-def _rope_tables(who, cos, sin, rows, half):
-    """fg_rmsnorm_rope_bf16's table modes: (cos, sin, table_f32) checked against the row count."""
-    if cos is not None and sin is None:
-        _dev(cos, "rope table", torch.float32)
-        if cos.shape != (rows, half, 2) or not cos.is_contiguous():
-            raise HipLibraryError(f"{who}: the fp32 rope table must be ({rows}, {half}, 2) contiguous")
-        return 1
-    if cos is not None:
-        _dev(cos, "cos", torch.float64), _dev(sin, "sin", torch.float64)
-        if cos.shape != (rows, half) or not cos.is_contiguous() or sin.shape != (rows, half) or not sin.is_contiguous():
-            raise HipLibraryError(f"{who}: rope tables must be ({rows}, {half}) contiguous")
-    return 0
 
 
 def rmsnorm_rope_q8(x, weight, num_heads, eps, cos=None, sin=None, q8=None, sq=None):

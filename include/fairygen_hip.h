@@ -385,6 +385,61 @@ int fg_softmax_bias_bf16(const void* scores, const void* bias, const int* key_ma
  * that expression rounded to bf16 as the reference's explicit GELU module does. */
 int fg_gated_gelu_bf16(const void* fc1, const void* gate, void* out, int64_t n, fg_stream_t stream);
 
+/* ------------------------------------------------------------- e4m3 Q K^T self-attention (opt-in)
+ * The self-attention with an 8-bit Q K^T product, under the contract above.  tests/test_attention_qk8.py holds the recipe, the argument
+ * checks, the stream and capture checks. */
+
+int fg_attn_qk8_version(void);           /* version of this extension, currently 1 */
+
+/* The form the reference's flash_attention takes when the sageattention package is present (models/wan_video_dit.py:48-52: sageattn with
+ * q, k, v): e4m3 Q K^T with K mean-smoothing, P V in bf16.  One head at a time, q and k (N, 128) after RMSNorm and RoPE:
+ *   kbar = mean of k over its N rows (per channel: the fp64 sum, divided by N, rounded once to fp32); k' = fp32(k) - kbar;
+ *   sk = max(max|k'| / 448, 2^-20), one per head; k8 = e4m3(k' / sk), round-to-nearest-even, saturating at +-448;
+ *   sq[r] = max(max|q[r]| / 448, 2^-20), one per row and head; q8 = e4m3(q / sq[r]);
+ *   out = softmax(scale * sq[r] * sk * (q8 k8^T)) v — the product accumulated in fp32 by the plain (unscaled) e4m3 MFMA, the online
+ *   softmax, the bf16 P and the bf16 P V of the 8-wave kernel behind fg_attn_fwd_bf16.  q . kbar is constant along a row: dropped.
+ * fg_attn_quant_qk_bf16: q, k (N, H*128) bf16 with leading dimensions ldq / ldk -> q8, k8 (N, H*128) e4m3 bytes (8-byte aligned),
+ * sq (N, H) and sk (H) fp32.  Two launches on `stream`; scratch: H*128 floats (the column means), 16-byte aligned.  One batch element.
+ * fg_attn_fwd_qk8_bf16: q8 (Nq, H*128), k8 (Nkv, H*128), sq (Nq, H), sk (H) as written above (q8, k8 16-byte aligned), v (Nkv, H*128)
+ * bf16 with leading dimension ldv, out (Nq, H*128) bf16 contiguous.  workspace: as for fg_attn_fwd_bf16, sized by fg_attn_workspace_bytes
+ * with B = 1.  Any Nkv >= 1; cross-attention is not meant to take it. */
+int fg_attn_quant_qk_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, void* q8, void* k8, float* sq, float* sk,
+                          void* scratch, int64_t scratch_bytes, int64_t N, int H, int D, fg_stream_t stream);
+int fg_attn_fwd_qk8_bf16(const void* q8, const void* k8, const float* sq, const float* sk, const void* v, int64_t ldv, void* out,
+                         int64_t Nq, int64_t Nkv, int H, int D, float scale, void* workspace, int64_t workspace_bytes,
+                         fg_stream_t stream);
+
+/* ------------------------------------------- the e4m3 operands written by the RMSNorm+RoPE pass
+ * The operands of fg_attn_fwd_qk8_bf16 written by the RMSNorm+RoPE pass itself, by the recipe above, unchanged: on the same inputs these
+ * entry points write the q8, sq, k8, sk and key mean that fg_rmsnorm_rope_bf16 followed by fg_attn_quant_qk_bf16 writes, byte for byte —
+ * the key mean where its fp64 sum is exact (8 significand bits + the exponent spread of the non-zero values + log2 N below 53 bits),
+ * which is where the order of a sum cannot show.  tests/test_attention_qk8_fused.py holds the comparison, the argument, stream and
+ * capture checks. */
+
+int fg_attn_qk8_fused_version(void);     /* version of this extension, currently 1 */
+
+/* Bytes of the key-statistics partials for `rows` keys of C channels: P records per channel (an fp64 sum, a minimum, a maximum: 16
+ * bytes), P a function of rows alone.  -1 on rows < 1 or a C that is not a positive multiple of 128 up to 4096. */
+int64_t fg_attn_qk8_fused_scratch_bytes(int64_t rows, int C);
+
+/* x (rows, C) bf16 with leading dimension ldx, weight (C), the rope tables and table_f32 as for fg_rmsnorm_rope_bf16, C = num_heads * 128.
+ * fg_rmsnorm_rope_q8_bf16: the normed, rotated row never leaves as bf16: q8 (rows, C) e4m3 bytes (8-byte aligned) and sq (rows,
+ * num_heads) fp32, one scale per row and head.  One launch.
+ * fg_rmsnorm_rope_kstats_bf16: k_out (rows, C) bf16 contiguous — fg_rmsnorm_rope_bf16's bytes — and, to `partials` (16-byte aligned,
+ * fg_attn_qk8_fused_scratch_bytes), every workgroup's per-channel sum, minimum and maximum of the rows it walked.  One launch; every
+ * record of the buffer is written (a workgroup without a row writes 0, +inf, -inf).
+ * fg_attn_quant_k_bf16: k (N, H*128) bf16 with leading dimension ldk and the partials written for these N rows -> kbar (H*128 fp32,
+ * 16-byte aligned; the mean), sk (H) and k8 (N, H*128) e4m3 bytes (8-byte aligned).  Two launches: the reduction of the partials
+ * (sk from the channel extremes: fp32 rounding is monotone, so max_rows |fl(k - kbar)| = max(fl(kmax - kbar), fl(kbar - kmin))), then
+ * the quantise pass. */
+int fg_rmsnorm_rope_q8_bf16(const void* x, int64_t ldx, const void* weight, const void* cos_tab, const void* sin_tab, int table_f32,
+                            void* q8, float* sq, int64_t rows, int C, int num_heads, float eps, fg_stream_t stream);
+int fg_rmsnorm_rope_kstats_bf16(const void* x, int64_t ldx, const void* weight, const void* cos_tab, const void* sin_tab, int table_f32,
+                                void* k_out, void* partials, int64_t partials_bytes, int64_t rows, int C, int num_heads, float eps,
+                                fg_stream_t stream);
+int fg_attn_quant_k_bf16(const void* k, int64_t ldk, const void* partials, int64_t partials_bytes, void* k8, float* sk, float* kbar,
+                         int64_t N, int H, int D, fg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-"""The opt-in e4m3 Q K^T self-attention (WanModel.enable_qk8_attention, fg_attn_quant_qk_bf16 + fg_attn_fwd_qk8_bf16, include/fairygen_hip_qk8.h): the form
+"""The opt-in e4m3 Q K^T self-attention (WanModel.enable_qk8_attention, fg_attn_quant_qk_bf16 + fg_attn_fwd_qk8_bf16, include/fairygen_hip.h): the form
 the reference's flash_attention takes when the sageattention package is present (models/wan_video_dit.py:48-52).
 
 The recipe is written out below in fp32 / fp64 torch (`quant_emu`, `attn_emu`) and is what the kernels are held to:
@@ -153,12 +153,13 @@ NAMES = ("fg_attn_quant_qk_bf16", "fg_attn_fwd_qk8_bf16")
 
 def test_abi_declared_exported_bound():
     lib = _hip.load()
-    header = open(os.path.join(REPO, "include", "fairygen_hip_qk8.h")).read()
-    # an extension header with a version of its own: the base ABI and its symbol list are what they were
+    header = open(os.path.join(REPO, "include", "fairygen_hip.h")).read()
     assert lib.fg_version() == _hip.ABI_VERSION and _hip.QK8_ABI_VERSION == 1 and lib.fg_attn_qk8_version() == 1
-    assert "version of this extension, currently 1" in header and '#include "fairygen_hip.h"' in header
-    assert sorted(set(re.findall(r"\b(fg_[a-z0-9_]+)\s*\(", header))) == _hip.QK8_EXPORTED_SYMBOLS
-    assert not set(_hip.QK8_EXPORTED_SYMBOLS) & set(_hip.EXPORTED_SYMBOLS)
+    assert "version of this extension, currently 1" in header
+    # the entry points and their version function: declared in the header, each exactly once, and in EXPORTED_SYMBOLS
+    declared = re.findall(r"^(?:int|int64_t) (fg_[a-z0-9_]+)\s*\(", header, re.M)
+    for name in NAMES + ("fg_attn_qk8_version",):
+        assert declared.count(name) == 1 and name in _hip.EXPORTED_SYMBOLS, name
     assert re.search(r"^int fg_attn_quant_qk_bf16\(const void\* q, int64_t ldq, const void\* k, int64_t ldk, void\* q8, void\* k8, float\* sq, "
                      r"float\* sk,\s*void\* scratch, int64_t scratch_bytes, int64_t N, int H, int D, fg_stream_t stream\);", header, re.M)
     assert re.search(r"^int fg_attn_fwd_qk8_bf16\(const void\* q8, const void\* k8, const float\* sq, const float\* sk, const void\* v, int64_t ldv, "
@@ -166,12 +167,12 @@ def test_abi_declared_exported_bound():
                      r"fg_stream_t stream\);", header, re.M)
     assert "models/wan_video_dit.py:48-52" in header
     V, I64, I32, F = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
-    assert _hip._QK8_SIGNATURES == {NAMES[0]: [V, I64, V, I64, V, V, V, V, V, I64, I64, I32, I32, V],
-                                    NAMES[1]: [V, V, V, V, V, I64, V, I64, I64, I32, I32, F, V, I64, V]}
+    assert {n: _hip._SIGNATURES[n] for n in NAMES} == {NAMES[0]: [V, I64, V, I64, V, V, V, V, V, I64, I64, I32, I32, V],
+                                                       NAMES[1]: [V, V, V, V, V, I64, V, I64, I64, I32, I32, F, V, I64, V]}
     raw = ctypes.CDLL(_hip.library_path())
     for name in NAMES:
-        assert name in _hip.QK8_EXPORTED_SYMBOLS and hasattr(raw, name) and getattr(lib, name).argtypes == _hip._QK8_SIGNATURES[name]
-        assert name not in _hip._SIGNATURES and name not in _hip._LOAD_TIME_SIGNATURES and name not in _hip._GRAPH_SIGNATURES
+        assert hasattr(raw, name) and getattr(lib, name).argtypes == _hip._SIGNATURES[name]
+    assert hasattr(raw, "fg_attn_qk8_version") and "fg_attn_qk8_version" in _hip._QUERIES
 
 
 def test_argument_checks():

@@ -1,11 +1,11 @@
-"""The e4m3 operands of the opt-in 8-bit Q K^T self-attention written by the RMSNorm+RoPE pass itself (include/fairygen_hip_qk8_fused.h:
+"""The e4m3 operands of the opt-in 8-bit Q K^T self-attention written by the RMSNorm+RoPE pass itself (include/fairygen_hip.h:
 fg_rmsnorm_rope_q8_bf16, fg_rmsnorm_rope_kstats_bf16, fg_attn_quant_k_bf16; WanModel.enable_qk8_attention(fused_producer=True)).  The recipe
 is tests/test_attention_qk8.py's, unchanged, and the yardstick is the path that file pins to it: hip.rmsnorm_rope -> hip.attn_quant_qk.  The
 fused producers must write the same q8, sq, k, k8, sk and key mean byte for byte, so nothing here has a tolerance.
 
   1. (no GPU) the two identities the one-pass key statistics rest on, in torch: an exact fp64 column sum does not depend on its order, and
      max_rows |fl(v - m)| = max(fl(vmax - m), fl(m - vmin)); and that the inputs of the GPU tests lie where the fp64 sum is exact.
-  2. (no GPU) the ABI: declared, exported, bound, disjoint from the two older symbol lists; the argument checks; the routing switch.
+  2. (no GPU) the ABI: declared once, exported, bound; the argument checks; the routing switch.
   3. the producers against the two-step path on strided, poisoned, guarded buffers; the composed attention; stream and capture.
   4. the tiny DiT forward and the captured loop: fused_producer=True equals fused_producer=False bit for bit."""
 import ctypes
@@ -144,21 +144,20 @@ def check_sum_is_exact(n, heads, variant):
 
 # ------------------------------------------------------------------------------------------------------------------ 2. the ABI and the switch
 NAMES = ("fg_rmsnorm_rope_q8_bf16", "fg_rmsnorm_rope_kstats_bf16", "fg_attn_quant_k_bf16")
+QUERIES = ("fg_attn_qk8_fused_version", "fg_attn_qk8_fused_scratch_bytes")
 
 
 def test_abi_declared_exported_bound():
     lib = _hip.load()
-    header = open(os.path.join(REPO, "include", "fairygen_hip_qk8_fused.h")).read()
+    header = open(os.path.join(REPO, "include", "fairygen_hip.h")).read()
     assert _hip.QK8F_ABI_VERSION == 1 and lib.fg_attn_qk8_fused_version() == 1
-    assert "version of this extension, currently 1" in header and '#include "fairygen_hip_qk8.h"' in header
-    declared = sorted(set(re.findall(r"^(?:int|int64_t) (fg_[a-z0-9_]+)\s*\(", header, re.M)))
-    assert declared == _hip.QK8F_EXPORTED_SYMBOLS == sorted(NAMES + ("fg_attn_qk8_fused_version", "fg_attn_qk8_fused_scratch_bytes"))
-    # the two older lists are what they were, and the new names are in neither
-    assert len(_hip.EXPORTED_SYMBOLS) == 47 and len(_hip.QK8_EXPORTED_SYMBOLS) == 3 and lib.fg_version() == _hip.ABI_VERSION
-    assert lib.fg_attn_qk8_version() == 1
-    assert not set(declared) & (set(_hip.EXPORTED_SYMBOLS) | set(_hip.QK8_EXPORTED_SYMBOLS))
-    for old in ("fairygen_hip.h", "fairygen_hip_qk8.h"):
-        assert not set(declared) & set(re.findall(r"\b(fg_[a-z0-9_]+)\s*\(", open(os.path.join(REPO, "include", old)).read()))
+    assert header.count("version of this extension, currently 1") == 2
+    # the entry points and their two query functions: declared in the header, each exactly once, and in EXPORTED_SYMBOLS
+    declared = re.findall(r"^(?:int|int64_t) (fg_[a-z0-9_]+)\s*\(", header, re.M)
+    for name in NAMES + QUERIES:
+        assert declared.count(name) == 1 and name in _hip.EXPORTED_SYMBOLS, name
+    assert set(QUERIES) <= set(_hip._QUERIES)
+    assert lib.fg_version() == _hip.ABI_VERSION and lib.fg_attn_qk8_version() == 1
     assert re.search(r"^int fg_rmsnorm_rope_q8_bf16\(const void\* x, int64_t ldx, const void\* weight, const void\* cos_tab, const void\* sin_tab, "
                      r"int table_f32,\s*void\* q8, float\* sq, int64_t rows, int C, int num_heads, float eps, fg_stream_t stream\);", header, re.M)
     assert re.search(r"^int fg_rmsnorm_rope_kstats_bf16\(const void\* x, int64_t ldx, const void\* weight, const void\* cos_tab, const void\* sin_tab, "
@@ -168,13 +167,12 @@ def test_abi_declared_exported_bound():
                      r"float\* kbar,\s*int64_t N, int H, int D, fg_stream_t stream\);", header, re.M)
     assert re.search(r"^int64_t fg_attn_qk8_fused_scratch_bytes\(int64_t rows, int C\);", header, re.M)
     V, I64, I32, F = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
-    assert _hip._QK8F_SIGNATURES == {NAMES[0]: [V, I64, V, V, V, I32, V, V, I64, I32, I32, F, V],
-                                     NAMES[1]: [V, I64, V, V, V, I32, V, V, I64, I64, I32, I32, F, V],
-                                     NAMES[2]: [V, I64, V, I64, V, V, V, I64, I32, I32, V]}
+    assert {n: _hip._SIGNATURES[n] for n in NAMES} == {NAMES[0]: [V, I64, V, V, V, I32, V, V, I64, I32, I32, F, V],
+                                                       NAMES[1]: [V, I64, V, V, V, I32, V, V, I64, I64, I32, I32, F, V],
+                                                       NAMES[2]: [V, I64, V, I64, V, V, V, I64, I32, I32, V]}
     raw = ctypes.CDLL(_hip.library_path())
     for name in NAMES:
-        assert hasattr(raw, name) and getattr(lib, name).argtypes == _hip._QK8F_SIGNATURES[name]
-        assert not any(name in t for t in (_hip._SIGNATURES, _hip._LOAD_TIME_SIGNATURES, _hip._GRAPH_SIGNATURES, _hip._QK8_SIGNATURES))
+        assert hasattr(raw, name) and getattr(lib, name).argtypes == _hip._SIGNATURES[name]
     assert hasattr(raw, "fg_attn_qk8_fused_version") and hasattr(raw, "fg_attn_qk8_fused_scratch_bytes")
 
 

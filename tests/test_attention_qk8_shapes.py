@@ -1,4 +1,4 @@
-"""The e4m3 attention entry points (include/fairygen_hip_qk8.h, include/fairygen_hip_qk8_fused.h) at every width and KV length they accept.
+"""The e4m3 attention entry points (include/fairygen_hip.h) at every width and KV length they accept.
 
 tests/test_attention_qk8.py and tests/test_attention_qk8_fused.py pin the recipe at the shapes the tiny and the full DiT use: 2 and 24
 heads, Nq = Nkv in {1 100, 2 049}.  The headers accept every C = num_heads * 128 <= 4 096 and "any Nkv >= 1"; this file runs the rest,

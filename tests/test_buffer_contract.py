@@ -45,6 +45,7 @@ Cost: the CPU reference work of the module (oracle attention and fp32 / bf16 con
 16-thread host; the whole module 4 s of pytest time (6 s of wall time) on an MI355X, where test_hip_kernels.py takes 15 s.
 """
 import ctypes
+import os
 
 import pytest
 import torch
@@ -854,8 +855,20 @@ def test_argument_checks():
 
     specs = _argcheck_specs(P, lib.fg_gemm_workspace_bytes(256, 256, 256))
     covered = {s[0] for s in specs}
-    skipped = {"fg_gemm_sched_reset"}      # test_gemm_sched_state.py
-    assert covered | skipped == set(hip._SIGNATURES), sorted(set(hip._SIGNATURES) - covered - skipped)
+    skipped = {      # entry point -> "file::test" that holds its argument checks
+        "fg_gemm_sched_reset": "test_gemm_sched_state.py::test_s_entry_points_validate_sched_and_workgroups",
+        "fg_lora_fuse_bf16": "test_lora_fuse_kernel.py::test_argument_checks",
+        "fg_cfg_euler_dev_bf16": "test_graph_step.py::test_cfg_euler_dev_argument_checks",
+        "fg_attn_quant_qk_bf16": "test_attention_qk8.py::test_argument_checks",
+        "fg_attn_fwd_qk8_bf16": "test_attention_qk8.py::test_argument_checks",
+        "fg_rmsnorm_rope_q8_bf16": "test_attention_qk8_fused.py::test_argument_checks",
+        "fg_rmsnorm_rope_kstats_bf16": "test_attention_qk8_fused.py::test_argument_checks",
+        "fg_attn_quant_k_bf16": "test_attention_qk8_fused.py::test_argument_checks",
+    }
+    assert covered | set(skipped) == set(hip._SIGNATURES) and not covered & set(skipped), sorted(set(hip._SIGNATURES) - covered - set(skipped))
+    for name, home in skipped.items():
+        path, test = home.split("::")
+        assert f"\ndef {test}(" in open(os.path.join(os.path.dirname(os.path.abspath(__file__)), path)).read(), f"{name}: {home} does not exist"
     for name, args, breaks in specs:
         assert len(args) == len(getattr(lib, name).argtypes), name
         if have_dev:

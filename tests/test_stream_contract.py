@@ -7,8 +7,9 @@ hidden synchronisation costs nothing; only the persistent GEMM was ever captured
 
   1. CASES: one call through a fairygen_amd.hip wrapper per case, with its inputs built from a seed on the CPU, the buffers it reads and
      writes, and the fg_* names it is declared to reach.  test_case_table_covers_the_abi (no GPU) holds the union of those names equal to
-     the launching entry points of hip._SIGNATURES + fg_lora_fuse_bf16 (the host queries and the two GEMM forms without a block — the
-     documented exception — stay out); on the GPU every case must launch exactly what it declares (recorded at hip._call), and the
+     the entry points of hip._SIGNATURES less the two GEMM forms without a block — the documented exception — and less ELSEWHERE, the
+     ones whose stream and capture checks have a named home in another module (the host queries are hip._QUERIES); on the GPU every
+     case must launch exactly what it declares (recorded at hip._call), and the
      cases of a launcher that picks between kernels assert the pick (fg_attn_split_choice, fg_conv_tile_choice, the scratch of a k-split).
   2. test_capture_and_replay: the call is captured on a fresh side stream in the default (strict) capture mode and replayed on two input
      sets; every output, overwritten with a byte sentinel before each replay, must equal the eager call on the default stream.
@@ -51,9 +52,18 @@ SENTINEL = 0xA5
 SEEDS = (9100, 9200)
 EPS = 1e-6
 RESET = "fg_gemm_sched_reset"
-# the two GEMM forms whose first call per stream allocates and synchronises: the header's documented exception (the host queries
-# fg_*_bytes, fg_*_choice, fg_version, fg_gemm_debug_grid are bound outside hip._SIGNATURES and launch nothing)
+# the two GEMM forms whose first call per stream allocates and synchronises: the header's documented exception (the host queries,
+# hip._QUERIES, launch nothing)
 LEGACY_GEMMS = {"fg_gemm_epilogue_bf16", "fg_gemm_fp8_bf16"}
+# entry point -> "file::test" that holds its stream and capture checks, for the ones that have no case here
+ELSEWHERE = {
+    "fg_cfg_euler_dev_bf16": "test_graph_step.py::test_cfg_euler_dev_capture_and_replay",
+    "fg_attn_quant_qk_bf16": "test_attention_qk8.py::test_entry_points_only_enqueue_and_capture",
+    "fg_attn_fwd_qk8_bf16": "test_attention_qk8.py::test_entry_points_only_enqueue_and_capture",
+    "fg_rmsnorm_rope_q8_bf16": "test_attention_qk8_fused.py::test_entry_points_only_enqueue_and_capture",
+    "fg_rmsnorm_rope_kstats_bf16": "test_attention_qk8_fused.py::test_entry_points_only_enqueue_and_capture",
+    "fg_attn_quant_k_bf16": "test_attention_qk8_fused.py::test_entry_points_only_enqueue_and_capture",
+}
 CHILD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "stream_contract_child.py")
 
 
@@ -350,11 +360,15 @@ CHILD_CASES = ["lora_apply-g1-r32", "conv-w4-res", "conv-256p", "attn-w4-plain",
 
 
 def test_case_table_covers_the_abi():
-    """Every launching entry point has a case: a new one cannot be added without one."""
+    """Every launching entry point has a case, or a named test elsewhere: a new one cannot be added without either."""
     declared = set().union(*(c.reaches for c in CASES.values()))
-    launching = (set(_hip._SIGNATURES) | set(_hip._LOAD_TIME_SIGNATURES)) - LEGACY_GEMMS
+    assert set(ELSEWHERE) <= set(_hip._SIGNATURES)
+    launching = set(_hip._SIGNATURES) - LEGACY_GEMMS - set(ELSEWHERE)
     assert declared == launching, f"without a case: {sorted(launching - declared)}; unknown: {sorted(declared - launching)}"
-    assert not any(n.endswith("_bytes") or n in ("fg_version", "fg_attn_split_choice", "fg_conv_tile_choice", "fg_gemm_debug_grid") for n in declared)
+    for name, home in ELSEWHERE.items():
+        path, test = home.split("::")
+        assert f"\ndef {test}(" in open(os.path.join(os.path.dirname(CHILD), path)).read(), f"{name}: {home} does not exist"
+    assert not declared & set(_hip._QUERIES)
     assert set(CHILD_CASES) <= set(CASES) and set(SCRATCH_CASES) == {n for n, (*_, split) in ATTN.items() if split} | set(GEMM_SMOKE)
     assert os.path.exists(CHILD) and not os.path.basename(CHILD).startswith("test_")
 
