@@ -159,12 +159,18 @@ def _rows2d(t, who, cols="C"):
 class ModTable:
     """AdaLN modulation rows: tensor (mod_rows, K, C) bf16; vector j of row r = table[r, j].
 
-    mod_rows 1 (T2V), 2 (TI2V: tokens < first_rows use row 0) or N (per token)."""
+    mod_rows 1 (T2V), 2 (TI2V: tokens < first_rows use row 0) or N (per token).
 
-    def __init__(self, table, first_rows=0):
+    A table of TWO rows is always the TI2V split, also on a call of two token rows: that is the only two-row table the model builds
+    (wan_video_dit.py forward_tokens_steps: R = 1 or 2 distinct rows, and a token shard behind the first latent frame arrives with
+    first_rows = 0, both of its tokens on row 1).  per_token=True states the other meaning — row r of the call reads row r of the
+    table, which must then have as many rows as the call — and is what makes a two-row per-token table reach the kernels as
+    first_rows = 1 (rows [0, 1) on row 0, the rest on row 1: the same thing); first_rows is not used with it."""
+
+    def __init__(self, table, first_rows=0, per_token=False):
         _dev(table, "mod table")
         assert table.dim() == 3 and table.is_contiguous()
-        self.table, self.first_rows = table, int(first_rows)
+        self.table, self.first_rows, self.per_token = table, int(first_rows), bool(per_token)
         self.mod_rows, self.k, self.c = table.shape
         self.ld = self.k * self.c
 
@@ -173,6 +179,11 @@ class ModTable:
 
 
 def _mod_args(mod, rows):
+    """(mod_rows, first_rows, mod_ld) of a row-kernel launch on `rows` token rows (the rule of mod_rows == rows == 2: ModTable)."""
+    if mod.per_token:
+        if mod.mod_rows != rows:
+            raise HipLibraryError(f"per-token modulation table has {mod.mod_rows} rows; the call has {rows}")
+        return mod.mod_rows, (1 if rows == 2 else 0), mod.ld
     if mod.mod_rows not in (1, 2, rows):
         raise HipLibraryError(f"modulation table has {mod.mod_rows} rows; expected 1, 2 or {rows}")
     return mod.mod_rows, mod.first_rows, mod.ld
@@ -210,8 +221,8 @@ def gate_residual(x, y, mod=None, gate_idx=None, out=None):
 def _ln_modulate_args(who, x, mod, gate_idx, shift_idx, scale_idx, norm_mod):
     """(gate, shift, scale, affine flag, table args) of a residual + modulate(LN) launch."""
     norm_mod = mod if norm_mod is None else norm_mod
-    if (norm_mod.mod_rows, norm_mod.first_rows, norm_mod.ld) != (mod.mod_rows, mod.first_rows, mod.ld):
-        raise HipLibraryError(f"{who}: gate and norm tables must share rows / first_rows / ld")
+    if (norm_mod.mod_rows, norm_mod.first_rows, norm_mod.ld, norm_mod.per_token) != (mod.mod_rows, mod.first_rows, mod.ld, mod.per_token):
+        raise HipLibraryError(f"{who}: gate and norm tables must share rows / first_rows / ld / per_token")
     gate = mod.vec(gate_idx) if gate_idx is not None else None
     return gate, norm_mod.vec(shift_idx), norm_mod.vec(scale_idx), 0, _mod_args(mod, _rows(x, "x")[0])
 
@@ -464,8 +475,8 @@ def _gemm_mode(name, residual, mod, gate_idx, act, n):
     if act not in (None, "gelu_tanh") or (act is not None and residual):
         raise HipLibraryError(f"{name}: act must be None or 'gelu_tanh', and not combined with residual=True")
     if residual and mod is not None:
-        if mod.mod_rows not in (1, 2) or mod.c != n:
-            raise HipLibraryError(f"{name}: the gate table must have 1 or 2 rows of N values")
+        if mod.mod_rows not in (1, 2) or mod.c != n or mod.per_token:
+            raise HipLibraryError(f"{name}: the gate table must have 1 or 2 rows of N values (no per-token table)")
         return 2, mod.vec(gate_idx), mod.mod_rows, mod.ld, mod.first_rows
     return (3 if residual else 4 if act else 0), None, 1, n, 0
 
@@ -544,8 +555,8 @@ def lora_apply(x, a, b, out, groups=1, mode="add", mod=None, gate_idx=None):
         raise HipLibraryError(f"lora_apply: a {tuple(a.shape)} / b {tuple(b.shape)} do not fit x (.., {k}) -> out (.., {n}) in {groups} group(s)")
     gate, gate_rows, gate_ld, first = None, 1, n, 0
     if mode == "gate":
-        if mod is None or mod.mod_rows not in (1, 2) or mod.c != n:
-            raise HipLibraryError("lora_apply: mode 'gate' needs a ModTable of 1 or 2 rows of N values")
+        if mod is None or mod.mod_rows not in (1, 2) or mod.c != n or mod.per_token:
+            raise HipLibraryError("lora_apply: mode 'gate' needs a ModTable of 1 or 2 rows of N values (no per-token table)")
         gate, gate_rows, gate_ld, first = mod.vec(gate_idx), mod.mod_rows, mod.ld, mod.first_rows
     _call("fg_lora_apply_bf16", _ptr(x2), x2.stride(0), _ptr(a), _ptr(b), _ptr(o2), o2.stride(0), x2.shape[0], k, n // groups, r, groups,
           _LORA_MODES[mode], gate, gate_rows, gate_ld, first, _stream(x))

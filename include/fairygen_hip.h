@@ -62,7 +62,10 @@ const char* fg_last_error(void);         /* thread-local, valid until the next f
  * vector starts at ptr + r*mod_ld elements.  mod_rows==1: one row for all tokens (T2V mode);
  * mod_rows==2: tokens [0,first_rows) use row 0 and the rest row 1 (TI2V mode: first latent frame is at
  * t=0, pipelines/wan_video.py:1218-1228); mod_rows==rows: one row per token (the reference's literal
- * (1,N,6,C) layout). */
+ * (1,N,6,C) layout).  mod_rows == 2 ALWAYS means the split, also when rows == 2: a call on two token rows with a two-row table
+ * and first_rows == 0 reads table row 1 for both (a TI2V token shard behind the first latent frame).  A per-token table of two
+ * rows is the split with first_rows == 1, and a caller has to pass it so (fairygen_amd.hip.ModTable(per_token=True) does);
+ * first_rows in [0, rows], 0 and rows included.  Pinned by tests/test_row_kernel_shapes.py. */
 
 /* out = bf16(bf16(bf16(LN(x)) * bf16(1+scale)) + shift): nn.LayerNorm(elementwise_affine=False) followed by
  * modulate(), models/wan_video_dit.py:63-64,205-206,224,227 and Head.forward :261-268. */
