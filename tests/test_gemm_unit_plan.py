@@ -34,7 +34,8 @@ def build_sched(M, N, k_bytes, lda_bytes, nxcd=8, per=32, have_ws=True, gm=4):
     tiles_m, tiles_n = (M + 255) // 256, N // 256
     total = tiles_m * tiles_n
     nk = k_bytes // 128
-    ws = have_ws and nk >= 96
+    rounds = (total + nxcd * per - 1) // (nxcd * per)
+    ws = have_ws and (nk >= 96 or rounds <= 8)          # GemmCall::enqueue: long reductions, and short launches (at most 8 rounds per CU)
     gmtn = gm * tiles_n
     s = dict(a=0x1000_0000_0000, w=0x2000_0000_0000, c=0x3000_0000_0000, bias=0x4000_0000_0000, ws=0x5000_0000_0000, cursors=0, gate=0, scale=0,
              M=M, lda_bytes=lda_bytes, ldc_bytes=N * 2, k_bytes=k_bytes, nk=nk, tiles_m=tiles_m, tiles_n=tiles_n, gm=gm, gmtn=gmtn,
@@ -171,14 +172,30 @@ def program(tail):
     return [ln.replace("%=", "") for ln in E.lines]
 
 
-@pytest.mark.parametrize("M,N,k_bytes,nxcd,per", [
+PLAN_SHAPES = [
     (27280, 3072, 6144, 8, 32), (27280, 9216, 6144, 8, 32), (27280, 14336, 6144, 8, 32), (27280, 3072, 28672, 8, 32),     # the DiT shapes, bf16
     (3410, 3072, 6144, 8, 32), (3410, 3072, 28672, 8, 32), (6820, 14336, 3072, 8, 32),                                      # token shards (the last: e4m3)
     (700, 768, 512, 8, 32), (4200, 4096, 1024, 8, 32), (600, 3072, 28672, 8, 32), (66200, 256, 12288, 8, 32), (10500, 2048, 256, 8, 32),
-    (27280, 3072, 6144, 8, 38), (513, 256, 256, 1, 40)])                                                                   # other CU counts / one XCD
+    (27280, 3072, 6144, 8, 38), (513, 256, 256, 1, 40)]                                                                    # other CU counts / one XCD
+
+
+@pytest.mark.parametrize("M,N,k_bytes,nxcd,per", PLAN_SHAPES)
 def test_scalar_record_program_matches_the_plan(M, N, k_bytes, nxcd, per):
+    check_records(M, N, k_bytes, nxcd, per, True)
+
+
+@pytest.mark.parametrize("M,N,k_bytes,nxcd,per", PLAN_SHAPES)
+def test_scalar_record_program_matches_the_plan_without_a_workspace(M, N, k_bytes, nxcd, per):
+    """The same shapes as a caller without scratch runs them: column pieces (second body) or whole left-over tiles, never k-range pieces."""
+    s = check_records(M, N, k_bytes, nxcd, per, False)
+    assert all(pl["split"] == 1 for pl in s["plans"])
+
+
+def check_records(M, N, k_bytes, nxcd, per, have_ws):
+    """Every unit of both lists of every XCD: the record the scalar program makes is the one the Python plan names, the unit behind the
+    last one is refused, and the units cover every tile of the output exactly once.  Returns the GemmSched fields."""
     lda = k_bytes + 128
-    s, blob = build_sched(M, N, k_bytes, lda, nxcd=nxcd, per=per)
+    s, blob = build_sched(M, N, k_bytes, lda, nxcd=nxcd, per=per, have_ws=have_ws)
     R, XD, WD = G.S["REC"], G.S["XD"], G.S["WD"]
     seen = set()
     for tail in (False, True):
@@ -213,3 +230,4 @@ def test_scalar_record_program_matches_the_plan(M, N, k_bytes, nxcd, per):
             assert sum(p[1] >> 16 for p in parts) == s["nk"] and ks[0] == 0 and all(p[0] == 2 for p in parts)
         else:
             assert len(parts) == 4 and len({p[2] for p in parts}) == 4
+    return s

@@ -133,7 +133,8 @@ def test_fused_residual_norms(hip):
 
 
 @pytest.mark.parametrize("M,K,N", [(700, 256, 768),       # 9 tiles: every one a 64-column tail piece (second body, ring of 3)
-                                   (4200, 512, 4096),     # 272 tiles: one full round of 256-column tiles + cut tail, ragged last rows
+                                   (4200, 512, 4096),     # 272 tiles: one full round + 2 left-over tiles per XCD, each as 4 k-range pieces of 2 of its 8 k-steps (short launch: the
+                                                          # scratch is taken; their column-cut form: test_gemm_shapes.py, test_gemm_sched_state.py), ragged last rows
                                    (10500, 128, 2048),    # 336 tiles: left-over tiles NOT cut (10 per XCD), K = one step pair, 4 rows in the last row tile
                                    (3410, 3072, 3072)])   # the 1/8 token shard of the headline clip: 168 tiles on 256 CUs (o / cross-q / cross-o of config 4)
 def test_gemm_epilogue(hip, M, K, N):
