@@ -19,10 +19,12 @@ NEGATIVE = ("è‰²è°ƒè‰³ä¸½ï¼Œè¿‡æ›ï¼Œé™æ€ï¼Œç»†èŠ‚æ¨¡ç³Šä¸æ¸…ï¼Œå­—å¹•ï¼Œé£æ
             "ç”»å¾—ä¸å¥½çš„æ‰‹éƒ¨ï¼Œç”»å¾—ä¸å¥½çš„è„¸éƒ¨ï¼Œç•¸å½¢çš„ï¼Œæ¯å®¹çš„ï¼Œå½¢æ€ç•¸å½¢çš„è‚¢ä½“ï¼Œæ‰‹æŒ‡èåˆï¼Œé™æ­¢ä¸åŠ¨çš„ç”»é¢ï¼Œæ‚ä¹±çš„èƒŒæ™¯ï¼Œä¸‰æ¡è…¿ï¼ŒèƒŒæ™¯äººå¾ˆå¤šï¼Œå€’ç€èµ°")
 
 
-def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False):
+def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False):
     dit_cfg = dict(computation_dtype=torch.float8_e4m3fn) if fp8 else {}
-    if qk8:
+    if qk8 or pv8:
         dit_cfg["attention_dtype"] = torch.float8_e4m3fn
+    if pv8:
+        dit_cfg["attention_pv_dtype"] = torch.float8_e4m3fn
     pipe = WanVideoPipeline.from_pretrained(
         torch_dtype=torch.bfloat16, device="cuda",
         model_configs=[
@@ -47,8 +49,10 @@ def main():
     ap.add_argument("--fp8", action="store_true", help="the reference's fp8 Linear mode for the DiT blocks")
     ap.add_argument("--qk8-attention", action="store_true",
                     help="e4m3 Q K^T in the DiT's self-attention (the reference's sageattn branch); P V and cross-attention stay bf16")
+    ap.add_argument("--pv8-attention", action="store_true",
+                    help="... and e4m3 P V as well (both MFMAs of self-attention 8-bit); implies --qk8-attention")
     a = ap.parse_args()
-    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention)
+    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or a.pv8_attention, a.pv8_attention)
     image = Image.open(a.image).convert("RGB").resize((832, 480))
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     video = pipe(prompt=a.prompt, negative_prompt=NEGATIVE, input_image=image, num_frames=81, seed=1, tiled=True)

@@ -82,6 +82,23 @@ _QUERIES = {
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_QUERIES))      # what include/fairygen_hip.h declares
 
+# The extension of include/fairygen_hip_pv8.h (self-attention with the P V product on the e4m3 MFMA too): a second pair of tables, bound
+# and version-checked by load() next to the first; the main table, its header and ABI_VERSION do not change for it.
+PV8_ABI_VERSION = 1       # fg_attn_pv8_version
+_PV8_SIGNATURES = {
+    "fg_attn_quant_vt_bf16": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
+    "fg_attn_fwd_pv8_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _i64, _vp],
+}
+_PV8_QUERIES = {
+    "fg_attn_pv8_version": (_i32, []),
+    "fg_attn_pv8_scratch_bytes": (_i64, [_i64, _i32]),
+}
+PV8_SYMBOLS = sorted(list(_PV8_SIGNATURES) + list(_PV8_QUERIES))    # what include/fairygen_hip_pv8.h declares
+# Byte p of a 64-key tile of v8t holds key PV8_KEY_ORDER[p] of the tile: the order in which a lane of the attention kernel holds the
+# scores of its query row (lane half p >> 5, score sub-tile (p >> 4) & 1, accumulator register p & 15)
+PV8_KEY_ORDER = tuple(32 * ((p >> 4) & 1) + 8 * ((p & 15) >> 2) + 4 * (p >> 5) + (p & 3) for p in range(64))
+PV8_LOG2_C, PV8_DEFER_LOG2 = 5, 3     # P8 = e4m3(2^5 p), p <= 2^3 under the deferred rescale of the e4m3 P V form: 2^8 <= 448
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -101,12 +118,13 @@ def load():
             f"{_LIB_PATH} not found: build it with `make -C fairygen_amd/csrc` (or __graft_entry__.build()). "
             "fairygen_amd has no CPU / PyTorch fallback for its kernels.")
     lib = ctypes.CDLL(_LIB_PATH)
-    for name, argtypes in _SIGNATURES.items():
+    for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
-    for name, (restype, argtypes) in _QUERIES.items():
+    for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
-                                 ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)")):
+                                 ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
+                                 ("fg_attn_pv8_version", PV8_ABI_VERSION, " (e4m3 P V extension)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -694,10 +712,38 @@ def attn_quant_qk(q, k, num_heads, bufs=None):
     return bufs
 
 
-def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, workspace=None):
+def attention_pv8_scratch(n, num_heads, head_dim, device):
+    """The buffers fg_attn_quant_vt_bf16 fills for (n, num_heads * head_dim) v: (v8t (H, 128, n rounded up to 64) e4m3, sv (H, 128) fp32,
+    the statistics scratch)."""
+    if head_dim != 128:
+        raise HipLibraryError(f"attention_pv8_scratch: only head_dim 128 is supported (got {head_dim})")
+    need = load().fg_attn_pv8_scratch_bytes(n, num_heads)
+    if need < 0:
+        raise HipLibraryError(f"attention_pv8_scratch: {load().fg_last_error().decode()}")
+    return (torch.empty((num_heads, head_dim, (n + 63) // 64 * 64), dtype=torch.float8_e4m3fn, device=device),
+            torch.empty((num_heads, head_dim), dtype=torch.float32, device=device), torch.empty(need, dtype=torch.uint8, device=device))
+
+
+def attn_quant_vt(v, num_heads, bufs=None):
+    """The e4m3 V operand of the e4m3 P V form from v (1, N, H*128) bf16 (a column slice with a leading dimension is fine): one scale per
+    head and channel, the bytes transposed and tile-ordered by PV8_KEY_ORDER (include/fairygen_hip_pv8.h).  bufs: attention_pv8_scratch's."""
+    ldv = _ld_rows(v, "v")
+    b, n, hd = v.shape
+    if b != 1:
+        raise HipLibraryError(f"attn_quant_vt: v must be (1, N, H*D), got {tuple(v.shape)}")
+    bufs = attention_pv8_scratch(n, num_heads, hd // num_heads, v.device) if bufs is None else bufs
+    v8t, sv, scratch = bufs
+    if v8t.shape != (num_heads, hd // num_heads, (n + 63) // 64 * 64) or sv.shape != (num_heads, hd // num_heads) or not v8t.is_contiguous():
+        raise HipLibraryError("attn_quant_vt: bufs do not match (N, H*D)")
+    _call("fg_attn_quant_vt_bf16", _ptr(v), ldv, _ptr(v8t), _ptr(sv), _ptr(scratch), scratch.numel(), n, num_heads, hd // num_heads, _stream(v))
+    return bufs
+
+
+def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, workspace=None, pv8=False, pv8_bufs=None):
     """fg_attn_fwd_qk8_bf16 on operands that are quantised already (attn_quant_qk's, or the fused producers'): q8 (Nq, H*128), k8 (Nkv,
     H*128) e4m3, sq (Nq, H), sk (H), v (1, Nkv, H*128) bf16 -> (1, Nq, H*128); the model calls it with Nq = Nkv.  workspace as in
-    attention()."""
+    attention().  pv8: the P V product in e4m3 too — fg_attn_quant_vt_bf16 on v (into pv8_bufs: attention_pv8_scratch's tuple, else
+    allocated), then fg_attn_fwd_pv8_bf16."""
     ldv = _ld_rows(v, "v")
     b, nkv, hd = v.shape
     nq, d = q8.shape[0], hd // num_heads
@@ -705,19 +751,24 @@ def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, worksp
         raise HipLibraryError(f"attention_qk8_pre: one batch element, k8 and sk for v {tuple(v.shape)}, sq for q8 {tuple(q8.shape)}")
     out = torch.empty((b, nq, hd), dtype=v.dtype, device=v.device) if out is None else out
     ws, need = _attn_ws(v.device, 1, nq, nkv, num_heads, workspace)
+    if pv8:
+        v8t, sv, _ = attn_quant_vt(v, num_heads, pv8_bufs)
+        _call("fg_attn_fwd_pv8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
+              float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
+        return out
     _call("fg_attn_fwd_qk8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v), ldv, _ptr(out), nq, nkv, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
     return out
 
 
-def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs=None):
+def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs=None, pv8=False, pv8_bufs=None):
     """attention() for self-attention of one batch element with the e4m3 Q K^T product (the reference's sageattn branch,
     models/wan_video_dit.py:48-52): fg_attn_quant_qk_bf16, then fg_attn_fwd_qk8_bf16.  workspace as in attention(); bufs: the quantised
-    operands' buffers when the caller owns them (a captured step), else allocated per call."""
+    operands' buffers when the caller owns them (a captured step), else allocated per call.  pv8 / pv8_bufs: attention_qk8_pre's."""
     if v.shape != q.shape:
         raise HipLibraryError(f"attention_qk8: self-attention only, q, k, v of one shape (got v {tuple(v.shape)})")
     q8, k8, sq, sk, _ = attn_quant_qk(q, k, num_heads, bufs)
-    return attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=out, scale=scale, workspace=workspace)
+    return attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=out, scale=scale, workspace=workspace, pv8=pv8, pv8_bufs=pv8_bufs)
 
 
 def attention_qk8_fused_scratch(n, num_heads, head_dim, device):

@@ -35,6 +35,8 @@ class ModelConfig:
     computation_dtype: Optional[torch.dtype] = None
     # torch.float8_e4m3fn: the DiT's self-attention with the e4m3 Q K^T product (WanModel.enable_qk8_attention); None: bf16
     attention_dtype: Optional[torch.dtype] = None
+    # torch.float8_e4m3fn (with attention_dtype): the P V product of that self-attention in e4m3 too (enable_qk8_attention(pv8=True)); None: bf16
+    attention_pv_dtype: Optional[torch.dtype] = None
     clear_parameters: bool = False
 
     def check_input(self):
@@ -54,7 +56,8 @@ class ModelConfig:
     def vram_config(self):
         return {k: getattr(self, k) for k in (
             "offload_device", "offload_dtype", "onload_device", "onload_dtype",
-            "preparing_device", "preparing_dtype", "computation_device", "computation_dtype", "attention_dtype")}
+            "preparing_device", "preparing_dtype", "computation_device", "computation_dtype", "attention_dtype",
+            "attention_pv_dtype")}
 
 
 # --------------------------------------------------------------------------------- state-dict files
@@ -208,13 +211,21 @@ class ModelPool:
                 if not hasattr(model, "enable_fp8_linear"):
                     raise NotImplementedError(f"fp8 computation is only built for the DiT Linears, not for {cfg['model_name']}")
                 model.enable_fp8_linear(comp)
-            attn = vram_config.get("attention_dtype")
+            attn, attn_pv = vram_config.get("attention_dtype"), vram_config.get("attention_pv_dtype")
+            if attn_pv is not None:
+                if attn_pv != torch.float8_e4m3fn:
+                    raise NotImplementedError(f"attention_pv_dtype={attn_pv}: the 8-bit P V self-attention is built for torch.float8_e4m3fn only")
+                if attn is None:
+                    raise NotImplementedError("attention_pv_dtype without attention_dtype: the 8-bit P V product is built on the 8-bit Q K^T "
+                                              "self-attention (attention_dtype=torch.float8_e4m3fn)")
             if attn is not None:
                 if attn != torch.float8_e4m3fn:
                     raise NotImplementedError(f"attention_dtype={attn}: the 8-bit Q K^T self-attention is built for torch.float8_e4m3fn only")
                 if not hasattr(model, "enable_qk8_attention"):
                     raise NotImplementedError(f"attention_dtype is only built for the DiT's self-attention, not for {cfg['model_name']}")
                 model.enable_qk8_attention()
+                if attn_pv is not None:
+                    model.enable_qk8_attention(pv8=True)      # P V in e4m3 too
                 model.qk8_fused_producer = True      # the operands from the RMSNorm+RoPE pass itself: the same bits, k read once
             self.model.append(model)
             self.model_name.append(cfg["model_name"])

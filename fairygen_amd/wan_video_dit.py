@@ -213,8 +213,20 @@ class _BlockLinears:
             # the e4m3 Q K^T form (enable_qk8_attention); a captured step owns the quantised operands' buffers as it owns the split-KV scratch
             if self.owned is not None:
                 kw["bufs"] = self.qk8_bufs(q.shape[1], attn.num_heads, q.shape[2] // attn.num_heads, q.device, False)
-            return hip.attention_qk8(q, k, v, attn.num_heads, **kw)
+            return hip.attention_qk8(q, k, v, attn.num_heads, **kw, **self.pv8_kw(v, attn.num_heads))
         return attn(q, k, v, **kw)
+
+    def pv8_kw(self, v, num_heads):
+        """The pv8= / pv8_bufs= of the e4m3 attention call on v (1, N, H*D): nothing unless enable_qk8_attention(pv8=True); a captured step
+        owns v8t, sv and the statistics scratch next to the e4m3 q / k buffers."""
+        if not self.model.pv8_attention:
+            return {}
+        if self.owned is None:
+            return {"pv8": True}
+        key = (v.shape[1], num_heads, v.shape[2] // num_heads, v.device, "pv8")
+        if key not in self.owned.attn_qk8_bufs:
+            self.owned.attn_qk8_bufs[key] = hip.attention_pv8_scratch(*key[:4])
+        return {"pv8": True, "pv8_bufs": self.owned.attn_qk8_bufs[key]}
 
     def qk8_bufs(self, n, num_heads, head_dim, device, fused):
         """The e4m3 operands' buffers: a captured step's own, made once per shape (fused: with the key-statistics partials); None in an
@@ -239,7 +251,8 @@ class _BlockLinears:
         hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, q8=q8, sq=sq)
         hip.attn_quant_k(k, parts, nh, k8, sk, kbar)
         kw = {} if self.owned is None else {"workspace": self.owned.attn_workspace}
-        return hip.attention_qk8_pre(q8, k8, sq, sk, qkv[..., 2 * c:], nh, scale=scale, **kw)
+        v = qkv[..., 2 * c:]
+        return hip.attention_qk8_pre(q8, k8, sq, sk, v, nh, scale=scale, **kw, **self.pv8_kw(v, nh))
 
     def q8(self, a):
         return a.q8 if a.q8 is not None else hip.fp8_quant_rows(a.bf16, None)
@@ -468,6 +481,8 @@ class WanModel(nn.Module):
         self.qk8_attention = False
         # ... with its operands written by the RMSNorm+RoPE pass (True) or by the quantise pass behind it (False); the same bits
         self.qk8_fused_producer = False
+        # ... and with the P V product in e4m3 too (enable_qk8_attention(pv8=True)); False: P V in bf16
+        self.pv8_attention = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -504,7 +519,7 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ e4m3 Q K^T self-attention (models/wan_video_dit.py:48-52)
-    def enable_qk8_attention(self, flag=True, fused_producer=False):
+    def enable_qk8_attention(self, flag=True, fused_producer=False, pv8=False):
         """Run self-attention of every block like the reference's flash_attention does when the sageattention package is present
         (sageattn(q, k, v)): Q K^T from e4m3 operands — K mean-smoothed with one scale per head, Q with one scale per row and head
         (fg_attn_quant_qk_bf16) — on fg_attn_fwd_qk8_bf16; softmax and P V as before, v in bf16.  Only the stock AttentionModule of
@@ -514,9 +529,16 @@ class WanModel(nn.Module):
         fused_producer: the RMSNorm+RoPE pass itself writes the operands (fg_rmsnorm_rope_q8_bf16, fg_rmsnorm_rope_kstats_bf16,
         fg_attn_quant_k_bf16: q never exists as bf16, k is read once, not three times); False keeps the quantise pass behind the two
         norms, the form a plain call has always had and tests/test_attention_qk8.py pins to the oracle by its launches.  Both write the
-        same bytes, so the forward does not depend on it; ModelConfig(attention_dtype=...) asks for the fused producers."""
+        same bytes, so the forward does not depend on it; ModelConfig(attention_dtype=...) asks for the fused producers.
+        pv8: the other half of sageattn on current parts — P V on the e4m3 MFMA as well (include/fairygen_hip_pv8.h): v leaves
+        fg_attn_quant_vt_bf16 as e4m3 bytes, transposed, with one scale per head and channel, and fg_attn_fwd_pv8_bf16 takes the place of
+        fg_attn_fwd_qk8_bf16.  It is a form of this mode (it needs flag), has its routing, works behind either producer path and
+        composes with the same things; ModelConfig(attention_pv_dtype=...) asks for it."""
+        if pv8 and not flag:
+            raise ValueError("enable_qk8_attention(pv8=True) needs the e4m3 Q K^T mode on (flag=True)")
         self.qk8_attention = bool(flag)
         self.qk8_fused_producer = bool(flag) and bool(fused_producer)
+        self.pv8_attention = bool(flag) and bool(pv8)
         return self
 
     def check_qk8_layout(self, shard):

@@ -57,12 +57,16 @@ def main():
     ap.add_argument("--spike", action="store_true", help="also check an input that forces the deferred-rescale branch")
     ap.add_argument("--qk8", action="store_true", help="also time the e4m3 Q K^T form of the package's own library in the same rounds: "
                     "'qk8' = fg_attn_quant_qk_bf16 + fg_attn_fwd_qk8_bf16, 'qk8-attn' = the attention launch alone (nq == nkv)")
+    ap.add_argument("--pv8", action="store_true", help="implies --qk8; also time, in the same rounds, the form with the P V product in e4m3 too: "
+                    "'pv8' = fg_attn_quant_qk_bf16 + fg_attn_quant_vt_bf16 + fg_attn_fwd_pv8_bf16, 'pv8-attn' = the attention launch alone, "
+                    "and the quantise passes alone: 'quant-qk', 'quant-vt' (nq == nkv)")
     ap.add_argument("--qk8-fused", action="store_true", help="time the whole chain from the q | k | v buffer of the qkv GEMM to the attention "
                     "output (nq == nkv), in three forms: 'chain-bf16' = RMSNorm+RoPE of q and k + fg_attn_fwd_bf16 (the default path, its "
                     "pre-multiplied form), 'chain-qk8' = the same two norms + fg_attn_quant_qk_bf16 + fg_attn_fwd_qk8_bf16, 'chain-qk8-fused' = "
                     "the fused producers (fg_rmsnorm_rope_kstats_bf16, fg_rmsnorm_rope_q8_bf16, fg_attn_quant_k_bf16) + fg_attn_fwd_qk8_bf16; "
                     "and the producers of each form alone ('prod-*').  The two e4m3 chains are first checked to be the same bytes")
     a = ap.parse_args()
+    a.qk8 = a.qk8 or a.pv8
     dev = "cuda"
     g = torch.Generator(dev).manual_seed(0)
     c = a.heads * 128
@@ -126,6 +130,24 @@ def main():
             hip._call("fg_attn_fwd_qk8_bf16", *[hip._ptr(t) for t in bufs[:4]], hip._ptr(v), v.stride(1), hip._ptr(out), a.nq, a.nq, a.heads, 128,
                       128 ** -0.5, hip._ptr(wsb) if need else None, need, hip._stream(out))
         fns += [("qk8", lambda: hip.attention_qk8(q, k, v, a.heads, out=out, workspace=ws, bufs=bufs)), ("qk8-attn", attn_only)]
+    if a.pv8:
+        pv_bufs, ws_pv = hip.attention_pv8_scratch(a.nq, a.heads, 128, q.device), []
+
+        def pv8_attn_only():
+            hip._call("fg_attn_fwd_pv8_bf16", *[hip._ptr(t) for t in bufs[:4]], hip._ptr(pv_bufs[0]), hip._ptr(pv_bufs[1]), hip._ptr(out), a.nq, a.nq,
+                      a.heads, 128, 128 ** -0.5, hip._ptr(wsb) if need else None, need, hip._stream(out))
+
+        def pv8_chain():
+            hip.attention_qk8(q, k, v, a.heads, out=out, workspace=ws_pv, bufs=bufs, pv8=True, pv8_bufs=pv_bufs)
+        ref = reference(q, k, v)
+        for name, fn in (("qk8", fns[-2][1]), ("pv8", pv8_chain)):
+            out.zero_()
+            fn()
+            torch.cuda.synchronize()
+            err = (out[0, rows].float() - ref).abs()
+            print(f"check[random] {name}: max|out - ref_f32| = {err.max().item():.5f}, mean {err.mean().item():.6f}", flush=True)
+        fns += [("pv8", pv8_chain), ("pv8-attn", pv8_attn_only), ("quant-qk", lambda: hip.attn_quant_qk(q, k, a.heads, bufs)),
+                ("quant-vt", lambda: hip.attn_quant_vt(v, a.heads, pv_bufs))]
     if a.qk8_fused:
         n, nh = a.nq, a.heads
         qkv = rnd(1, n, 3 * c)
@@ -189,7 +211,7 @@ def main():
     for n, ts in times.items():
         ts = sorted(ts)
         med, mn = ts[len(ts) // 2], ts[0]
-        if n.startswith(("chain-", "prod-")):      # several launches: the mean and the spread of the repeated runs, no FLOP rate
+        if n.startswith(("chain-", "prod-", "quant-")):      # several launches: the mean and the spread of the repeated runs, no FLOP rate
             mean = sum(ts) / len(ts)
             sd = (sum((t - mean) ** 2 for t in ts) / max(len(ts) - 1, 1)) ** 0.5
             print(f"{n}: N={a.nq} H={a.heads}: mean {mean:.4f} ms, sd {sd:.4f}, median {med:.4f}, min {mn:.4f}, max {ts[-1]:.4f} ({len(ts)} runs)", flush=True)
