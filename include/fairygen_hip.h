@@ -315,8 +315,8 @@ int fg_conv3d_cl_bf16(const void* x, const void* w_packed, const void* bias,
                       const void* residual, void* out,
                       int T, int H, int W, int Cin, int Cout, int kt, int ks,
                       int resample, int time_interleave, fg_stream_t stream);
-/* Diagnostic: the tile variant fg_conv3d_cl_bf16 launches for an output of (T,H,W,Cout): 256 = conv3d_cl_256_kernel
- * (256x256x64 tile, LDS-DMA staging) when it fills the chip, else 128 = conv3d_cl_kernel (128x128x64). */
+/* Diagnostic: the tile variant fg_conv3d_cl_bf16 launches for an output of (T,H,W,Cout): 256 = conv3d_cl_w4_kernel or
+ * conv3d_cl_256p_kernel (256x256x64 tile, LDS-DMA staging) when it fills the chip, else 128 = conv3d_cl_kernel (128x128x64). */
 int fg_conv_tile_choice(int T, int H, int W, int Cout);
 
 /* out = main + DupUp3D(x): models/wan_video_vae.py:417-439,510-512.  x (T,H,W,Cin); main/out

@@ -16,7 +16,7 @@ Entry point, the instantiation or path each case reaches, and how that was confi
   fg_attn_quant_k_bf16          attn_k_finalise_kernel and attn_quant_k_kernel at h * 128 for h up to 31, P = 8 records.
   fg_attn_quant_qk_bf16         attn_k_stats_kernel and attn_quant_qk_kernel at 1, 5, 17, 32 heads against the CPU recipe (the yardstick
                      of the three above must itself be right at these widths), and at every width above as that yardstick.
-  fg_attn_fwd_qk8_bf16          attn_fwd_kernel<8, 1, false, true> at 3 heads (odd: bh % H, the XCD remap over 3 or 6 workgroups) on one
+  fg_attn_fwd_qk8_bf16          attn_fwd_kernel<true> at 3 heads (odd: bh % H, the XCD remap over 3 or 6 workgroups) on one
                      key, fewer keys than a tile, one full tile, a ragged second tile, Nq < 256, Nq = 2 x 256 + 1, Nkv = 1 024 and 1 025,
                      Nq != Nkv in both directions; every case without a workspace (direct workgroups only) and with the default one.
                      fg_attn_split_choice (asserted): (R, S) = (1, 2) for (64, 1 000), (256, 1 024), (70, 1 300) and (2, 2) for

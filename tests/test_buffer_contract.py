@@ -197,7 +197,7 @@ def _attn_data(nq, nkv, heads, seed):
 
 
 ATTN_CASES = [      # name, Nq, Nkv, heads, form, workspace, split expected for B = 2.  Nkv = 28 mod 64 (540, 1500; 1000 is 40 mod 64), Nq not a multiple of 256
-    ("short-kv", 300, 540, 2, "plain", True, False),                 # attn_fwd_kernel<8, 1, true> (Nkv <= 1024)
+    ("short-kv", 300, 540, 2, "plain", True, False),                 # attn_fwd_kernel<> (Nkv <= 1024)
     ("short-kv-split", 300, 1000, 8, "plain", True, True),           # ... its pieces + combine
     ("switch-1024", 300, 1024, 2, "plain", True, None),              # the last Nkv of the short-KV kernel
     ("switch-1025", 300, 1025, 2, "plain", True, None),              # the first of the 4-wave kernel: one key in the 17th tile

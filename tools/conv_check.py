@@ -1,4 +1,4 @@
-"""Correctness of fg_conv3d_cl_bf16 (whatever form FAIRYGEN_CONV_TILE selects) against an fp32 torch convolution on the device."""
+"""Correctness of fg_conv3d_cl_bf16 (every kernel its launcher selects among) against an fp32 torch convolution on the device."""
 import os, sys, itertools
 import torch
 import torch.nn.functional as F
