@@ -35,6 +35,9 @@ def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=Fals
         tokenizer_config=ModelConfig(path=tokenizer))
     if lora:
         pipe.load_lora(pipe.dit, lora, alpha=1)
+    if (qk8 or pv8) and getattr(pipe, "parallel", None) is not None:
+        # a token-sharded layout: the e4m3 mode with its statistics exchange (off by default; no multi-GPU hardware run exists)
+        pipe.dit.enable_qk8_attention(fused_producer=pipe.dit.qk8_fused_producer, pv8=pv8, sharded=True)
     return pipe
 
 

@@ -15,54 +15,11 @@
 #include "common.h"
 #include "../../include/fairygen_hip_pv8.h"
 #include "attn_qk8_quant.h"
+#include "attn_pv8_parts.h"
 
 namespace {
 
-constexpr int kTileKeys = 64;
-constexpr int kMaxParts = 256, kMaxTileBlocks = 32;
-
-// records per channel: a function of the key count alone, 16 rows a workgroup until one workgroup per CU is reached
-inline int64_t stat_parts(int64_t n) {
-    const int64_t p = (n + 15) / 16;
-    return p > kMaxParts ? kMaxParts : p;
-}
-
-// Dword (4 keys) d of a tile's 16 holds the keys 4 kg .. 4 kg + 3 with d = kPv8Dword(kg): MFMA k index 32 hh + 16 sub + j stands for key
-// 32 sub + 8 (j >> 2) + 4 hh + (j & 3), so keys 4 kg + (0..3) (sub = kg >> 3, j >> 2 = (kg >> 1) & 3, hh = kg & 1) are bytes 4 d + (0..3)
-__device__ __forceinline__ int pv8_dword(int kg) { return 8 * (kg & 1) + 4 * (kg >> 3) + ((kg >> 1) & 3); }
-
-// Workgroup (x, y) of 4 waves: lane l owns the 8 channels of 16-byte chunk 64 y + l; wave w walks the rows 4 x + w + 4 gridDim.x i.
-__global__ __launch_bounds__(256) void attn_v_stats_kernel(const bf16* __restrict__ v, int64_t ldv, float* __restrict__ rec, int64_t N, int C) {
-    __shared__ float amax_s[3][8][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int chunk = blockIdx.y * 64 + lane;
-    const bool live = chunk * 8 < C;
-    float amax[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) amax[j] = 0.f;
-    if (live) {
-        for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < N; row += (int64_t)gridDim.x * 4) {
-            const bf16x8 x = *reinterpret_cast<const bf16x8*>(v + row * ldv + (int64_t)chunk * 8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) amax[j] = fmaxf(amax[j], fabsf((float)x[j]));
-        }
-    }
-    if (wave > 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) amax_s[wave - 1][j][lane] = amax[j];
-    }
-    __syncthreads();
-    if (wave > 0 || !live) return;
-    f32x4 lo, hi;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float a = fmaxf(fmaxf(amax[j], amax_s[0][j][lane]), fmaxf(amax_s[1][j][lane], amax_s[2][j][lane]));
-        if (j < 4) lo[j] = a; else hi[j - 4] = a;
-    }
-    float* o = rec + (int64_t)blockIdx.x * C + (int64_t)chunk * 8;
-    *reinterpret_cast<f32x4*>(o) = lo;
-    *reinterpret_cast<f32x4*>(o + 4) = hi;
-}
+constexpr int kMaxTileBlocks = 32;
 
 // Workgroup (x, h) of 256: the scales of head h from the `parts` records, then the tiles x, x + gridDim.x, ..  Thread t converts the 8
 // channels of chunk cl = t & 15 of the 4 keys 4 kg .. 4 kg + 3, kg = t >> 4: 8 dwords, one per channel, to row 8 cl + j of the image at
@@ -107,21 +64,7 @@ __global__ __launch_bounds__(256) void attn_quant_vt_kernel(const bf16* __restri
         for (int j = 0; j < 8; ++j)
             img[cl * 8 + j][wr] = cvt2_e4m3(f[0][j] / s[j], f[1][j] / s[j]) | (cvt2_e4m3(f[2][j] / s[j], f[3][j] / s[j]) << 16);
         __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int idx = tid + 256 * i, ch = idx >> 2, q = idx & 3, x = ch >> 3;      // x: the chunk cl that wrote row ch
-            const u32x4 rd = *reinterpret_cast<const u32x4*>(&img[ch][4 * (q ^ (x >> 2))]);
-            u32x4 w;      // logical dword d of the chunk sits at d ^ (x & 3)
-            w[0] = (x & 1) ? rd[1] : rd[0];
-            w[1] = (x & 1) ? rd[0] : rd[1];
-            w[2] = (x & 1) ? rd[3] : rd[2];
-            w[3] = (x & 1) ? rd[2] : rd[3];
-            if (x & 2) {
-                const uint32_t a = w[0], b = w[1];
-                w[0] = w[2]; w[1] = w[3]; w[2] = a; w[3] = b;
-            }
-            *reinterpret_cast<u32x4*>(v8t + ((int64_t)h * kD + ch) * Nkp + t * kTileKeys + q * 16) = w;
-        }
+        pv8_store_tile(img, v8t, h, Nkp, t, tid);
         __syncthreads();
     }
 }
@@ -135,7 +78,7 @@ extern "C" int64_t fg_attn_pv8_scratch_bytes(int64_t N, int H) {
         fg_set_error("fg_attn_pv8_scratch_bytes: N must be positive, H in 1..65535 (got N=%lld H=%d)", (long long)N, H);
         return -1;
     }
-    return stat_parts(N) * H * kD * 4;
+    return v_stat_parts(N) * H * kD * 4;
 }
 
 extern "C" int fg_attn_quant_vt_bf16(const void* v, int64_t ldv, void* v8t, float* sv, void* scratch, int64_t scratch_bytes, int64_t N, int H,
@@ -147,7 +90,7 @@ extern "C" int fg_attn_quant_vt_bf16(const void* v, int64_t ldv, void* v8t, floa
     FG_CHECK_ARG(ldv >= hd && ldv % 8 == 0, "fg_attn_quant_vt_bf16: ldv must be >= H*D and a multiple of 8");
     FG_CHECK_ARG(FG_ALIGNED16(v) && FG_ALIGNED16(v8t) && FG_ALIGNED16(sv) && FG_ALIGNED16(scratch),
                  "fg_attn_quant_vt_bf16: v, v8t, sv and scratch must be 16-byte aligned");
-    const int64_t parts = stat_parts(N);
+    const int64_t parts = v_stat_parts(N);
     FG_CHECK_ARG(scratch_bytes >= parts * hd * 4, "fg_attn_quant_vt_bf16: scratch must hold %lld bytes (got %lld)", (long long)(parts * hd * 4),
                  (long long)scratch_bytes);
     hipLaunchKernelGGL(attn_v_stats_kernel, dim3((unsigned)parts, (unsigned)((hd / 8 + 63) / 64)), dim3(256), 0, (hipStream_t)stream, (const bf16*)v,

@@ -99,6 +99,20 @@ PV8_SYMBOLS = sorted(list(_PV8_SIGNATURES) + list(_PV8_QUERIES))    # what inclu
 PV8_KEY_ORDER = tuple(32 * ((p >> 4) & 1) + 8 * ((p & 15) >> 2) + 4 * (p >> 5) + (p & 3) for p in range(64))
 PV8_LOG2_C, PV8_DEFER_LOG2 = 5, 3     # P8 = e4m3(2^5 p), p <= 2^3 under the deferred rescale of the e4m3 P V form: 2^8 <= 448
 
+# The extension of include/fairygen_hip_shard8.h (the e4m3 operands of a token shard whose K / V are all-gathered): a third pair of tables.
+SHARD8_ABI_VERSION = 1    # fg_attn_shard8_version
+_SHARD8_SIGNATURES = {
+    "fg_attn_shard8_stats": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp],
+    "fg_attn_shard8_quant": [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
+    "fg_attn_shard8_vt": [_vp, _vp, _i64, _i32, _i32, _vp],
+}
+_SHARD8_QUERIES = {
+    "fg_attn_shard8_version": (_i32, []),
+    "fg_attn_shard8_record_bytes": (_i64, [_i32]),
+    "fg_attn_shard8_scratch_bytes": (_i64, [_i64, _i32]),
+}
+SHARD8_SYMBOLS = sorted(list(_SHARD8_SIGNATURES) + list(_SHARD8_QUERIES))    # what include/fairygen_hip_shard8.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -118,13 +132,14 @@ def load():
             f"{_LIB_PATH} not found: build it with `make -C fairygen_amd/csrc` (or __graft_entry__.build()). "
             "fairygen_amd has no CPU / PyTorch fallback for its kernels.")
     lib = ctypes.CDLL(_LIB_PATH)
-    for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()):
+    for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
-    for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()):
+    for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
-                                 ("fg_attn_pv8_version", PV8_ABI_VERSION, " (e4m3 P V extension)")):
+                                 ("fg_attn_pv8_version", PV8_ABI_VERSION, " (e4m3 P V extension)"),
+                                 ("fg_attn_shard8_version", SHARD8_ABI_VERSION, " (e4m3 operands of a token shard)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -759,6 +774,95 @@ def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, worksp
     _call("fg_attn_fwd_qk8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v), ldv, _ptr(out), nq, nkv, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
     return out
+
+
+def attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None, workspace=None):
+    """fg_attn_fwd_pv8_bf16 on operands that are ALL ready: q8 (Nq, H*128), k8 (Nkv, H*128) e4m3, sq (Nq, H), sk (H), v8t (H, 128, Nkv
+    rounded up to 64) e4m3 and sv (H, 128) as attn_quant_vt or attn_shard8_vt left them -> (1, Nq, H*128) bf16.  Nq need not be Nkv (a
+    token shard's queries against all keys).  workspace as in attention()."""
+    (nq, hd), nkv = q8.shape, k8.shape[0]
+    d = hd // num_heads
+    if k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads or sv.numel() != hd or not v8t.is_contiguous() or \
+            v8t.shape != (num_heads, d, (nkv + 63) // 64 * 64):
+        raise HipLibraryError(f"attention_pv8_pre: k8, sq, sk, v8t, sv do not match q8 {tuple(q8.shape)} and {nkv} keys")
+    out = torch.empty((1, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
+    ws, need = _attn_ws(q8.device, 1, nq, nkv, num_heads, workspace)
+    _call("fg_attn_fwd_pv8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
+          float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q8))
+    return out
+
+
+# ---- the e4m3 operands of a token shard (include/fairygen_hip_shard8.h)
+def attn_shard8_record_bytes(c):
+    need = load().fg_attn_shard8_record_bytes(c)
+    if need < 0:
+        raise HipLibraryError(f"attn_shard8_record_bytes: {load().fg_last_error().decode()}")
+    return need
+
+
+def attn_shard8_neutral_record(c, device):
+    """The record of a rank without rows (sum 0, minimum +inf, maximum -inf, |v| maximum 0) as (20 * c,) uint8 on `device`."""
+    rec = torch.zeros(attn_shard8_record_bytes(c), dtype=torch.uint8)
+    rec[8 * c:12 * c].view(torch.float32).fill_(float("inf"))
+    rec[12 * c:16 * c].view(torch.float32).fill_(float("-inf"))
+    return rec.to(device)
+
+
+def attn_shard8_stats(partials, rows, num_heads, v=None, record=None):
+    """This rank's statistics record from rmsnorm_rope_kstats's partials of its `rows` local k rows and, for the e4m3 P V form, its v
+    (1, rows, H*128) bf16 (a column slice is fine; None: the |v| maxima are written as 0) -> (20 * H * 128,) uint8."""
+    c = num_heads * 128
+    _dev(partials, "partials", torch.uint8)
+    record = torch.empty(attn_shard8_record_bytes(c), dtype=torch.uint8, device=partials.device) if record is None else record
+    scratch, ldv = None, 0
+    if v is not None:
+        ldv = _ld_rows(v, "v")
+        if v.shape != (1, rows, c):
+            raise HipLibraryError(f"attn_shard8_stats: v must be (1, {rows}, {c}), got {tuple(v.shape)}")
+        scratch = torch.empty(load().fg_attn_shard8_scratch_bytes(rows, c), dtype=torch.uint8, device=v.device)
+    _call("fg_attn_shard8_stats", _ptr(partials), partials.numel(), _ptr(v), ldv, _ptr(record), record.numel(), _ptr(scratch),
+          scratch.numel() if scratch is not None else 0, rows, num_heads, 128, _stream(partials))
+    return record
+
+
+def attn_shard8_quant(records, n, k, num_heads, v=None, k8=None, v8=None):
+    """The gathered records (W, 20 * H * 128) uint8 and the key count n of all ranks -> the scales every rank agrees on, and this rank's
+    rows converted: k (1, rows, H*128) bf16 -> k8 (rows, H*128) e4m3; v likewise -> v8 ROW-MAJOR (None without v).  Returns (k8, v8, sk
+    (H), kbar (H*128), sv (H, 128) or None)."""
+    ldk = _ld_rows(k, "k")
+    b, rows, hd = k.shape
+    _dev(records, "records", torch.uint8)
+    if b != 1 or hd != num_heads * 128 or records.dim() != 2 or not records.is_contiguous():
+        raise HipLibraryError(f"attn_shard8_quant: k must be (1, rows, H*128) and records (W, 20*H*128), got {tuple(k.shape)}, {tuple(records.shape)}")
+    f8 = torch.float8_e4m3fn
+    k8 = torch.empty((rows, hd), dtype=f8, device=k.device) if k8 is None else k8
+    sk, kbar = torch.empty(num_heads, dtype=torch.float32, device=k.device), torch.empty(hd, dtype=torch.float32, device=k.device)
+    sv, ldv = None, 0
+    if v is not None:
+        ldv = _ld_rows(v, "v")
+        v8 = torch.empty((rows, hd), dtype=f8, device=k.device) if v8 is None else v8
+        sv = torch.empty((num_heads, 128), dtype=torch.float32, device=k.device)
+        if v.shape != k.shape or v8.shape != (rows, hd) or not v8.is_contiguous():
+            raise HipLibraryError("attn_shard8_quant: v and v8 must match k")
+    if k8.shape != (rows, hd) or not k8.is_contiguous():
+        raise HipLibraryError("attn_shard8_quant: k8 must be (rows, H*128) contiguous")
+    _call("fg_attn_shard8_quant", _ptr(records), records.numel(), records.shape[0], n, _ptr(k), ldk, _ptr(v), ldv, _ptr(k8),
+          _ptr(v8) if v is not None else None, _ptr(sk), _ptr(kbar), _ptr(sv), rows, num_heads, 128, _stream(k))
+    return k8, (v8 if v is not None else None), sk, kbar, sv
+
+
+def attn_shard8_vt(v8, num_heads, v8t=None):
+    """The gathered v8 (N, H*128) row-major e4m3 -> v8t (H, 128, N rounded up to 64) in the tile order of PV8_KEY_ORDER, padding zero."""
+    if v8.dtype not in (torch.float8_e4m3fn, torch.uint8) or v8.device.type != "cuda" or v8.dim() != 2 or not v8.is_contiguous() or \
+            v8.shape[1] != num_heads * 128:
+        raise HipLibraryError("attn_shard8_vt: v8 must be a contiguous (N, H*128) e4m3 tensor on a HIP device")
+    n = v8.shape[0]
+    shape = (num_heads, 128, (n + 63) // 64 * 64)
+    v8t = torch.empty(shape, dtype=torch.float8_e4m3fn, device=v8.device) if v8t is None else v8t
+    if v8t.shape != shape or not v8t.is_contiguous():
+        raise HipLibraryError(f"attn_shard8_vt: v8t must be {shape} contiguous")
+    _call("fg_attn_shard8_vt", _ptr(v8), _ptr(v8t), n, num_heads, 128, _stream(v8))
+    return v8t
 
 
 def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs=None, pv8=False, pv8_bufs=None):

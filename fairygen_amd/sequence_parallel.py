@@ -8,6 +8,9 @@ the exact "halo" of a temporal shard is the whole sequence; two
 
 * ``attn_mode="allgather"``: K and V (after RMSNorm+RoPE) are all-gathered once per layer (2 collectives, 7/8 of
   2·N·3072·2 B received per rank: 293 MB at N = 27 280, P = 8); attention = local queries x all keys, all heads.
+  With ``WanModel.enable_qk8_attention(sharded=True)`` (opt-in) one small record per rank is all-gathered first
+  (``all_gather_records_async``: 20·C bytes of key / value statistics) and K / V travel as e4m3 bytes: 220 MB (k8 + bf16 v)
+  or 147 MB (k8 + v8) by the same arithmetic — not a measurement, no multi-GPU run exists.
 * ``attn_mode="ulysses"`` (what xfuser does, :125-146): one all-to-all turns the token shard of q/k/v into a
   head shard (all N tokens, 24/P heads), attention runs per head group over the whole sequence, a second
   all-to-all brings the output back (2 collectives, 4·(N/P)·3072·2 B·(P-1)/P sent per rank: 73 MB at P = 8 —
@@ -110,6 +113,12 @@ class TokenShard:
         and wait() — in the pipeline: the other CFG branch's GEMMs / attention — overlaps the xGMI transfer."""
         return _PendingKV(self, k, v, n)
 
+    def all_gather_records_async(self, record):
+        """Start the all-gather of one small fixed-size record per rank (the key / value statistics of the e4m3 attention on a token shard:
+        20 * C bytes, include/fairygen_hip_shard8.h); `.wait()` -> (world, record.numel()) in rank order, this rank's own included.
+        Staged through the host on a backend without device collectives, like all_gather_kv_async."""
+        return _PendingRecords(self, record)
+
     def all_gather_tokens(self, x, n):
         """x (1, n_local, C) -> (1, N, C) (final head all-gather, wan_video.py:1379-1382)."""
         if not self.active:
@@ -206,6 +215,27 @@ class _PendingKV:
         for w in self.works:
             w.wait()
         return self.kf[: self.n].unsqueeze(0), self.vf[: self.n].unsqueeze(0)
+
+
+class _PendingRecords:
+    def __init__(self, shard, record):
+        self.work, self._send = None, record.contiguous().view(-1)
+        if not shard.active:
+            self.full = self._send.unsqueeze(0)
+            return
+        flat = torch.empty(shard.world_size * self._send.numel(), dtype=record.dtype, device=record.device)
+        self.full = flat.view(shard.world_size, -1)
+        if _staged(record, shard.group):      # single-GPU rehearsal backend: synchronous, through the host
+            host = torch.empty(flat.shape, dtype=record.dtype)
+            dist.all_gather_into_tensor(host, self._send.cpu(), group=shard.group)
+            flat.copy_(host)
+        else:
+            self.work = dist.all_gather_into_tensor(flat, self._send, group=shard.group, async_op=True)
+
+    def wait(self):
+        if self.work is not None:
+            self.work.wait()
+        return self.full
 
 
 def _all_to_all_rows(shard, send, recv):

@@ -483,6 +483,8 @@ class WanModel(nn.Module):
         self.qk8_fused_producer = False
         # ... and with the P V product in e4m3 too (enable_qk8_attention(pv8=True)); False: P V in bf16
         self.pv8_attention = False
+        # ... and on token-sharded layouts (enable_qk8_attention(sharded=True)); False: an active shard raises
+        self.qk8_sharded = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -519,13 +521,13 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ e4m3 Q K^T self-attention (models/wan_video_dit.py:48-52)
-    def enable_qk8_attention(self, flag=True, fused_producer=False, pv8=False):
+    def enable_qk8_attention(self, flag=True, fused_producer=False, pv8=False, sharded=False):
         """Run self-attention of every block like the reference's flash_attention does when the sageattention package is present
         (sageattn(q, k, v)): Q K^T from e4m3 operands — K mean-smoothed with one scale per head, Q with one scale per row and head
         (fg_attn_quant_qk_bf16) — on fg_attn_fwd_qk8_bf16; softmax and P V as before, v in bf16.  Only the stock AttentionModule of
         self-attention over more than QK8_MIN_KV keys takes it; cross-attention (512 keys, 1.9 % of the attention FLOPs) stays bf16.
         q is then rounded as the reference rounds it (attn_scale: no factor folded into its RoPE table).  Composes with
-        enable_fp8_linear, hot adapters and graph=True; token-sharded layouts raise (kbar and sk would need a collective).
+        enable_fp8_linear, hot adapters and graph=True; token-sharded layouts raise unless sharded=True (below).
         fused_producer: the RMSNorm+RoPE pass itself writes the operands (fg_rmsnorm_rope_q8_bf16, fg_rmsnorm_rope_kstats_bf16,
         fg_attn_quant_k_bf16: q never exists as bf16, k is read once, not three times); False keeps the quantise pass behind the two
         norms, the form a plain call has always had and tests/test_attention_qk8.py pins to the oracle by its launches.  Both write the
@@ -533,18 +535,32 @@ class WanModel(nn.Module):
         pv8: the other half of sageattn on current parts — P V on the e4m3 MFMA as well (include/fairygen_hip_pv8.h): v leaves
         fg_attn_quant_vt_bf16 as e4m3 bytes, transposed, with one scale per head and channel, and fg_attn_fwd_pv8_bf16 takes the place of
         fg_attn_fwd_qk8_bf16.  It is a form of this mode (it needs flag), has its routing, works behind either producer path and
-        composes with the same things; ModelConfig(attention_pv_dtype=...) asks for it."""
+        composes with the same things; ModelConfig(attention_pv_dtype=...) asks for it.
+        sharded: off by default, and then an active token shard raises.  True lets the mode (either form) run on a token-sharded layout
+        whose total key count exceeds QK8_MIN_KV; a shorter sequence keeps the bf16 sharded path.  attn_mode="ulysses": a rank holds all N
+        tokens of its heads behind the first all-to-all, every statistic is local, and the received views go through attention_qk8.
+        attn_mode="allgather" (include/fairygen_hip_shard8.h): each rank reduces its rows to one record per block (per channel the fp64 key
+        sum, the key minimum and maximum, the maximum of |v|: 20 * C bytes), the records are all-gathered, every rank derives the same key
+        mean, sk and sv from them, and the K / V all-gather moves the e4m3 bytes (k8; with pv8 also v8) in place of bf16.  For any split
+        of the rows the gathered operands and the scales are byte for byte those of the unsharded mode, where the fp64 key sum is exact
+        (include/fairygen_hip.h); the attention kernels are the same.  Composes with enable_fp8_linear, hot adapters and cfg_parallel=2 (the
+        shard is then the half-group); graph=True with a shard raises as before; attn_mode="windows" has no exchange in a forward and
+        is not affected.  No multi-GPU hardware run of this project exists: the mode is tested with emulated ranks on one GPU."""
         if pv8 and not flag:
             raise ValueError("enable_qk8_attention(pv8=True) needs the e4m3 Q K^T mode on (flag=True)")
+        if sharded and not flag:
+            raise ValueError("enable_qk8_attention(sharded=True) needs the e4m3 Q K^T mode on (flag=True)")
         self.qk8_attention = bool(flag)
         self.qk8_fused_producer = bool(flag) and bool(fused_producer)
         self.pv8_attention = bool(flag) and bool(pv8)
+        self.qk8_sharded = bool(flag) and bool(sharded)
         return self
 
     def check_qk8_layout(self, shard):
-        if self.qk8_attention and shard is not None and shard.active:
+        if self.qk8_attention and not self.qk8_sharded and shard is not None and shard.active:
             raise NotImplementedError("enable_qk8_attention() with a token-sharded layout: the key mean and the per-head key scale of the e4m3 "
-                                      "Q K^T form span all ranks' tokens and would need a collective")
+                                      "Q K^T form span all ranks' tokens and would need a collective; enable_qk8_attention(sharded=True) "
+                                      "runs that exchange")
 
     def _scaled_linear(self, xq, scale_a, w8, bias, **state):
         """fp8_linear's matmul (:347-354: torch._scaled_mm with row-wise scale_a, unit scale_b, bf16 bias, bf16 out): on this repo's e4m3
@@ -765,11 +781,17 @@ class WanModel(nn.Module):
             yield i
             qg, kg, vg = pending.wait()
             o_full = shard.ulysses_out_buffer(shard_total, g, qkv)
-            hip.attention(qg, kg, vg, shard.heads_local(nh), out=o_full[:shard_total].unsqueeze(0), scale=scale)
+            if takes_qk8_attention(self, sa.attn, shard_total, qkv.shape[0]):      # all N tokens of this rank's heads: every statistic is local
+                hip.attention_qk8(qg, kg, vg, shard.heads_local(nh), out=o_full[:shard_total].unsqueeze(0), scale=scale,
+                                  pv8=self.pv8_attention)
+            else:
+                hip.attention(qg, kg, vg, shard.heads_local(nh), out=o_full[:shard_total].unsqueeze(0), scale=scale)
             pending = shard.ulysses_out_async(o_full, shard_total, n_loc)
             yield i
             a = torch.empty((1, n_loc, c), dtype=qkv.dtype, device=qkv.device)
             hip.copy_groups(pending.wait_blocks().view(-1), size * g, g, a.view(-1), g, c, p_, n_loc, g)
+        elif takes_qk8_attention(self, sa.attn, shard_total, qkv.shape[0]):
+            a = yield from self._shard8_attention_steps(i, sa, qkv, rq, rk, scale, shard, shard_total)
         else:
             k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
             pending = shard.all_gather_kv_async(k, v, shard_total)
@@ -779,6 +801,39 @@ class WanModel(nn.Module):
             a = sa.attn(q, k, v) if scale is None else sa.attn(q, k, v, scale=scale)
         # x += gate_msa*y ; h = norm3(x)  (reference :225-226)
         return lin.residual(x, a, f"blocks.{i}.self_attn.o", sa.o.weight, sa.o.bias, w8[1], mod, 2, affine=blk.norm3)
+
+    def _shard8_attention_steps(self, i, sa, qkv, rq, rk, scale, shard, shard_total):
+        """Block i's self-attention in the e4m3 form on the K / V all-gather layout (enable_qk8_attention(sharded=True),
+        include/fairygen_hip_shard8.h): this rank's queries against all N keys.  Two exchanges, a yield after each has been started: the
+        ranks' statistics records (20 * C bytes each), from which every rank derives the unsharded key mean, sk and sv; then k8 and v (with
+        pv8: v8) through all_gather_kv_async, as uint8 views.  A rank without rows launches nothing and sends the neutral record."""
+        c, nh, eps, pv8 = self.dim, self.num_heads, self.eps, self.pv8_attention
+        n_loc, dev = qkv.shape[1], qkv.device
+        v = qkv[..., 2 * c:]
+        if n_loc:
+            k, parts = hip.rmsnorm_rope_kstats(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
+            record = hip.attn_shard8_stats(parts, n_loc, nh, v if pv8 else None)
+        else:
+            record = hip.attn_shard8_neutral_record(c, dev)
+        pending = shard.all_gather_records_async(record)
+        yield i
+        if n_loc:
+            q8, sq = hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)      # overlaps the record exchange
+            k8, v8, sk, _, sv = hip.attn_shard8_quant(pending.wait(), shard_total, k, nh, v if pv8 else None)
+            k8, v_send = k8.view(torch.uint8), (v8.view(torch.uint8) if pv8 else v[0])
+        else:
+            pending.wait()
+            k8 = torch.empty((0, c), dtype=torch.uint8, device=dev)
+            v_send = k8 if pv8 else v[0]
+        pending = shard.all_gather_kv_async(k8.unsqueeze(0), v_send.unsqueeze(0), shard_total)
+        yield i
+        k8f, vf = pending.wait()
+        if not n_loc:
+            return torch.empty((1, 0, c), dtype=qkv.dtype, device=dev)
+        k8f = k8f[0].view(torch.float8_e4m3fn)
+        if pv8:
+            return hip.attention_pv8_pre(q8, k8f, sq, sk, hip.attn_shard8_vt(vf[0].contiguous(), nh), sv, nh, scale=scale)
+        return hip.attention_qk8_pre(q8, k8f, sq, sk, vf, nh, scale=scale)
 
     # ------------------------------------------------------------------ the 30-block token forward
     def forward_tokens(self, x, context, mod_rows_t, t_rows, first_rows, rope, shard=None, shard_total=None, tea_cache=None,

@@ -44,8 +44,75 @@ def runner(lib, q, k, v, heads, out):
     return fn
 
 
+def shard8(a):
+    """--shard8: one rank's attention chain of the K / V all-gather layout, from its rows of the q | k | v buffer to its attention output, at
+    nq = ceil(nkv / world) local rows against nkv keys: 'chain-bf16' (RMSNorm+RoPE x 2, gather of k and v, fg_attn_fwd_bf16), 'chain-qk8-sharded'
+    and 'chain-pv8-sharded' (enable_qk8_attention(sharded=True): key statistics, record, e4m3 q, quantise, gather of the e4m3 bytes, the
+    transpose pass, the e4m3 attention).  ONE process, ONE GPU: local copies of the same size stand in for the collectives, so nothing here
+    says anything about xGMI.  Then the HBM-bound passes alone with their achieved GB/s, beside fg_attn_quant_vt_bf16 on the same rows."""
+    dev, heads, n = "cuda", a.heads, a.nkv
+    c, nl = heads * 128, -(-a.nkv // a.world)
+    g = torch.Generator(dev).manual_seed(0)
+    qkv = torch.randn((1, nl, 3 * c), generator=g, device=dev).to(torch.bfloat16)
+    w = torch.ones(c, dtype=torch.bfloat16, device=dev)
+    ang = torch.rand((nl, 64), generator=g, device=dev, dtype=torch.float64) * 6.283
+    tab = torch.stack([ang.cos(), ang.sin()], -1).float().contiguous()
+    qs, ks, vs = qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:]
+    out = torch.empty((1, nl, c), dtype=torch.bfloat16, device=dev)
+
+    def gather(local):      # every "peer" contributes a copy of the local rows
+        return local.reshape(1, nl, -1).expand(a.world, nl, -1).reshape(a.world * nl, -1)[:n]
+
+    def chain_bf16():
+        k = hip.rmsnorm_rope(ks, w, heads, 1e-6, tab)
+        q = hip.rmsnorm_rope(qs, w, heads, 1e-6, tab)
+        hip.attention(q, gather(k[0]).unsqueeze(0), gather(vs[0]).unsqueeze(0), heads, out=out)
+
+    def chain_8(pv8):
+        v = vs if pv8 else None
+        k, parts = hip.rmsnorm_rope_kstats(ks, w, heads, 1e-6, tab)
+        rec = hip.attn_shard8_stats(parts, nl, heads, v)
+        q8, sq = hip.rmsnorm_rope_q8(qs, w, heads, 1e-6, tab)
+        k8, v8, sk, _, sv = hip.attn_shard8_quant(rec.view(1, -1).repeat(a.world, 1), n, k, heads, v)
+        k8f = gather(k8.view(torch.uint8)).view(torch.float8_e4m3fn)
+        if pv8:
+            hip.attention_pv8_pre(q8, k8f, sq, sk, hip.attn_shard8_vt(gather(v8.view(torch.uint8)), heads), sv, heads, out=out)
+        else:
+            hip.attention_qk8_pre(q8, k8f, sq, sk, gather(vs[0]).unsqueeze(0), heads, out=out)
+
+    k, parts = hip.rmsnorm_rope_kstats(ks, w, heads, 1e-6, tab)
+    rec = hip.attn_shard8_stats(parts, nl, heads, vs).view(1, -1).repeat(a.world, 1)
+    v8_full = torch.empty((n, c), dtype=torch.uint8, device=dev).random_(0, 120)
+    vt_bufs = hip.attention_pv8_scratch(nl, heads, 128, dev)
+    mb = nl * c / 1e6
+    fns = [("chain-bf16", chain_bf16, None), ("chain-qk8-sharded", lambda: chain_8(False), None), ("chain-pv8-sharded", lambda: chain_8(True), None),
+           ("shard8-stats (v)", lambda: hip.attn_shard8_stats(parts, nl, heads, vs), 2 * mb),
+           ("shard8-quant (k, v)", lambda: hip.attn_shard8_quant(rec, n, k, heads, vs), 6 * mb),
+           ("shard8-vt", lambda: hip.attn_shard8_vt(v8_full, heads), 2 * n * c / 1e6),
+           ("quant-vt (same rows)", lambda: hip.attn_quant_vt(vs, heads, vt_bufs), 5 * mb)]
+    times = {name: [] for name, _, _ in fns}
+    for _ in range(a.rounds):
+        for name, fn, _ in fns:
+            for _ in range(a.iters):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1))
+    print(f"one rank of {a.world}: nq = {nl}, nkv = {n}, {heads} heads; medians of {a.rounds * a.iters} launches after {a.iters} warm-up; "
+          "local copies stand in for the collectives (no xGMI figure)")
+    for name, _, mbytes in fns:
+        t = sorted(times[name][a.iters:])
+        med = t[len(t) // 2]
+        print(f"{name:24s} {med:8.3f} ms" + (f"   {mbytes / med:7.0f} GB/s ({mbytes:.1f} MB read + written)" if mbytes else ""), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--shard8", action="store_true", help="time one rank's attention chain of the K / V all-gather layout (--world ranks, nkv keys "
+                    "in all) for bf16, qk8-sharded and pv8-sharded, and the new passes alone; nothing else runs")
+    ap.add_argument("--world", type=int, default=8)
     ap.add_argument("--libs", default="base=" + hip.library_path())
     ap.add_argument("--nq", type=int, default=27280)
     ap.add_argument("--nkv", type=int, default=27280)
@@ -66,6 +133,8 @@ def main():
                     "the fused producers (fg_rmsnorm_rope_kstats_bf16, fg_rmsnorm_rope_q8_bf16, fg_attn_quant_k_bf16) + fg_attn_fwd_qk8_bf16; "
                     "and the producers of each form alone ('prod-*').  The two e4m3 chains are first checked to be the same bytes")
     a = ap.parse_args()
+    if a.shard8:
+        return shard8(a)
     a.qk8 = a.qk8 or a.pv8
     dev = "cuda"
     g = torch.Generator(dev).manual_seed(0)
