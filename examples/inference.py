@@ -19,12 +19,14 @@ NEGATIVE = ("è‰²è°ƒè‰³ä¸½ï¼Œè¿‡æ›ï¼Œé™æ€ï¼Œç»†èŠ‚æ¨¡ç³Šä¸æ¸…ï¼Œå­—å¹•ï¼Œé£æ
             "ç”»å¾—ä¸å¥½çš„æ‰‹éƒ¨ï¼Œç”»å¾—ä¸å¥½çš„è„¸éƒ¨ï¼Œç•¸å½¢çš„ï¼Œæ¯å®¹çš„ï¼Œå½¢æ€ç•¸å½¢çš„è‚¢ä½“ï¼Œæ‰‹æŒ‡èåˆï¼Œé™æ­¢ä¸åŠ¨çš„ç”»é¢ï¼Œæ‚ä¹±çš„èƒŒæ™¯ï¼Œä¸‰æ¡è…¿ï¼ŒèƒŒæ™¯äººå¾ˆå¤šï¼Œå€’ç€èµ°")
 
 
-def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False):
+def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False, cross8=False):
     dit_cfg = dict(computation_dtype=torch.float8_e4m3fn) if fp8 else {}
     if qk8 or pv8:
         dit_cfg["attention_dtype"] = torch.float8_e4m3fn
     if pv8:
         dit_cfg["attention_pv_dtype"] = torch.float8_e4m3fn
+    if cross8:
+        dit_cfg["cross_attention_dtype"] = torch.float8_e4m3fn
     pipe = WanVideoPipeline.from_pretrained(
         torch_dtype=torch.bfloat16, device="cuda",
         model_configs=[
@@ -36,7 +38,8 @@ def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=Fals
     if lora:
         pipe.load_lora(pipe.dit, lora, alpha=1)
     if (qk8 or pv8) and getattr(pipe, "parallel", None) is not None:
-        # a token-sharded layout: the e4m3 mode with its statistics exchange (off by default; no multi-GPU hardware run exists)
+        # a token-sharded layout: the e4m3 mode with its statistics exchange (off by default; no multi-GPU hardware run exists); the e4m3
+        # cross-attention is not run on token shards and is switched off here
         pipe.dit.enable_qk8_attention(fused_producer=pipe.dit.qk8_fused_producer, pv8=pv8, sharded=True)
     return pipe
 
@@ -54,8 +57,11 @@ def main():
                     help="e4m3 Q K^T in the DiT's self-attention (the reference's sageattn branch); P V and cross-attention stay bf16")
     ap.add_argument("--pv8-attention", action="store_true",
                     help="... and e4m3 P V as well (both MFMAs of self-attention 8-bit); implies --qk8-attention")
+    ap.add_argument("--cross8-attention", action="store_true",
+                    help="... and cross-attention over the text context in the same e4m3 form; implies --pv8-attention")
     a = ap.parse_args()
-    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or a.pv8_attention, a.pv8_attention)
+    pv8 = a.pv8_attention or a.cross8_attention
+    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or pv8, pv8, a.cross8_attention)
     image = Image.open(a.image).convert("RGB").resize((832, 480))
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     video = pipe(prompt=a.prompt, negative_prompt=NEGATIVE, input_image=image, num_frames=81, seed=1, tiled=True)

@@ -113,6 +113,17 @@ _SHARD8_QUERIES = {
 }
 SHARD8_SYMBOLS = sorted(list(_SHARD8_SIGNATURES) + list(_SHARD8_QUERIES))    # what include/fairygen_hip_shard8.h declares
 
+# The extension of include/fairygen_hip_cross8.h (e4m3 cross-attention with a head's K8 and V8^T resident in LDS): a fourth pair of tables.
+CROSS8_ABI_VERSION = 1    # fg_attn_cross8_version
+_CROSS8_SIGNATURES = {
+    "fg_attn_fwd_cross8_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp],
+}
+_CROSS8_QUERIES = {
+    "fg_attn_cross8_version": (_i32, []),
+    "fg_attn_cross8_max_kv": (_i64, []),
+}
+CROSS8_SYMBOLS = sorted(list(_CROSS8_SIGNATURES) + list(_CROSS8_QUERIES))    # what include/fairygen_hip_cross8.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -132,14 +143,17 @@ def load():
             f"{_LIB_PATH} not found: build it with `make -C fairygen_amd/csrc` (or __graft_entry__.build()). "
             "fairygen_amd has no CPU / PyTorch fallback for its kernels.")
     lib = ctypes.CDLL(_LIB_PATH)
-    for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()):
+    for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
+            list(_CROSS8_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
-    for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()):
+    for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
+            list(_CROSS8_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
                                  ("fg_attn_pv8_version", PV8_ABI_VERSION, " (e4m3 P V extension)"),
-                                 ("fg_attn_shard8_version", SHARD8_ABI_VERSION, " (e4m3 operands of a token shard)")):
+                                 ("fg_attn_shard8_version", SHARD8_ABI_VERSION, " (e4m3 operands of a token shard)"),
+                                 ("fg_attn_cross8_version", CROSS8_ABI_VERSION, " (e4m3 cross-attention, K8 / V8^T in LDS)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -789,6 +803,26 @@ def attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None, 
     ws, need = _attn_ws(q8.device, 1, nq, nkv, num_heads, workspace)
     _call("fg_attn_fwd_pv8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q8))
+    return out
+
+
+def attention_cross8_max_kv():
+    """The most keys attention_cross8_pre takes (fg_attn_cross8_max_kv: 640, what 160 KiB of LDS hold of a head's K8 and V8^T)."""
+    return int(load().fg_attn_cross8_max_kv())
+
+
+def attention_cross8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None):
+    """fg_attn_fwd_cross8_bf16 (include/fairygen_hip_cross8.h) on attention_pv8_pre's operands, Nkv <= attention_cross8_max_kv(): every
+    workgroup keeps its head's K8 and V8^T in LDS and walks many query blocks against them.  One launch, no workspace; the bits of
+    attention_pv8_pre without one."""
+    (nq, hd), nkv = q8.shape, k8.shape[0]
+    d = hd // num_heads
+    if k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads or sv.numel() != hd or not v8t.is_contiguous() or \
+            v8t.shape != (num_heads, d, (nkv + 63) // 64 * 64):
+        raise HipLibraryError(f"attention_cross8_pre: k8, sq, sk, v8t, sv do not match q8 {tuple(q8.shape)} and {nkv} keys")
+    out = torch.empty((1, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
+    _call("fg_attn_fwd_cross8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
+          float(d) ** -0.5 if scale is None else float(scale), _stream(q8))
     return out
 
 

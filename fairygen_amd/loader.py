@@ -37,6 +37,8 @@ class ModelConfig:
     attention_dtype: Optional[torch.dtype] = None
     # torch.float8_e4m3fn (with attention_dtype): the P V product of that self-attention in e4m3 too (enable_qk8_attention(pv8=True)); None: bf16
     attention_pv_dtype: Optional[torch.dtype] = None
+    # torch.float8_e4m3fn (with both of the above): cross-attention in the e4m3 form too (enable_qk8_attention(pv8=True, cross=True)); None: bf16
+    cross_attention_dtype: Optional[torch.dtype] = None
     clear_parameters: bool = False
 
     def check_input(self):
@@ -57,7 +59,7 @@ class ModelConfig:
         return {k: getattr(self, k) for k in (
             "offload_device", "offload_dtype", "onload_device", "onload_dtype",
             "preparing_device", "preparing_dtype", "computation_device", "computation_dtype", "attention_dtype",
-            "attention_pv_dtype")}
+            "attention_pv_dtype", "cross_attention_dtype")}
 
 
 # --------------------------------------------------------------------------------- state-dict files
@@ -218,6 +220,13 @@ class ModelPool:
                 if attn is None:
                     raise NotImplementedError("attention_pv_dtype without attention_dtype: the 8-bit P V product is built on the 8-bit Q K^T "
                                               "self-attention (attention_dtype=torch.float8_e4m3fn)")
+            attn_cross = vram_config.get("cross_attention_dtype")
+            if attn_cross is not None:
+                if attn_cross != torch.float8_e4m3fn:
+                    raise NotImplementedError(f"cross_attention_dtype={attn_cross}: the 8-bit cross-attention is built for torch.float8_e4m3fn only")
+                if attn is None or attn_pv is None:
+                    raise NotImplementedError("cross_attention_dtype without attention_dtype and attention_pv_dtype: the 8-bit cross-attention "
+                                              "takes the operands of the 8-bit Q K^T and P V self-attention (both torch.float8_e4m3fn)")
             if attn is not None:
                 if attn != torch.float8_e4m3fn:
                     raise NotImplementedError(f"attention_dtype={attn}: the 8-bit Q K^T self-attention is built for torch.float8_e4m3fn only")
@@ -225,7 +234,7 @@ class ModelPool:
                     raise NotImplementedError(f"attention_dtype is only built for the DiT's self-attention, not for {cfg['model_name']}")
                 model.enable_qk8_attention()
                 if attn_pv is not None:
-                    model.enable_qk8_attention(pv8=True)      # P V in e4m3 too
+                    model.enable_qk8_attention(pv8=True, cross=attn_cross is not None)      # P V in e4m3 too, and cross-attention if asked
                 model.qk8_fused_producer = True      # the operands from the RMSNorm+RoPE pass itself: the same bits, k read once
             self.model.append(model)
             self.model_name.append(cfg["model_name"])

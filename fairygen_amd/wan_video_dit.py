@@ -228,6 +228,29 @@ class _BlockLinears:
             self.owned.attn_qk8_bufs[key] = hip.attention_pv8_scratch(*key[:4])
         return {"pv8": True, "pv8_bufs": self.owned.attn_qk8_bufs[key]}
 
+    def cross8_q(self, qc, norm_q, num_heads):
+        """The e4m3 q operand of cross-attention (enable_qk8_attention(cross=True)) from the q Linear's output: the RMSNorm pass without a
+        RoPE table writes the e4m3 rows and their scales and no bf16 q.  A captured step owns the two buffers, one pair per shape for
+        all blocks (a block's pair is consumed before the next block writes it, in stream order)."""
+        kw = {}
+        if self.owned is not None:
+            key = (qc.shape[1], num_heads, qc.shape[2] // num_heads, qc.device, "cross8")
+            if key not in self.owned.attn_qk8_bufs:
+                self.owned.attn_qk8_bufs[key] = (torch.empty(qc.shape[1:], dtype=torch.float8_e4m3fn, device=qc.device),
+                                                 torch.empty((qc.shape[1], num_heads), dtype=torch.float32, device=qc.device))
+            kw["q8"], kw["sq"] = self.owned.attn_qk8_bufs[key]
+        return hip.rmsnorm_rope_q8(qc, norm_q.weight, num_heads, self.eps, **kw)
+
+    def cross8_context(self, kvc, norm_k, num_heads):
+        """The e4m3 operands of a block's context from its k | v rows (1, L, 2 C): (k8, sk, v8t, sv) — the RMSNorm pass of k that also leaves
+        the key statistics, the key conversion behind it, and fg_attn_quant_vt_bf16 on v.  Once per denoise loop with a kv_cache, which
+        then holds these four in place of (k, v); the buffers are the binding's own allocations either way."""
+        c = kvc.shape[-1] // 2
+        k, parts = hip.rmsnorm_rope_kstats(kvc[..., :c], norm_k.weight, num_heads, self.eps)
+        k8, sk, _ = hip.attn_quant_k(k, parts, num_heads)
+        v8t, sv, _ = hip.attn_quant_vt(kvc[..., c:], num_heads)
+        return k8, sk, v8t, sv
+
     def qk8_bufs(self, n, num_heads, head_dim, device, fused):
         """The e4m3 operands' buffers: a captured step's own, made once per shape (fused: with the key-statistics partials); None in an
         eager forward, where the binding allocates."""
@@ -327,6 +350,12 @@ class _BlockLinears:
 # enable_qk8_attention(): self-attention over more keys than this runs the e4m3 Q K^T kernel; at or below it (where fg_attn_fwd_bf16 itself
 # leaves its 4-wave kernel) the bf16 kernel runs
 QK8_MIN_KV = 1024
+
+
+def takes_cross8_attention(model, attn, n_kv, batch):
+    """enable_qk8_attention(cross=True): the stock AttentionModule of cross-attention, one batch element, a context whose K8 and V8^T fit
+    the LDS (hip.attention_cross8_max_kv(): 640 keys).  Anything else keeps the bf16 kernel."""
+    return bool(model.cross8_attention) and type(attn) is AttentionModule and batch == 1 and 1 <= n_kv <= hip.attention_cross8_max_kv()
 
 
 def takes_qk8_attention(model, attn, n_kv, batch):
@@ -485,6 +514,8 @@ class WanModel(nn.Module):
         self.pv8_attention = False
         # ... and on token-sharded layouts (enable_qk8_attention(sharded=True)); False: an active shard raises
         self.qk8_sharded = False
+        # ... and cross-attention in the e4m3 form too (enable_qk8_attention(pv8=True, cross=True)); False: cross-attention in bf16
+        self.cross8_attention = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -521,7 +552,7 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ e4m3 Q K^T self-attention (models/wan_video_dit.py:48-52)
-    def enable_qk8_attention(self, flag=True, fused_producer=False, pv8=False, sharded=False):
+    def enable_qk8_attention(self, flag=True, fused_producer=False, pv8=False, sharded=False, cross=False):
         """Run self-attention of every block like the reference's flash_attention does when the sageattention package is present
         (sageattn(q, k, v)): Q K^T from e4m3 operands — K mean-smoothed with one scale per head, Q with one scale per row and head
         (fg_attn_quant_qk_bf16) — on fg_attn_fwd_qk8_bf16; softmax and P V as before, v in bf16.  Only the stock AttentionModule of
@@ -545,18 +576,34 @@ class WanModel(nn.Module):
         of the rows the gathered operands and the scales are byte for byte those of the unsharded mode, where the fp64 key sum is exact
         (include/fairygen_hip.h); the attention kernels are the same.  Composes with enable_fp8_linear, hot adapters and cfg_parallel=2 (the
         shard is then the half-group); graph=True with a shard raises as before; attn_mode="windows" has no exchange in a forward and
-        is not affected.  No multi-GPU hardware run of this project exists: the mode is tested with emulated ranks on one GPU."""
+        is not affected.  No multi-GPU hardware run of this project exists: the mode is tested with emulated ranks on one GPU.
+        cross: cross-attention over the text context in the e4m3 form as well, as the reference's sageattn call covers it
+        (include/fairygen_hip_cross8.h).  It needs flag and pv8 (the operands are those of the e4m3 P V form).  Only the stock
+        AttentionModule, one batch element and a context of at most hip.attention_cross8_max_kv() keys take it (takes_cross8_attention).
+        The q norm writes e4m3 rows and their scales and no bf16 q (fg_rmsnorm_rope_q8_bf16 without a RoPE table); a block's context is
+        quantised where its k | v rows are computed — once per denoise loop with a kv_cache, which then holds (k8, sk, v8t, sv) in place
+        of (k, v); per call without one (sliding windows) — and fg_attn_fwd_cross8_bf16 keeps a head's K8 and V8^T in LDS while it walks
+        the query blocks.  Composes with enable_fp8_linear, hot adapters and graph=True (the captured step owns the q8 / sq buffers, the
+        context operands live in the loop's kv_cache).  An active token shard raises NotImplementedError, sharded=True or not: the
+        query rows are local and the context is whole on every rank, so no collective would be needed, but no sharded run of it has
+        been tested."""
         if pv8 and not flag:
             raise ValueError("enable_qk8_attention(pv8=True) needs the e4m3 Q K^T mode on (flag=True)")
         if sharded and not flag:
             raise ValueError("enable_qk8_attention(sharded=True) needs the e4m3 Q K^T mode on (flag=True)")
+        if cross and not (flag and pv8):
+            raise ValueError("enable_qk8_attention(cross=True) needs the e4m3 Q K^T mode and its e4m3 P V form on (flag=True, pv8=True)")
         self.qk8_attention = bool(flag)
         self.qk8_fused_producer = bool(flag) and bool(fused_producer)
         self.pv8_attention = bool(flag) and bool(pv8)
         self.qk8_sharded = bool(flag) and bool(sharded)
+        self.cross8_attention = bool(flag) and bool(pv8) and bool(cross)
         return self
 
     def check_qk8_layout(self, shard):
+        if self.cross8_attention and shard is not None and shard.active:
+            raise NotImplementedError("enable_qk8_attention(cross=True) with a token-sharded layout: the e4m3 cross-attention has not been "
+                                      "run on token shards; switch it off (cross=False) for a sharded run")
         if self.qk8_attention and not self.qk8_sharded and shard is not None and shard.active:
             raise NotImplementedError("enable_qk8_attention() with a token-sharded layout: the key mean and the per-head key scale of the e4m3 "
                                       "Q K^T form span all ranks' tokens and would need a collective; enable_qk8_attention(sharded=True) "
@@ -911,15 +958,27 @@ class WanModel(nn.Module):
                     cfg_prefix["x_sa"] = x.clone()
             # --- cross attention (reference :170-185)
             qc = lin.plain(h, (f"blocks.{i}.cross_attn.q",), ca.q.weight, ca.q.bias, w8[2], own=lin.own)
-            qc = hip.rmsnorm_rope(qc, ca.norm_q.weight, nh, eps)
-            if kv_cache is not None and i in kv_cache:
-                kc, vc = kv_cache[i]
-            else:      # 512 context rows, once per denoise loop with a kv_cache: library GEMM, adapters on the reference's torch ops
-                kvc = lin.plain(ctx, (f"blocks.{i}.cross_attn.k", f"blocks.{i}.cross_attn.v"), wkv_c, bkv_c, w8[3], hip_adapters=False)
-                kc, vc = hip.rmsnorm_rope(kvc[..., :c], ca.norm_k.weight, nh, eps), kvc[..., c:]
-                if kv_cache is not None:
-                    kv_cache[i] = (kc, vc)
-            ac = lin.attention(ca.attn, qc, kc, vc)
+            if takes_cross8_attention(self, ca.attn, context.shape[1], qc.shape[0]):      # enable_qk8_attention(cross=True)
+                q8c, sqc = lin.cross8_q(qc, ca.norm_q, nh)
+                if kv_cache is not None and i in kv_cache:
+                    ops8 = kv_cache[i]
+                else:
+                    kvc = lin.plain(ctx, (f"blocks.{i}.cross_attn.k", f"blocks.{i}.cross_attn.v"), wkv_c, bkv_c, w8[3], hip_adapters=False)
+                    ops8 = lin.cross8_context(kvc, ca.norm_k, nh)
+                    if kv_cache is not None:
+                        kv_cache[i] = ops8
+                k8c, skc, v8tc, svc = ops8
+                ac = hip.attention_cross8_pre(q8c, k8c, sqc, skc, v8tc, svc, nh)
+            else:
+                qc = hip.rmsnorm_rope(qc, ca.norm_q.weight, nh, eps)
+                if kv_cache is not None and i in kv_cache:
+                    kc, vc = kv_cache[i]
+                else:      # 512 context rows, once per denoise loop with a kv_cache: library GEMM, adapters on the reference's torch ops
+                    kvc = lin.plain(ctx, (f"blocks.{i}.cross_attn.k", f"blocks.{i}.cross_attn.v"), wkv_c, bkv_c, w8[3], hip_adapters=False)
+                    kc, vc = hip.rmsnorm_rope(kvc[..., :c], ca.norm_k.weight, nh, eps), kvc[..., c:]
+                    if kv_cache is not None:
+                        kv_cache[i] = (kc, vc)
+                ac = lin.attention(ca.attn, qc, kc, vc)
             # x += y ; h = modulate(norm2(x))  (reference :226-227); with both norm outputs wanted, norm3's bf16 row is written over
             x, h = lin.residual(x, ac, f"blocks.{i}.cross_attn.o", ca.o.weight, ca.o.bias, w8[4], mod, None, modulate=(mod, 3, 4),
                                 out=h.bf16 if lin.want_q8 else None)

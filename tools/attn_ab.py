@@ -108,8 +108,81 @@ def shard8(a):
         print(f"{name:24s} {med:8.3f} ms" + (f"   {mbytes / med:7.0f} GB/s ({mbytes:.1f} MB read + written)" if mbytes else ""), flush=True)
 
 
+def cross8(a):
+    """--cross8: cross-attention from the q Linear's output to the attention output, 24 heads over a context of --nkv rows (512), in ONE
+    process with alternating launches, at every --cross8-nq: (a) 'chain-bf16' = rmsnorm_rope + fg_attn_fwd_bf16, (b) 'chain-pv8' = the q8
+    producer (fg_rmsnorm_rope_q8_bf16 without a table) + fg_attn_fwd_pv8_bf16, (c) 'chain-cross8' = the q8 producer + fg_attn_fwd_cross8_bf16
+    (K8 and V8^T resident in LDS); the three attention launches alone ('attn-*'); and 'quant-context' = the quantisation of a block's
+    context (key norm with statistics, fg_attn_quant_k_bf16, fg_attn_quant_vt_bf16), paid once per denoise loop and timed on its own.
+    (b) and (c) are first checked to be the same bytes."""
+    dev, heads, nkv = "cuda", a.heads, a.nkv
+    c = heads * 128
+    g = torch.Generator(dev).manual_seed(0)
+    rnd = lambda *s: torch.randn(s, generator=g, device=dev, dtype=torch.float32).to(torch.bfloat16)  # noqa: E731
+    wq, wk = (1 + 0.1 * rnd(c).float()).to(torch.bfloat16), (1 + 0.1 * rnd(c).float()).to(torch.bfloat16)
+    kvc = rnd(1, nkv, 2 * c)
+
+    def quant_context():
+        k, parts = hip.rmsnorm_rope_kstats(kvc[..., :c], wk, heads, 1e-6)
+        k8, sk, _ = hip.attn_quant_k(k, parts, heads)
+        v8t, sv, _ = hip.attn_quant_vt(kvc[..., c:], heads)
+        return k8, sk, v8t, sv
+    k8, sk, v8t, sv = quant_context()
+    k16, v16 = hip.rmsnorm_rope(kvc[..., :c], wk, heads, 1e-6), kvc[..., c:]
+    for nq in (int(x) for x in a.cross8_nq.split(",")):
+        x = rnd(1, nq, c)
+        q16, o16, o8, oc = (torch.empty((1, nq, c), dtype=torch.bfloat16, device=dev) for _ in range(4))
+        q8, sq = torch.empty((nq, c), dtype=torch.float8_e4m3fn, device=dev), torch.empty((nq, heads), dtype=torch.float32, device=dev)
+        ws16, ws8 = [], []
+
+        def prod16():
+            hip.rmsnorm_rope(x, wq, heads, 1e-6, out=q16)
+
+        def prod8():
+            hip.rmsnorm_rope_q8(x, wq, heads, 1e-6, q8=q8, sq=sq)
+
+        def attn16():
+            hip.attention(q16, k16, v16, heads, out=o16, workspace=ws16)
+
+        def attn8():
+            hip.attention_pv8_pre(q8, k8, sq, sk, v8t, sv, heads, out=o8, workspace=ws8)
+
+        def attnc():
+            hip.attention_cross8_pre(q8, k8, sq, sk, v8t, sv, heads, out=oc)
+        fns = [("chain-bf16", lambda: (prod16(), attn16())), ("chain-pv8", lambda: (prod8(), attn8())), ("chain-cross8", lambda: (prod8(), attnc())),
+               ("attn-bf16", attn16), ("attn-pv8", attn8), ("attn-cross8", attnc), ("quant-context", quant_context)]
+        for _, fn in fns:
+            for _ in range(2):
+                fn()
+        torch.cuda.synchronize()
+        err = (oc.float() - o16.float()).abs()
+        print(f"check nq={nq}: fg_attn_fwd_cross8_bf16 and fg_attn_fwd_pv8_bf16 {'are the same bytes  OK' if torch.equal(oc, o8) else 'DIFFER  FAIL'}; "
+              f"against the bf16 chain max {err.max().item():.5f}, mean {err.mean().item():.6f}", flush=True)
+        times = {n: [] for n, _ in fns}
+        for _ in range(a.rounds):
+            for n, fn in fns:
+                evs = []
+                for _ in range(a.iters):
+                    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    s.record(); fn(); e.record()
+                    evs.append((s, e))
+                torch.cuda.synchronize()
+                times[n] += [s.elapsed_time(e) for s, e in evs]
+        fl = 4.0 * nq * nkv * c
+        for n, ts in times.items():
+            ts = sorted(ts)
+            mean = sum(ts) / len(ts)
+            sd = (sum((t - mean) ** 2 for t in ts) / max(len(ts) - 1, 1)) ** 0.5
+            rate = f" = {fl / ts[len(ts) // 2] / 1e9:.0f} TFLOP/s" if n.startswith("attn-") else ""
+            print(f"{n}: nq={nq} nkv={nkv} H={heads}: median {ts[len(ts) // 2]:.4f} ms{rate}, mean {mean:.4f}, sd {sd:.4f}, min {ts[0]:.4f}, max {ts[-1]:.4f} "
+                  f"({len(ts)} runs)", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cross8", action="store_true", help="time cross-attention over --nkv context rows (use --nkv 512) from the q Linear's output "
+                    "to the attention output: bf16, the e4m3 kernel of self-attention, and the kernel that keeps K8 / V8^T in LDS; nothing else runs")
+    ap.add_argument("--cross8-nq", default="27280,8190")
     ap.add_argument("--shard8", action="store_true", help="time one rank's attention chain of the K / V all-gather layout (--world ranks, nkv keys "
                     "in all) for bf16, qk8-sharded and pv8-sharded, and the new passes alone; nothing else runs")
     ap.add_argument("--world", type=int, default=8)
@@ -135,6 +208,8 @@ def main():
     a = ap.parse_args()
     if a.shard8:
         return shard8(a)
+    if a.cross8:
+        return cross8(a)
     a.qk8 = a.qk8 or a.pv8
     dev = "cuda"
     g = torch.Generator(dev).manual_seed(0)
