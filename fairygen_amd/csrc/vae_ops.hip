@@ -350,7 +350,9 @@ int fg_vae_tile_accumulate_bf16(const void* tile, void* values, void* weight, in
     FG_CHECK_ARG(tile && values && weight && C > 0, "fg_vae_tile_accumulate_bf16: null pointer");
     FG_CHECK_ARG(F > 0 && th > 0 && tw > 0 && y0 >= 0 && x0 >= 0 && y0 + th <= Hv && x0 + tw <= Wv && border_h >= 0 && border_w >= 0,
                  "fg_vae_tile_accumulate_bf16: tile does not fit the canvas");
-    FG_CHECK_ARG(((bound_bits & 1) || border_h <= th) && ((bound_bits & 4) || border_w <= tw), "fg_vae_tile_accumulate_bf16: border wider than tile");
+    // a ramp on either free side of an axis needs `border` pixels of the tile (the reference's slice assignment raises otherwise)
+    FG_CHECK_ARG(((bound_bits & 3) == 3 || border_h <= th) && ((bound_bits & 12) == 12 || border_w <= tw),
+                 "fg_vae_tile_accumulate_bf16: border wider than tile");
     hipLaunchKernelGGL(tile_accumulate_kernel, dim3(grid_for((int64_t)F * th * tw)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16*)tile, (bf16*)values, (bf16*)weight, C, F, Hv, Wv, th, tw, y0, x0, border_h, border_w, bound_bits);
     return fg_launch_status("fg_vae_tile_accumulate_bf16");

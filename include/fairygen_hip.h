@@ -347,7 +347,8 @@ int fg_vae_unpatchify_bf16(const void* x, void* video, int T, int H, int W, int 
  * values[:, :, y0:y0+th, x0:x0+tw] += tile*mask ; weight[...] += mask, bf16 accumulators like the
  * reference; mask(y,x) = min(ramp_h(y), ramp_w(x)), ramps of width border_h/border_w on non-bound sides.
  * values (C,F,Hv,Wv), weight (F,Hv,Wv), tile (C,F,th,tw) (C = 3 decode, 48 tiled_encode :1176-1201).
- * bound bits: 1 top, 2 bottom, 4 left, 8 right. */
+ * bound bits: 1 top, 2 bottom, 4 left, 8 right.  An axis with a free side needs border <= tile length (FG_EINVAL otherwise, as
+ * the reference's slice assignment raises there); a tile shorter than two borders takes the second ramp where the two overlap. */
 int fg_vae_tile_accumulate_bf16(const void* tile, void* values, void* weight,
                                 int C, int F, int Hv, int Wv, int th, int tw, int y0, int x0,
                                 int border_h, int border_w, int bound_bits, fg_stream_t stream);
