@@ -14,6 +14,7 @@
 // HBM-bound: v is read twice, half a byte written per byte read.
 #include "common.h"
 #include "../../include/fairygen_hip_pv8.h"
+#include "../../include/fairygen_hip_batch8.h"
 #include "attn_qk8_quant.h"
 #include "attn_pv8_parts.h"
 
@@ -27,46 +28,27 @@ constexpr int kMaxTileBlocks = 32;
 // themselves and the chunks of a row among themselves, and the read below undoes both).
 __global__ __launch_bounds__(256) void attn_quant_vt_kernel(const bf16* __restrict__ v, int64_t ldv, const float* __restrict__ rec, int parts,
                                                             uint8_t* __restrict__ v8t, float* __restrict__ sv, int64_t N, int64_t Nkp, int H) {
-    __shared__ float red_s[kD];
-    __shared__ float sv_s[kD];
-    __shared__ __attribute__((aligned(16))) uint32_t img[kD][16];
-    const int h = blockIdx.y, tid = threadIdx.x, C = H * kD;
-    {
-        const int c = tid & (kD - 1), g = tid >> 7;
-        float a = 0.f;
-        for (int p = g; p < parts; p += 2) a = fmaxf(a, rec[(int64_t)p * C + h * kD + c]);
-        if (g == 1) red_s[c] = a;
-        __syncthreads();
-        if (g == 0) {
-            const float s = fmaxf(fmaxf(a, red_s[c]) / kE4M3Max, kScaleFloor);
-            sv_s[c] = s;
-            if (blockIdx.x == 0) sv[h * kD + c] = s;
-        }
-        __syncthreads();
-    }
-    const int cl = tid & 15, kg = tid >> 4;
-    float s[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = sv_s[cl * 8 + j];
-    const int wr = pv8_dword(kg) ^ cl;
-    const int64_t nt = Nkp / kTileKeys;
-    for (int64_t t = blockIdx.x; t < nt; t += gridDim.x) {
-        float f[4][8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int64_t key = t * kTileKeys + 4 * kg + i;
-            bf16x8 x = {};
-            if (key < N) x = *reinterpret_cast<const bf16x8*>(v + key * ldv + (int64_t)h * kD + cl * 8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) f[i][j] = key < N ? (float)x[j] : 0.f;      // the padding keys of the last tile: zero bytes
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            img[cl * 8 + j][wr] = cvt2_e4m3(f[0][j] / s[j], f[1][j] / s[j]) | (cvt2_e4m3(f[2][j] / s[j], f[3][j] / s[j]) << 16);
-        __syncthreads();
-        pv8_store_tile(img, v8t, h, Nkp, t, tid);
-        __syncthreads();
-    }
+#include "attn_quant_vt_body.inc"
+}
+
+// The batched forms (include/fairygen_hip_batch8.h): grid dimension z picks the batch element, which runs the single-element body on its
+// own pointers; bs.rec counts floats.
+struct QuantVtStrides {
+    int64_t v, v8t, sv, rec;
+};
+
+__global__ __launch_bounds__(256) void attn_v_stats_b_kernel(const bf16* __restrict__ v, int64_t ldv, float* __restrict__ rec, int64_t N, int C,
+                                                             const QuantVtStrides bs) {
+    const int64_t b = blockIdx.z;
+    attn_v_stats_body(v + b * bs.v, ldv, rec + b * bs.rec, N, C);
+}
+
+__global__ __launch_bounds__(256) void attn_quant_vt_b_kernel(const bf16* __restrict__ v, int64_t ldv, const float* __restrict__ rec, int parts,
+                                                              uint8_t* __restrict__ v8t, float* __restrict__ sv, int64_t N, int64_t Nkp, int H,
+                                                              const QuantVtStrides bs) {
+    const int64_t b = blockIdx.z;
+    v += b * bs.v; rec += b * bs.rec; v8t += b * bs.v8t; sv += b * bs.sv;
+#include "attn_quant_vt_body.inc"
 }
 
 }  // namespace
@@ -100,4 +82,32 @@ extern "C" int fg_attn_quant_vt_bf16(const void* v, int64_t ldv, void* v8t, floa
     hipLaunchKernelGGL(attn_quant_vt_kernel, dim3((unsigned)(nt < kMaxTileBlocks ? nt : kMaxTileBlocks), (unsigned)H), dim3(256), 0,
                        (hipStream_t)stream, (const bf16*)v, ldv, (const float*)scratch, (int)parts, (uint8_t*)v8t, sv, N, nkp, H);
     return fg_launch_status("fg_attn_quant_vt_bf16");
+}
+
+extern "C" int fg_attn_quant_vt_bf16_b(const void* v, int64_t ldv, int64_t bs_v, void* v8t, int64_t bs_v8t, float* sv, int64_t bs_sv,
+                                       void* scratch, int64_t scratch_bytes, int64_t bs_scratch, int B, int64_t N, int H, int D,
+                                       fg_stream_t stream) {
+    FG_CHECK_ARG(v && v8t && sv && scratch, "fg_attn_quant_vt_bf16_b: null pointer");
+    FG_CHECK_ARG(D == kD, "fg_attn_quant_vt_bf16_b: only head_dim 128 is supported (got %d)", D);
+    FG_CHECK_ARG(B >= 1 && B <= 65535, "fg_attn_quant_vt_bf16_b: B must be in 1..65535 (got %d)", B);
+    FG_CHECK_ARG(N > 0 && H > 0 && H <= 65535, "fg_attn_quant_vt_bf16_b: N must be positive, H in 1..65535");
+    const int64_t hd = (int64_t)H * D, nkp = (N + kTileKeys - 1) / kTileKeys * kTileKeys;
+    FG_CHECK_ARG(ldv >= hd && ldv % 8 == 0, "fg_attn_quant_vt_bf16_b: ldv must be >= H*D and a multiple of 8");
+    FG_CHECK_ARG(FG_ALIGNED16(v) && FG_ALIGNED16(v8t) && FG_ALIGNED16(sv) && FG_ALIGNED16(scratch),
+                 "fg_attn_quant_vt_bf16_b: v, v8t, sv and scratch must be 16-byte aligned");
+    const int64_t parts = v_stat_parts(N);
+    FG_CHECK_ARG(scratch_bytes >= parts * hd * 4, "fg_attn_quant_vt_bf16_b: scratch must hold %lld bytes per element (got %lld)",
+                 (long long)(parts * hd * 4), (long long)scratch_bytes);
+    FG_CHECK_ARG(bs_v >= (N - 1) * ldv + hd && bs_v8t >= hd * nkp && bs_sv >= hd && bs_scratch >= parts * hd * 4,
+                 "fg_attn_quant_vt_bf16_b: a batch stride is smaller than one element of its operand");
+    FG_CHECK_ARG(bs_v % 8 == 0 && bs_v8t % 16 == 0 && bs_sv % 4 == 0 && bs_scratch % 16 == 0,
+                 "fg_attn_quant_vt_bf16_b: batch strides must keep the alignment (v: 8 elements; v8t: 16 bytes; sv: 4 floats; scratch: 16 bytes)");
+    const QuantVtStrides bs{bs_v, bs_v8t, bs_sv, bs_scratch / 4};
+    hipLaunchKernelGGL(attn_v_stats_b_kernel, dim3((unsigned)parts, (unsigned)((hd / 8 + 63) / 64), (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, (const bf16*)v, ldv, (float*)scratch, N, (int)hd, bs);
+    if (int e = fg_launch_status("fg_attn_quant_vt_bf16_b (v statistics)")) return e;
+    const int64_t nt = nkp / kTileKeys;
+    hipLaunchKernelGGL(attn_quant_vt_b_kernel, dim3((unsigned)(nt < kMaxTileBlocks ? nt : kMaxTileBlocks), (unsigned)H, (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, (const bf16*)v, ldv, (const float*)scratch, (int)parts, (uint8_t*)v8t, sv, N, nkp, H, bs);
+    return fg_launch_status("fg_attn_quant_vt_bf16_b");
 }

@@ -17,7 +17,7 @@ inline int64_t v_stat_parts(int64_t n) {
 }
 
 // Workgroup (x, y) of 4 waves: lane l owns the 8 channels of 16-byte chunk 64 y + l; wave w walks the rows 4 x + w + 4 gridDim.x i.
-__global__ __launch_bounds__(256) void attn_v_stats_kernel(const bf16* __restrict__ v, int64_t ldv, float* __restrict__ rec, int64_t N, int C) {
+__device__ __forceinline__ void attn_v_stats_body(const bf16* __restrict__ v, int64_t ldv, float* __restrict__ rec, int64_t N, int C) {
     __shared__ float amax_s[3][8][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int chunk = blockIdx.y * 64 + lane;
@@ -47,6 +47,10 @@ __global__ __launch_bounds__(256) void attn_v_stats_kernel(const bf16* __restric
     float* o = rec + (int64_t)blockIdx.x * C + (int64_t)chunk * 8;
     *reinterpret_cast<f32x4*>(o) = lo;
     *reinterpret_cast<f32x4*>(o + 4) = hi;
+}
+
+__global__ __launch_bounds__(256) void attn_v_stats_kernel(const bf16* __restrict__ v, int64_t ldv, float* __restrict__ rec, int64_t N, int C) {
+    attn_v_stats_body(v, ldv, rec, N, C);
 }
 
 // Dword (4 keys) d of a tile's 16 holds the keys 4 kg .. 4 kg + 3 with d = kPv8Dword(kg): MFMA k index 32 hh + 16 sub + j stands for key

@@ -10,6 +10,7 @@
 // mean), then the quantise pass over 16 rows x 1 head per workgroup.  HBM-bound: q and k are read once by the second pass and k twice
 // more by the first, 1.5 bytes written per 4 read.
 #include "common.h"
+#include "../../include/fairygen_hip_batch8.h"
 #include "attn_qk8_quant.h"
 
 namespace {
@@ -17,63 +18,13 @@ namespace {
 // One workgroup of 1024 per head.  Thread t: 16-byte chunk t & 15 of the rows (t >> 4) + 64 i.
 __global__ __launch_bounds__(1024) void attn_k_stats_kernel(const bf16* __restrict__ k, int64_t ldk, float* __restrict__ kbar,
                                                             float* __restrict__ sk, int64_t N) {
-    __shared__ double red[16][kD];
-    __shared__ float mean_s[kD];
-    __shared__ float amax_s[16];
-    const int h = blockIdx.x, tid = threadIdx.x, c = tid & 15, rl = tid >> 4, wave = tid >> 6, lane = tid & 63;
-    const bf16* kp = k + (int64_t)h * kD + c * 8;
-    double acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = 0.0;
-    for (int64_t row = rl; row < N; row += 64) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(kp + row * ldk);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += (double)(float)v[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        acc[j] += __shfl_xor(acc[j], 16, 64);
-        acc[j] += __shfl_xor(acc[j], 32, 64);
-    }
-    if (lane < 16) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) red[wave][c * 8 + j] = acc[j];
-    }
-    __syncthreads();
-    if (tid < kD) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) s += red[w][tid];
-        const float m = (float)(s / (double)N);
-        mean_s[tid] = m;
-        kbar[h * kD + tid] = m;
-    }
-    __syncthreads();
-    float m[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m[j] = mean_s[c * 8 + j];
-    float amax = 0.f;
-    for (int64_t row = rl; row < N; row += 64) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(kp + row * ldk);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)v[j] - m[j]));
-    }
-    amax = wave_max(amax);
-    if (lane == 0) amax_s[wave] = amax;
-    __syncthreads();
-    if (tid == 0) {
-        float a = amax_s[0];
-#pragma unroll
-        for (int w = 1; w < 16; ++w) a = fmaxf(a, amax_s[w]);
-        sk[h] = fmaxf(a / kE4M3Max, kScaleFloor);
-    }
+#include "attn_k_stats_body.inc"
 }
 
 // 16 rows of one head per workgroup of 256: 16 lanes x 8 channels cover a row.
-__global__ __launch_bounds__(256) void attn_quant_qk_kernel(const bf16* __restrict__ q, int64_t ldq, const bf16* __restrict__ k, int64_t ldk,
-                                                            const float* __restrict__ kbar, const float* __restrict__ sk,
-                                                            uint8_t* __restrict__ q8, uint8_t* __restrict__ k8, float* __restrict__ sq,
-                                                            int64_t N, int H) {
+__device__ __forceinline__ void attn_quant_qk_body(const bf16* __restrict__ q, int64_t ldq, const bf16* __restrict__ k, int64_t ldk,
+                                                   const float* __restrict__ kbar, const float* __restrict__ sk, uint8_t* __restrict__ q8,
+                                                   uint8_t* __restrict__ k8, float* __restrict__ sq, int64_t N, int H) {
     const int h = blockIdx.y, tid = threadIdx.x, c = tid & 15;
     const int64_t row = (int64_t)blockIdx.x * 16 + (tid >> 4);
     const bool valid = row < N;
@@ -100,6 +51,35 @@ __global__ __launch_bounds__(256) void attn_quant_qk_kernel(const bf16* __restri
     if (c == 0) sq[row * H + h] = s_q;
 }
 
+__global__ __launch_bounds__(256) void attn_quant_qk_kernel(const bf16* __restrict__ q, int64_t ldq, const bf16* __restrict__ k, int64_t ldk,
+                                                            const float* __restrict__ kbar, const float* __restrict__ sk,
+                                                            uint8_t* __restrict__ q8, uint8_t* __restrict__ k8, float* __restrict__ sq,
+                                                            int64_t N, int H) {
+    attn_quant_qk_body(q, ldq, k, ldk, kbar, sk, q8, k8, sq, N, H);
+}
+
+// The batched forms (include/fairygen_hip_batch8.h): one more grid dimension picks the batch element, whose pointers the strides give;
+// the element then runs the body of the single-element kernel.
+struct QuantQkStrides {
+    int64_t q, k, q8, k8, sq, sk, kbar;
+};
+
+__global__ __launch_bounds__(1024) void attn_k_stats_b_kernel(const bf16* __restrict__ k, int64_t ldk, float* __restrict__ kbar,
+                                                              float* __restrict__ sk, int64_t N, const QuantQkStrides bs) {
+    const int64_t b = blockIdx.y;
+    k += b * bs.k; kbar += b * bs.kbar; sk += b * bs.sk;
+#include "attn_k_stats_body.inc"
+}
+
+__global__ __launch_bounds__(256) void attn_quant_qk_b_kernel(const bf16* __restrict__ q, int64_t ldq, const bf16* __restrict__ k, int64_t ldk,
+                                                              const float* __restrict__ kbar, const float* __restrict__ sk,
+                                                              uint8_t* __restrict__ q8, uint8_t* __restrict__ k8, float* __restrict__ sq,
+                                                              int64_t N, int H, const QuantQkStrides bs) {
+    const int64_t b = blockIdx.z;
+    attn_quant_qk_body(q + b * bs.q, ldq, k + b * bs.k, ldk, kbar + b * bs.kbar, sk + b * bs.sk, q8 + b * bs.q8, k8 + b * bs.k8,
+                       sq + b * bs.sq, N, H);
+}
+
 }  // namespace
 
 extern "C" int fg_attn_qk8_version(void) { return 1; }
@@ -122,4 +102,38 @@ extern "C" int fg_attn_quant_qk_bf16(const void* q, int64_t ldq, const void* k, 
     hipLaunchKernelGGL(attn_quant_qk_kernel, dim3((unsigned)((N + 15) / 16), (unsigned)H), dim3(256), 0, (hipStream_t)stream, (const bf16*)q, ldq,
                        (const bf16*)k, ldk, (const float*)scratch, (const float*)sk, (uint8_t*)q8, (uint8_t*)k8, sq, N, H);
     return fg_launch_status("fg_attn_quant_qk_bf16");
+}
+
+extern "C" int fg_attn_batch8_version(void) { return 1; }
+
+extern "C" int fg_attn_quant_qk_bf16_b(const void* q, int64_t ldq, int64_t bs_q, const void* k, int64_t ldk, int64_t bs_k, void* q8,
+                                       int64_t bs_q8, void* k8, int64_t bs_k8, float* sq, int64_t bs_sq, float* sk, int64_t bs_sk,
+                                       void* scratch, int64_t scratch_bytes, int64_t bs_scratch, int B, int64_t N, int H, int D,
+                                       fg_stream_t stream) {
+    FG_CHECK_ARG(q && k && q8 && k8 && sq && sk && scratch, "fg_attn_quant_qk_bf16_b: null pointer");
+    FG_CHECK_ARG(D == kD, "fg_attn_quant_qk_bf16_b: only head_dim 128 is supported (got %d)", D);
+    FG_CHECK_ARG(B >= 1 && B <= 65535, "fg_attn_quant_qk_bf16_b: B must be in 1..65535 (got %d)", B);
+    FG_CHECK_ARG(N > 0 && H > 0 && H <= 65535, "fg_attn_quant_qk_bf16_b: N must be positive, H in 1..65535");
+    const int64_t hd = (int64_t)H * D;
+    FG_CHECK_ARG(ldq >= hd && ldk >= hd && ldq % 8 == 0 && ldk % 8 == 0,
+                 "fg_attn_quant_qk_bf16_b: leading dimensions must be >= H*D and multiples of 8");
+    FG_CHECK_ARG(FG_ALIGNED16(q) && FG_ALIGNED16(k) && FG_ALIGNED16(scratch) && (((uintptr_t)q8 | (uintptr_t)k8) & 7) == 0 &&
+                     (((uintptr_t)sq | (uintptr_t)sk) & 3) == 0,
+                 "fg_attn_quant_qk_bf16_b: q, k, scratch must be 16-byte aligned (q8, k8: 8; sq, sk: 4)");
+    FG_CHECK_ARG(scratch_bytes >= hd * 4, "fg_attn_quant_qk_bf16_b: scratch must hold H*D floats per element (%lld bytes, got %lld)",
+                 (long long)(hd * 4), (long long)scratch_bytes);
+    FG_CHECK_ARG(bs_q >= (N - 1) * ldq + hd && bs_k >= (N - 1) * ldk + hd && bs_q8 >= N * hd && bs_k8 >= N * hd && bs_sq >= N * H &&
+                     bs_sk >= H && bs_scratch >= hd * 4,
+                 "fg_attn_quant_qk_bf16_b: a batch stride is smaller than one element of its operand");
+    FG_CHECK_ARG(bs_q % 8 == 0 && bs_k % 8 == 0 && bs_q8 % 8 == 0 && bs_k8 % 8 == 0 && bs_scratch % 16 == 0,
+                 "fg_attn_quant_qk_bf16_b: batch strides must keep the alignment (q, k: 8 elements; q8, k8: 8 bytes; scratch: 16 bytes)");
+    FG_CHECK_ARG((N + 15) / 16 < (1ll << 31), "fg_attn_quant_qk_bf16_b: grid too large");
+    const QuantQkStrides bs{bs_q, bs_k, bs_q8, bs_k8, bs_sq, bs_sk, bs_scratch / 4};
+    hipLaunchKernelGGL(attn_k_stats_b_kernel, dim3((unsigned)H, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, (const bf16*)k, ldk,
+                       (float*)scratch, sk, N, bs);
+    if (int e = fg_launch_status("fg_attn_quant_qk_bf16_b (k statistics)")) return e;
+    hipLaunchKernelGGL(attn_quant_qk_b_kernel, dim3((unsigned)((N + 15) / 16), (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16*)q, ldq, (const bf16*)k, ldk, (const float*)scratch, (const float*)sk, (uint8_t*)q8, (uint8_t*)k8, sq, N, H,
+                       bs);
+    return fg_launch_status("fg_attn_quant_qk_bf16_b");
 }

@@ -11,6 +11,7 @@
 // mean.  The scale: fl(v - m) is monotone in v, so max over rows of |fl(v - m)| is max(fl(vmax - m), fl(m - vmin)).
 // Per q/k element pair 10 bytes of HBM traffic (q 2 in 1 out, k 2 in 2 out, then 2 in 1 out) where the two-step path moves 18.
 #include "common.h"
+#include "../../include/fairygen_hip_batch8.h"
 #include "rmsnorm_rope_row.h"
 #include "attn_qk8_quant.h"
 
@@ -34,29 +35,19 @@ __global__ __launch_bounds__(256, 4) void rmsnorm_rope_q8_kernel(const bf16* __r
                                                                  const void* __restrict__ ctv, const void* __restrict__ stv,
                                                                  uint8_t* __restrict__ q8, float* __restrict__ sq, int64_t rows, int C,
                                                                  float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = C >> 3, H = C >> 7;
-    Row r;
-    load_row(x + row * ldx, C, lane, r);
-    const RopeRow rr = rope_begin<F32TAB, true>(r, ctv, row, C, kD, eps, lane);
-#pragma unroll
-    for (int i = 0; i < kMaxVec; ++i) {
-        const int vi = lane + i * 64;
-        if (vi < nvec) {         // nvec is a multiple of 16: the 16 lanes of a head are in or out together
-            float o[8];
-            rope_vec<F32TAB, true>(rr, r.v[i], ld8(w + (int64_t)vi * 8), ctv, stv, row, kD, vi, o);
-            float amax = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(o[j]));
-#pragma unroll
-            for (int s = 8; s > 0; s >>= 1) amax = fmaxf(amax, __shfl_xor(amax, s, 64));
-            const float s_q = fmaxf(amax / kE4M3Max, kScaleFloor);
-            *reinterpret_cast<u32x2*>(q8 + row * C + (int64_t)vi * 8) = quant8_e4m3(o, s_q);
-            if ((lane & 15) == 0) sq[row * H + (vi >> 4)] = s_q;
-        }
-    }
+#include "rmsnorm_rope_q8_body.inc"
+}
+
+// The batched forms (include/fairygen_hip_batch8.h): the last grid dimension picks the batch element — `rows` rows of the one matrix x,
+// the table rows 0 .. rows - 1 — and the element runs the body of the single-element kernel on its own pointers.
+template <bool F32TAB>
+__global__ __launch_bounds__(256, 4) void rmsnorm_rope_q8_b_kernel(const bf16* __restrict__ x, int64_t ldx, const bf16* __restrict__ w,
+                                                                   const void* __restrict__ ctv, const void* __restrict__ stv,
+                                                                   uint8_t* __restrict__ q8, float* __restrict__ sq, int64_t rows, int C,
+                                                                   float eps) {
+    const int64_t r0 = (int64_t)blockIdx.y * rows;
+    x += r0 * ldx; q8 += r0 * C; sq += r0 * (C >> 7);
+#include "rmsnorm_rope_q8_body.inc"
 }
 
 // The norm of rmsnorm_rope_kernel over the rows 4 (blockIdx + gridDim i) + wave, NV = ceil(C / 512) vectors a lane: every lane keeps
@@ -68,119 +59,47 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kstats_kernel(const bf16* __
                                                                   bf16* __restrict__ out, double* __restrict__ psum,
                                                                   float* __restrict__ pmin, float* __restrict__ pmax, int64_t rows,
                                                                   int C, float eps) {
-    __shared__ double sum_s[NV * 512];       // [vector slot][element][lane]: conflict-free
-    __shared__ float min_s[NV * 512], max_s[NV * 512];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nvec = C >> 3;
-    double sum[NV][8];
-    float mn[NV][8], mx[NV][8];
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            sum[i][j] = 0.0;
-            mn[i][j] = INFINITY;
-            mx[i][j] = -INFINITY;
-        }
-    for (int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + wave; row < rows; row += (int64_t)gridDim.x * kRowsPerBlock) {
-        RowT<NV> r;
-        load_row(x + row * ldx, C, lane, r);
-        const RopeRow rr = rope_begin<F32TAB, true>(r, ctv, row, C, kD, eps, lane);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int vi = lane + i * 64;
-            if (vi < nvec) {
-                float o[8];
-                rope_vec<F32TAB, true>(rr, r.v[i], ld8(w + (int64_t)vi * 8), ctv, stv, row, kD, vi, o);
-                st8(out + row * C + (int64_t)vi * 8, o);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    sum[i][j] += (double)o[j];
-                    mn[i][j] = fminf(mn[i][j], o[j]);
-                    mx[i][j] = fmaxf(mx[i][j], o[j]);
-                }
-            }
-        }
-    }
-    for (int wv = 1; wv < kRowsPerBlock; ++wv) {
-        if (wave == wv) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    sum_s[(i * 8 + j) * 64 + lane] = sum[i][j];
-                    min_s[(i * 8 + j) * 64 + lane] = mn[i][j];
-                    max_s[(i * 8 + j) * 64 + lane] = mx[i][j];
-                }
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    sum[i][j] += sum_s[(i * 8 + j) * 64 + lane];
-                    mn[i][j] = fminf(mn[i][j], min_s[(i * 8 + j) * 64 + lane]);
-                    mx[i][j] = fmaxf(mx[i][j], max_s[(i * 8 + j) * 64 + lane]);
-                }
-        }
-        __syncthreads();
-    }
-    if (wave != 0) return;
-    const int64_t base = (int64_t)blockIdx.x * C;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int vi = lane + i * 64;
-        if (vi < nvec) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                psum[base + vi * 8 + j] = sum[i][j];
-                pmin[base + vi * 8 + j] = mn[i][j];
-                pmax[base + vi * 8 + j] = mx[i][j];
-            }
-        }
-    }
+#include "rmsnorm_rope_kstats_body.inc"
+}
+
+// batched: element blockIdx.y; its partials block (gridDim.x records: sums, minima, maxima) lies bs_partials bytes behind the previous one
+template <bool F32TAB, int NV>
+__global__ __launch_bounds__(256) void rmsnorm_rope_kstats_b_kernel(const bf16* __restrict__ x, int64_t ldx, const bf16* __restrict__ w,
+                                                                    const void* __restrict__ ctv, const void* __restrict__ stv,
+                                                                    bf16* __restrict__ out, char* __restrict__ partials,
+                                                                    int64_t bs_partials, int64_t rows, int C, float eps) {
+    const int64_t r0 = (int64_t)blockIdx.y * rows, pc = (int64_t)gridDim.x * C;
+    double* __restrict__ psum = reinterpret_cast<double*>(partials + (int64_t)blockIdx.y * bs_partials);
+    float* __restrict__ pmin = reinterpret_cast<float*>(psum + pc);
+    float* __restrict__ pmax = pmin + pc;
+    x += r0 * ldx; out += r0 * C;
+#include "rmsnorm_rope_kstats_body.inc"
 }
 
 // One workgroup of 1024 per head: thread t reduces channel t & 127 over the records (t >> 7) + 8 i, LDS joins the 8 groups.
 __global__ __launch_bounds__(1024) void attn_k_finalise_kernel(const double* __restrict__ psum, const float* __restrict__ pmin,
                                                                const float* __restrict__ pmax, int P, int C, float* __restrict__ kbar,
                                                                float* __restrict__ sk, int64_t N) {
-    __shared__ double sum_s[8][kD];
-    __shared__ float min_s[8][kD], max_s[8][kD];
-    __shared__ float amax_s[2];
-    const int h = blockIdx.x, tid = threadIdx.x, c = tid & (kD - 1), g = tid >> 7;
-    double s = 0.0;
-    float lo = INFINITY, hi = -INFINITY;
-    for (int p = g; p < P; p += 8) {
-        const int64_t o = (int64_t)p * C + h * kD + c;
-        s += psum[o];
-        lo = fminf(lo, pmin[o]);
-        hi = fmaxf(hi, pmax[o]);
-    }
-    sum_s[g][c] = s;
-    min_s[g][c] = lo;
-    max_s[g][c] = hi;
-    __syncthreads();
-    if (tid < kD) {
-#pragma unroll
-        for (int i = 1; i < 8; ++i) {
-            s += sum_s[i][c];
-            lo = fminf(lo, min_s[i][c]);
-            hi = fmaxf(hi, max_s[i][c]);
-        }
-        const float m = (float)(s / (double)N);
-        kbar[h * kD + c] = m;
-        const float amax = wave_max(fmaxf(hi - m, m - lo));
-        if ((tid & 63) == 0) amax_s[tid >> 6] = amax;
-    }
-    __syncthreads();
-    if (tid == 0) sk[h] = fmaxf(fmaxf(amax_s[0], amax_s[1]) / kE4M3Max, kScaleFloor);
+#include "attn_k_finalise_body.inc"
+}
+
+struct QuantKStrides {
+    int64_t k, partials, k8, sk, kbar;
+};
+
+__global__ __launch_bounds__(1024) void attn_k_finalise_b_kernel(const char* __restrict__ partials, int P, int C, float* __restrict__ kbar,
+                                                                 float* __restrict__ sk, int64_t N, const QuantKStrides bs) {
+    const int64_t b = blockIdx.y, pc = (int64_t)P * C;
+    const double* __restrict__ psum = reinterpret_cast<const double*>(partials + b * bs.partials);
+    const float* __restrict__ pmin = reinterpret_cast<const float*>(psum + pc);
+    const float* __restrict__ pmax = pmin + pc;
+    kbar += b * bs.kbar; sk += b * bs.sk;
+#include "attn_k_finalise_body.inc"
 }
 
 // The k half of attn_quant_qk_kernel: 16 rows of one head per workgroup of 256, 16 lanes x 8 channels cover a row.
-__global__ __launch_bounds__(256) void attn_quant_k_kernel(const bf16* __restrict__ k, int64_t ldk, const float* __restrict__ kbar,
-                                                           const float* __restrict__ sk, uint8_t* __restrict__ k8, int64_t N, int H) {
+__device__ __forceinline__ void attn_quant_k_body(const bf16* __restrict__ k, int64_t ldk, const float* __restrict__ kbar,
+                                                  const float* __restrict__ sk, uint8_t* __restrict__ k8, int64_t N, int H) {
     const int h = blockIdx.y, tid = threadIdx.x, c = tid & 15;
     const int64_t row = (int64_t)blockIdx.x * 16 + (tid >> 4);
     if (row >= N) return;
@@ -191,6 +110,18 @@ __global__ __launch_bounds__(256) void attn_quant_k_kernel(const bf16* __restric
 #pragma unroll
     for (int j = 0; j < 8; ++j) kf[j] = (float)kv[j] - (j < 4 ? m0[j & 3] : m1[j & 3]);
     *reinterpret_cast<u32x2*>(k8 + (row * H + h) * kD + c * 8) = quant8_e4m3(kf, s_k);
+}
+
+__global__ __launch_bounds__(256) void attn_quant_k_kernel(const bf16* __restrict__ k, int64_t ldk, const float* __restrict__ kbar,
+                                                           const float* __restrict__ sk, uint8_t* __restrict__ k8, int64_t N, int H) {
+    attn_quant_k_body(k, ldk, kbar, sk, k8, N, H);
+}
+
+__global__ __launch_bounds__(256) void attn_quant_k_b_kernel(const bf16* __restrict__ k, int64_t ldk, const float* __restrict__ kbar,
+                                                             const float* __restrict__ sk, uint8_t* __restrict__ k8, int64_t N, int H,
+                                                             const QuantKStrides bs) {
+    const int64_t b = blockIdx.z;
+    attn_quant_k_body(k + b * bs.k, ldk, kbar + b * bs.kbar, sk + b * bs.sk, k8 + b * bs.k8, N, H);
 }
 
 // The checks the two producers share; C = num_heads * 128 <= 4096.
@@ -288,4 +219,80 @@ extern "C" int fg_attn_quant_k_bf16(const void* k, int64_t ldk, const void* part
     hipLaunchKernelGGL(attn_quant_k_kernel, dim3((unsigned)((N + 15) / 16), (unsigned)H), dim3(256), 0, (hipStream_t)stream, (const bf16*)k, ldk,
                        (const float*)kbar, (const float*)sk, (uint8_t*)k8, N, H);
     return fg_launch_status("fg_attn_quant_k_bf16");
+}
+
+// ---- the batched forms (include/fairygen_hip_batch8.h): the same launches with the batch as one more grid dimension
+extern "C" int fg_rmsnorm_rope_q8_bf16_b(const void* x, int64_t ldx, const void* weight, const void* cos_tab, const void* sin_tab,
+                                         int table_f32, void* q8, float* sq, int B, int64_t rows, int C, int num_heads, float eps,
+                                         fg_stream_t stream) {
+    FG_CHECK_ARG(q8 && sq, "fg_rmsnorm_rope_q8_bf16_b: null pointer");
+    FG_CHECK_ARG(B >= 1 && B <= 65535, "fg_rmsnorm_rope_q8_bf16_b: B must be in 1..65535 (got %d)", B);
+    if (int e = check_producer("fg_rmsnorm_rope_q8_bf16_b", x, ldx, weight, cos_tab, sin_tab, table_f32, rows, C, num_heads)) return e;
+    FG_CHECK_ARG((((uintptr_t)q8) & 7) == 0 && (((uintptr_t)sq) & 3) == 0, "fg_rmsnorm_rope_q8_bf16_b: q8 must be 8-byte aligned (sq: 4)");
+    const dim3 grid((unsigned)((rows + kRowsPerBlock - 1) / kRowsPerBlock), (unsigned)B);
+    if (table_f32)
+        hipLaunchKernelGGL(rmsnorm_rope_q8_b_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, ldx, (const bf16*)weight,
+                           cos_tab, sin_tab, (uint8_t*)q8, sq, rows, C, eps);
+    else
+        hipLaunchKernelGGL(rmsnorm_rope_q8_b_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, ldx, (const bf16*)weight,
+                           cos_tab, sin_tab, (uint8_t*)q8, sq, rows, C, eps);
+    return fg_launch_status("fg_rmsnorm_rope_q8_bf16_b");
+}
+
+extern "C" int fg_rmsnorm_rope_kstats_bf16_b(const void* x, int64_t ldx, const void* weight, const void* cos_tab, const void* sin_tab,
+                                             int table_f32, void* k_out, void* partials, int64_t partials_bytes, int64_t bs_partials, int B,
+                                             int64_t rows, int C, int num_heads, float eps, fg_stream_t stream) {
+    FG_CHECK_ARG(k_out && partials, "fg_rmsnorm_rope_kstats_bf16_b: null pointer");
+    FG_CHECK_ARG(B >= 1 && B <= 65535, "fg_rmsnorm_rope_kstats_bf16_b: B must be in 1..65535 (got %d)", B);
+    if (int e = check_producer("fg_rmsnorm_rope_kstats_bf16_b", x, ldx, weight, cos_tab, sin_tab, table_f32, rows, C, num_heads)) return e;
+    FG_CHECK_ARG(FG_ALIGNED16(k_out) && FG_ALIGNED16(partials), "fg_rmsnorm_rope_kstats_bf16_b: k_out and partials must be 16-byte aligned");
+    FG_CHECK_ARG(partials_bytes >= partials_bytes_for(rows, C),
+                 "fg_rmsnorm_rope_kstats_bf16_b: partials must hold %lld bytes per element (got %lld)", (long long)partials_bytes_for(rows, C),
+                 (long long)partials_bytes);
+    FG_CHECK_ARG(bs_partials >= partials_bytes_for(rows, C) && bs_partials % 16 == 0,
+                 "fg_rmsnorm_rope_kstats_bf16_b: the batch stride of partials must cover one element's block and be a multiple of 16");
+    const int64_t P = stat_parts(rows);
+#define FG_KSTATS_LAUNCH(TAB, NV)                                                                                                      \
+    hipLaunchKernelGGL((rmsnorm_rope_kstats_b_kernel<TAB, NV>), dim3((unsigned)P, (unsigned)B), dim3(256), 0, (hipStream_t)stream,      \
+                       (const bf16*)x, ldx, (const bf16*)weight, cos_tab, sin_tab, (bf16*)k_out, (char*)partials, bs_partials, rows, C, eps)
+#define FG_KSTATS_CASE(NV)                                            \
+    case NV:                                                          \
+        if (table_f32) FG_KSTATS_LAUNCH(true, NV);                    \
+        else FG_KSTATS_LAUNCH(false, NV);                             \
+        break;
+    switch ((C + 511) / 512) {
+        FG_KSTATS_CASE(1) FG_KSTATS_CASE(2) FG_KSTATS_CASE(3) FG_KSTATS_CASE(4)
+        FG_KSTATS_CASE(5) FG_KSTATS_CASE(6) FG_KSTATS_CASE(7) FG_KSTATS_CASE(8)
+    }
+#undef FG_KSTATS_CASE
+#undef FG_KSTATS_LAUNCH
+    return fg_launch_status("fg_rmsnorm_rope_kstats_bf16_b");
+}
+
+extern "C" int fg_attn_quant_k_bf16_b(const void* k, int64_t ldk, int64_t bs_k, const void* partials, int64_t partials_bytes,
+                                      int64_t bs_partials, void* k8, int64_t bs_k8, float* sk, int64_t bs_sk, float* kbar, int64_t bs_kbar,
+                                      int B, int64_t N, int H, int D, fg_stream_t stream) {
+    FG_CHECK_ARG(k && partials && k8 && sk && kbar, "fg_attn_quant_k_bf16_b: null pointer");
+    FG_CHECK_ARG(D == kD, "fg_attn_quant_k_bf16_b: only head_dim 128 is supported (got %d)", D);
+    FG_CHECK_ARG(B >= 1 && B <= 65535, "fg_attn_quant_k_bf16_b: B must be in 1..65535 (got %d)", B);
+    FG_CHECK_ARG(N > 0 && H > 0 && H <= kMaxVec * 4, "fg_attn_quant_k_bf16_b: N must be positive, H in 1..%d", kMaxVec * 4);
+    const int C = H * kD;
+    FG_CHECK_ARG(ldk >= C && ldk % 8 == 0, "fg_attn_quant_k_bf16_b: ldk must be >= H*D and a multiple of 8");
+    FG_CHECK_ARG(FG_ALIGNED16(k) && FG_ALIGNED16(partials) && FG_ALIGNED16(kbar) && (((uintptr_t)k8) & 7) == 0 && (((uintptr_t)sk) & 3) == 0,
+                 "fg_attn_quant_k_bf16_b: k, partials, kbar must be 16-byte aligned (k8: 8; sk: 4)");
+    FG_CHECK_ARG(partials_bytes >= partials_bytes_for(N, C), "fg_attn_quant_k_bf16_b: partials must hold %lld bytes per element (got %lld)",
+                 (long long)partials_bytes_for(N, C), (long long)partials_bytes);
+    FG_CHECK_ARG(bs_k >= (N - 1) * ldk + C && bs_partials >= partials_bytes_for(N, C) && bs_k8 >= N * C && bs_sk >= H && bs_kbar >= C,
+                 "fg_attn_quant_k_bf16_b: a batch stride is smaller than one element of its operand");
+    FG_CHECK_ARG(bs_k % 8 == 0 && bs_partials % 16 == 0 && bs_k8 % 8 == 0 && bs_kbar % 4 == 0,
+                 "fg_attn_quant_k_bf16_b: batch strides must keep the alignment (k: 8 elements; partials: 16 bytes; k8: 8 bytes; kbar: 4 floats)");
+    FG_CHECK_ARG((N + 15) / 16 < (1ll << 31), "fg_attn_quant_k_bf16_b: grid too large");
+    const int64_t P = stat_parts(N);
+    const QuantKStrides bs{bs_k, bs_partials, bs_k8, bs_sk, bs_kbar};
+    hipLaunchKernelGGL(attn_k_finalise_b_kernel, dim3((unsigned)H, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, (const char*)partials,
+                       (int)P, C, kbar, sk, N, bs);
+    if (int e = fg_launch_status("fg_attn_quant_k_bf16_b (k statistics)")) return e;
+    hipLaunchKernelGGL(attn_quant_k_b_kernel, dim3((unsigned)((N + 15) / 16), (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16*)k, ldk, (const float*)kbar, (const float*)sk, (uint8_t*)k8, N, H, bs);
+    return fg_launch_status("fg_attn_quant_k_bf16_b");
 }

@@ -124,6 +124,27 @@ _CROSS8_QUERIES = {
 }
 CROSS8_SYMBOLS = sorted(list(_CROSS8_SIGNATURES) + list(_CROSS8_QUERIES))    # what include/fairygen_hip_cross8.h declares
 
+# The extension of include/fairygen_hip_batch8.h (the whole e4m3 attention chain on a batch, one launch sequence): a fifth pair of tables.
+BATCH8_ABI_VERSION = 1    # fg_attn_batch8_version
+_BATCH8_SIGNATURES = {
+    "fg_attn_quant_qk_bf16_b": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i64,
+                                _i32, _i32, _vp],
+    "fg_rmsnorm_rope_q8_bf16_b": [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _vp],
+    "fg_rmsnorm_rope_kstats_bf16_b": [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _i64, _i32, _i32, _f32, _vp],
+    "fg_attn_quant_k_bf16_b": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _i32, _i32, _vp],
+    "fg_attn_quant_vt_bf16_b": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i64, _i32, _i32, _vp],
+    "fg_attn_fwd_qk8_bf16_b": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _i32, _f32, _vp,
+                               _i64, _vp],
+    "fg_attn_fwd_pv8_bf16_b": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _i32, _f32,
+                               _vp, _i64, _vp],
+    "fg_attn_fwd_cross8_bf16_b": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _i32,
+                                  _f32, _vp],
+}
+_BATCH8_QUERIES = {
+    "fg_attn_batch8_version": (_i32, []),
+}
+BATCH8_SYMBOLS = sorted(list(_BATCH8_SIGNATURES) + list(_BATCH8_QUERIES))    # what include/fairygen_hip_batch8.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -144,16 +165,17 @@ def load():
             "fairygen_amd has no CPU / PyTorch fallback for its kernels.")
     lib = ctypes.CDLL(_LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
-            list(_CROSS8_SIGNATURES.items()):
+            list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
-            list(_CROSS8_QUERIES.items()):
+            list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
                                  ("fg_attn_pv8_version", PV8_ABI_VERSION, " (e4m3 P V extension)"),
                                  ("fg_attn_shard8_version", SHARD8_ABI_VERSION, " (e4m3 operands of a token shard)"),
-                                 ("fg_attn_cross8_version", CROSS8_ABI_VERSION, " (e4m3 cross-attention, K8 / V8^T in LDS)")):
+                                 ("fg_attn_cross8_version", CROSS8_ABI_VERSION, " (e4m3 cross-attention, K8 / V8^T in LDS)"),
+                                 ("fg_attn_batch8_version", BATCH8_ABI_VERSION, " (e4m3 attention on batches)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -676,10 +698,11 @@ def _ld_rows(t, name):
 _attn_workspace = {}      # (device, stream) -> scratch tensor for the split-KV partials (grown on demand, reused)
 
 
-def _attn_ws(device, b, nq, nkv, num_heads, workspace):
+def _attn_ws(device, b, nq, nkv, num_heads, workspace, per_element=False):
     """(ws, need): the split-KV scratch of an attention launch and the bytes it wants (0: none).  ws is the tensor of the caller's list
-    `workspace`, or with None the one kept for (device, current stream); either is grown here when it is smaller than need."""
-    need = load().fg_attn_workspace_bytes(b, nq, nkv, num_heads)
+    `workspace`, or with None the one kept for (device, current stream); either is grown here when it is smaller than need.
+    per_element (the batched e4m3 forms, include/fairygen_hip_batch8.h): b shares of what ONE element's plan wants."""
+    need = b * load().fg_attn_workspace_bytes(1, nq, nkv, num_heads) if per_element else load().fg_attn_workspace_bytes(b, nq, nkv, num_heads)
     if workspace is not None:
         ws = workspace[0] if workspace else None
         if need > 0 and (ws is None or ws.numel() < need or ws.device != device):
@@ -717,9 +740,15 @@ def attention(q, k, v, num_heads, out=None, scale=None, workspace=None):
     return out
 
 
-def attention_qk8_scratch(n, num_heads, head_dim, device):
-    """The buffers fg_attn_quant_qk_bf16 fills for (n, num_heads * head_dim) q and k: (q8, k8, sq, sk, kbar scratch)."""
+def attention_qk8_scratch(n, num_heads, head_dim, device, batch=1):
+    """The buffers fg_attn_quant_qk_bf16 fills for (n, num_heads * head_dim) q and k: (q8, k8, sq, sk, kbar scratch).  batch > 1: the
+    same five with a leading batch dimension, for the batched entry points (include/fairygen_hip_batch8.h)."""
     hd = num_heads * head_dim
+    if batch > 1:
+        f8, f32 = torch.float8_e4m3fn, torch.float32
+        return (torch.empty((batch, n, hd), dtype=f8, device=device), torch.empty((batch, n, hd), dtype=f8, device=device),
+                torch.empty((batch, n, num_heads), dtype=f32, device=device), torch.empty((batch, num_heads), dtype=f32, device=device),
+                torch.empty((batch, hd), dtype=f32, device=device))
     return (torch.empty((n, hd), dtype=torch.float8_e4m3fn, device=device), torch.empty((n, hd), dtype=torch.float8_e4m3fn, device=device),
             torch.empty((n, num_heads), dtype=torch.float32, device=device), torch.empty(num_heads, dtype=torch.float32, device=device),
             torch.empty(hd, dtype=torch.float32, device=device))
@@ -730,6 +759,15 @@ def attn_quant_qk(q, k, num_heads, bufs=None):
     one scale per head, Q with one scale per row and head (include/fairygen_hip.h).  bufs: attention_qk8_scratch's tuple, else allocated."""
     ldq, ldk = _ld_rows(q, "q"), _ld_rows(k, "k")
     b, n, hd = q.shape
+    if b > 1 and k.shape == q.shape:      # a batch: fg_attn_quant_qk_bf16_b, every statistic per element
+        bufs = attention_qk8_scratch(n, num_heads, hd // num_heads, q.device, b) if bufs is None else bufs
+        q8, k8, sq, sk, kbar = bufs
+        if q8.shape != (b, n, hd) or k8.shape != (b, n, hd) or sq.shape != (b, n, num_heads) or sk.shape != (b, num_heads) or \
+                kbar.shape != (b, hd) or not all(t.is_contiguous() for t in bufs):
+            raise HipLibraryError("attn_quant_qk: bufs do not match (B, N, H*D)")
+        _call("fg_attn_quant_qk_bf16_b", _ptr(q), ldq, q.stride(0), _ptr(k), ldk, k.stride(0), _ptr(q8), n * hd, _ptr(k8), n * hd, _ptr(sq),
+              n * num_heads, _ptr(sk), num_heads, _ptr(kbar), hd * 4, hd * 4, b, n, num_heads, hd // num_heads, _stream(q))
+        return bufs
     if b != 1 or k.shape != q.shape:
         raise HipLibraryError(f"attn_quant_qk: q and k must both be (1, N, H*D), got {tuple(q.shape)} and {tuple(k.shape)}")
     bufs = attention_qk8_scratch(n, num_heads, hd // num_heads, q.device) if bufs is None else bufs
@@ -741,16 +779,18 @@ def attn_quant_qk(q, k, num_heads, bufs=None):
     return bufs
 
 
-def attention_pv8_scratch(n, num_heads, head_dim, device):
+def attention_pv8_scratch(n, num_heads, head_dim, device, batch=1):
     """The buffers fg_attn_quant_vt_bf16 fills for (n, num_heads * head_dim) v: (v8t (H, 128, n rounded up to 64) e4m3, sv (H, 128) fp32,
-    the statistics scratch)."""
+    the statistics scratch).  batch > 1: the same three with a leading batch dimension (include/fairygen_hip_batch8.h)."""
     if head_dim != 128:
         raise HipLibraryError(f"attention_pv8_scratch: only head_dim 128 is supported (got {head_dim})")
     need = load().fg_attn_pv8_scratch_bytes(n, num_heads)
     if need < 0:
         raise HipLibraryError(f"attention_pv8_scratch: {load().fg_last_error().decode()}")
-    return (torch.empty((num_heads, head_dim, (n + 63) // 64 * 64), dtype=torch.float8_e4m3fn, device=device),
-            torch.empty((num_heads, head_dim), dtype=torch.float32, device=device), torch.empty(need, dtype=torch.uint8, device=device))
+    lead = (batch,) if batch > 1 else ()
+    return (torch.empty(lead + (num_heads, head_dim, (n + 63) // 64 * 64), dtype=torch.float8_e4m3fn, device=device),
+            torch.empty(lead + (num_heads, head_dim), dtype=torch.float32, device=device),
+            torch.empty(lead + (need,), dtype=torch.uint8, device=device))
 
 
 def attn_quant_vt(v, num_heads, bufs=None):
@@ -758,6 +798,16 @@ def attn_quant_vt(v, num_heads, bufs=None):
     head and channel, the bytes transposed and tile-ordered by PV8_KEY_ORDER (include/fairygen_hip_pv8.h).  bufs: attention_pv8_scratch's."""
     ldv = _ld_rows(v, "v")
     b, n, hd = v.shape
+    if b > 1:      # a batch: fg_attn_quant_vt_bf16_b, sv per element
+        bufs = attention_pv8_scratch(n, num_heads, hd // num_heads, v.device, b) if bufs is None else bufs
+        v8t, sv, scratch = bufs
+        nkp = (n + 63) // 64 * 64
+        if v8t.shape != (b, num_heads, hd // num_heads, nkp) or sv.shape != (b, num_heads, hd // num_heads) or scratch.dim() != 2 or \
+                scratch.shape[0] != b or not all(t.is_contiguous() for t in bufs):
+            raise HipLibraryError("attn_quant_vt: bufs do not match (B, N, H*D)")
+        _call("fg_attn_quant_vt_bf16_b", _ptr(v), ldv, v.stride(0), _ptr(v8t), hd * nkp, _ptr(sv), hd, _ptr(scratch), scratch.shape[1],
+              scratch.stride(0), b, n, num_heads, hd // num_heads, _stream(v))
+        return bufs
     if b != 1:
         raise HipLibraryError(f"attn_quant_vt: v must be (1, N, H*D), got {tuple(v.shape)}")
     bufs = attention_pv8_scratch(n, num_heads, hd // num_heads, v.device) if bufs is None else bufs
@@ -775,6 +825,20 @@ def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, worksp
     allocated), then fg_attn_fwd_pv8_bf16."""
     ldv = _ld_rows(v, "v")
     b, nkv, hd = v.shape
+    if b > 1 and q8.dim() == 3:      # a batch of operands (attn_quant_qk's, or the fused producers', on a batch): the _b entry points
+        nq, d = q8.shape[1], hd // num_heads
+        if q8.shape != (b, nq, hd) or k8.shape != (b, nkv, hd) or sq.shape != (b, nq, num_heads) or sk.shape != (b, num_heads) or \
+                not all(t.is_contiguous() for t in (q8, k8, sq, sk)):
+            raise HipLibraryError(f"attention_qk8_pre: k8 and sk for v {tuple(v.shape)}, sq for q8 {tuple(q8.shape)}, all contiguous")
+        if pv8:
+            v8t, sv, _ = attn_quant_vt(v, num_heads, pv8_bufs)
+            return attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=out, scale=scale, workspace=workspace)
+        out = torch.empty((b, nq, hd), dtype=v.dtype, device=v.device) if out is None else out
+        ws, need = _attn_ws(v.device, b, nq, nkv, num_heads, workspace, per_element=True)
+        _call("fg_attn_fwd_qk8_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v), ldv,
+              v.stride(0), _ptr(out), nq * hd, b, nq, nkv, num_heads, d, float(d) ** -0.5 if scale is None else float(scale),
+              _ptr(ws) if need > 0 else None, need, _stream(v))
+        return out
     nq, d = q8.shape[0], hd // num_heads
     if b != 1 or q8.shape != (nq, hd) or k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads:
         raise HipLibraryError(f"attention_qk8_pre: one batch element, k8 and sk for v {tuple(v.shape)}, sq for q8 {tuple(q8.shape)}")
@@ -790,10 +854,28 @@ def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, worksp
     return out
 
 
+def _batch8_check(who, q8, k8, sq, sk, v8t, sv, num_heads):
+    """(B, Nq, H*D, Nkv, D) of a batch of ready e4m3 operands, each contiguous with a leading batch dimension."""
+    (b, nq, hd), nkv = q8.shape, k8.shape[1]
+    d = hd // num_heads
+    if k8.shape != (b, nkv, hd) or sq.shape != (b, nq, num_heads) or sk.shape != (b, num_heads) or sv.shape != (b, num_heads, d) or \
+            v8t.shape != (b, num_heads, d, (nkv + 63) // 64 * 64) or not all(t.is_contiguous() for t in (q8, k8, sq, sk, v8t, sv)):
+        raise HipLibraryError(f"{who}: k8, sq, sk, v8t, sv do not match the batch q8 {tuple(q8.shape)} and {nkv} keys (all contiguous)")
+    return b, nq, hd, nkv, d
+
+
 def attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None, workspace=None):
     """fg_attn_fwd_pv8_bf16 on operands that are ALL ready: q8 (Nq, H*128), k8 (Nkv, H*128) e4m3, sq (Nq, H), sk (H), v8t (H, 128, Nkv
     rounded up to 64) e4m3 and sv (H, 128) as attn_quant_vt or attn_shard8_vt left them -> (1, Nq, H*128) bf16.  Nq need not be Nkv (a
-    token shard's queries against all keys).  workspace as in attention()."""
+    token shard's queries against all keys).  workspace as in attention().  With a leading batch dimension on all six: the batched form."""
+    if q8.dim() == 3:
+        b, nq, hd, nkv, d = _batch8_check("attention_pv8_pre", q8, k8, sq, sk, v8t, sv, num_heads)
+        out = torch.empty((b, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
+        ws, need = _attn_ws(q8.device, b, nq, nkv, num_heads, workspace, per_element=True)
+        _call("fg_attn_fwd_pv8_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
+              v8t.stride(0), _ptr(sv), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d, float(d) ** -0.5 if scale is None else float(scale),
+              _ptr(ws) if need > 0 else None, need, _stream(q8))
+        return out
     (nq, hd), nkv = q8.shape, k8.shape[0]
     d = hd // num_heads
     if k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads or sv.numel() != hd or not v8t.is_contiguous() or \
@@ -814,7 +896,14 @@ def attention_cross8_max_kv():
 def attention_cross8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None):
     """fg_attn_fwd_cross8_bf16 (include/fairygen_hip_cross8.h) on attention_pv8_pre's operands, Nkv <= attention_cross8_max_kv(): every
     workgroup keeps its head's K8 and V8^T in LDS and walks many query blocks against them.  One launch, no workspace; the bits of
-    attention_pv8_pre without one."""
+    attention_pv8_pre without one.  With a leading batch dimension on all six: fg_attn_fwd_cross8_bf16_b, each workgroup on ONE element."""
+    if q8.dim() == 3:
+        b, nq, hd, nkv, d = _batch8_check("attention_cross8_pre", q8, k8, sq, sk, v8t, sv, num_heads)
+        out = torch.empty((b, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
+        _call("fg_attn_fwd_cross8_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
+              v8t.stride(0), _ptr(sv), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d, float(d) ** -0.5 if scale is None else float(scale),
+              _stream(q8))
+        return out
     (nq, hd), nkv = q8.shape, k8.shape[0]
     d = hd // num_heads
     if k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads or sv.numel() != hd or not v8t.is_contiguous() or \
@@ -909,13 +998,14 @@ def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs
     return attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=out, scale=scale, workspace=workspace, pv8=pv8, pv8_bufs=pv8_bufs)
 
 
-def attention_qk8_fused_scratch(n, num_heads, head_dim, device):
+def attention_qk8_fused_scratch(n, num_heads, head_dim, device, batch=1):
     """The buffers of the fused producers for (n, num_heads * head_dim) q and k: attention_qk8_scratch's five (q8, k8, sq, sk, the key
     mean) and the key-statistics partials rmsnorm_rope_kstats hands to attn_quant_k."""
     need = load().fg_attn_qk8_fused_scratch_bytes(n, num_heads * head_dim)
     if need < 0:
         raise HipLibraryError(f"attention_qk8_fused_scratch: {load().fg_last_error().decode()}")
-    return attention_qk8_scratch(n, num_heads, head_dim, device) + (torch.empty(need, dtype=torch.uint8, device=device),)
+    return attention_qk8_scratch(n, num_heads, head_dim, device, batch) + \
+        (torch.empty(((batch,) if batch > 1 else ()) + (need,), dtype=torch.uint8, device=device),)
 
 
 def rmsnorm_rope_q8(x, weight, num_heads, eps, cos=None, sin=None, q8=None, sq=None):
@@ -923,6 +1013,16 @@ def rmsnorm_rope_q8(x, weight, num_heads, eps, cos=None, sin=None, q8=None, sq=N
     num_heads)), the bytes attn_quant_qk makes of rmsnorm_rope's output, which is never written."""
     _dev(x, "x"), _dev(weight, "weight")
     c = x.shape[-1]
+    if x.dim() == 3 and x.shape[0] > 1:      # a batch: the B * rows rows of one matrix, the table per element (fg_rmsnorm_rope_q8_bf16_b)
+        ld, (b, rows) = _ld_rows(x, "x"), x.shape[:2]
+        f32tab = _rope_tables("rmsnorm_rope_q8", cos, sin, rows, c // num_heads // 2)
+        q8 = torch.empty((b, rows, c), dtype=torch.float8_e4m3fn, device=x.device) if q8 is None else q8
+        sq = torch.empty((b, rows, num_heads), dtype=torch.float32, device=x.device) if sq is None else sq
+        if q8.shape != (b, rows, c) or sq.shape != (b, rows, num_heads) or not q8.is_contiguous() or not sq.is_contiguous():
+            raise HipLibraryError("rmsnorm_rope_q8: q8 must be (B, rows, C), sq (B, rows, num_heads), contiguous")
+        _call("fg_rmsnorm_rope_q8_bf16_b", _ptr(x), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(q8), _ptr(sq), b, rows, c, num_heads,
+              eps, _stream(x))
+        return q8, sq
     x2 = _rows2d(x, "rmsnorm_rope_q8")
     rows, ld = x2.shape[0], x2.stride(0)
     f32tab = _rope_tables("rmsnorm_rope_q8", cos, sin, rows, c // num_heads // 2)
@@ -940,6 +1040,22 @@ def rmsnorm_rope_kstats(x, weight, num_heads, eps, cos=None, sin=None, out=None,
     bytes, partials (attention_qk8_fused_scratch's last buffer, else allocated) for attn_quant_k."""
     _dev(x, "x"), _dev(weight, "weight")
     c = x.shape[-1]
+    if x.dim() == 3 and x.shape[0] > 1:      # a batch: one partials block per element (fg_rmsnorm_rope_kstats_bf16_b)
+        ld, (b, rows) = _ld_rows(x, "x"), x.shape[:2]
+        f32tab = _rope_tables("rmsnorm_rope_kstats", cos, sin, rows, c // num_heads // 2)
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+        if out.shape != x.shape or not out.is_contiguous():
+            raise HipLibraryError("rmsnorm_rope_kstats: out must be contiguous and of x's shape")
+        if partials is None:
+            need = load().fg_attn_qk8_fused_scratch_bytes(rows, c)
+            if need < 0:
+                raise HipLibraryError(f"rmsnorm_rope_kstats: {load().fg_last_error().decode()}")
+            partials = torch.empty((b, need), dtype=torch.uint8, device=x.device)
+        if partials.dim() != 2 or partials.shape[0] != b or partials.stride(1) != 1:
+            raise HipLibraryError("rmsnorm_rope_kstats: partials of a batch must be (B, bytes)")
+        _call("fg_rmsnorm_rope_kstats_bf16_b", _ptr(x), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(out), _ptr(partials),
+              partials.shape[1], partials.stride(0), b, rows, c, num_heads, eps, _stream(x))
+        return out, partials
     x2 = _rows2d(x, "rmsnorm_rope_kstats")
     rows, ld = x2.shape[0], x2.stride(0)
     f32tab = _rope_tables("rmsnorm_rope_kstats", cos, sin, rows, c // num_heads // 2)
@@ -960,6 +1076,17 @@ def attn_quant_k(k, partials, num_heads, k8=None, sk=None, kbar=None):
     """The e4m3 k operand from rmsnorm_rope_kstats's pair: k (1, N, H*128) bf16 -> (k8 (N, H*128), sk (H), the key mean (H*128))."""
     ldk = _ld_rows(k, "k")
     b, n, hd = k.shape
+    if b > 1:      # a batch: fg_attn_quant_k_bf16_b on rmsnorm_rope_kstats's (B, bytes) partials
+        f32 = torch.float32
+        k8 = torch.empty((b, n, hd), dtype=torch.float8_e4m3fn, device=k.device) if k8 is None else k8
+        sk = torch.empty((b, num_heads), dtype=f32, device=k.device) if sk is None else sk
+        kbar = torch.empty((b, hd), dtype=f32, device=k.device) if kbar is None else kbar
+        if k8.shape != (b, n, hd) or sk.shape != (b, num_heads) or kbar.shape != (b, hd) or partials.dim() != 2 or partials.shape[0] != b or \
+                not all(t.is_contiguous() for t in (k8, sk, kbar)):
+            raise HipLibraryError("attn_quant_k: k8, sk, kbar, partials do not match (B, N, H*D)")
+        _call("fg_attn_quant_k_bf16_b", _ptr(k), ldk, k.stride(0), _ptr(partials), partials.shape[1], partials.stride(0), _ptr(k8), n * hd,
+              _ptr(sk), num_heads, _ptr(kbar), hd, b, n, num_heads, hd // num_heads, _stream(k))
+        return k8, sk, kbar
     if b != 1:
         raise HipLibraryError(f"attn_quant_k: k must be (1, N, H*D), got {tuple(k.shape)}")
     k8 = torch.empty((n, hd), dtype=torch.float8_e4m3fn, device=k.device) if k8 is None else k8
