@@ -19,8 +19,10 @@ NEGATIVE = ("è‰²è°ƒè‰³ä¸½ï¼Œè¿‡æ›ï¼Œé™æ€ï¼Œç»†èŠ‚æ¨¡ç³Šä¸æ¸…ï¼Œå­—å¹•ï¼Œé£æ
             "ç”»å¾—ä¸å¥½çš„æ‰‹éƒ¨ï¼Œç”»å¾—ä¸å¥½çš„è„¸éƒ¨ï¼Œç•¸å½¢çš„ï¼Œæ¯å®¹çš„ï¼Œå½¢æ€ç•¸å½¢çš„è‚¢ä½“ï¼Œæ‰‹æŒ‡èåˆï¼Œé™æ­¢ä¸åŠ¨çš„ç”»é¢ï¼Œæ‚ä¹±çš„èƒŒæ™¯ï¼Œä¸‰æ¡è…¿ï¼ŒèƒŒæ™¯äººå¾ˆå¤šï¼Œå€’ç€èµ°")
 
 
-def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False, cross8=False):
+def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False, cross8=False, stacked_cfg=False):
     dit_cfg = dict(computation_dtype=torch.float8_e4m3fn) if fp8 else {}
+    if stacked_cfg:
+        dit_cfg["stacked_cfg"] = True
     if qk8 or pv8:
         dit_cfg["attention_dtype"] = torch.float8_e4m3fn
     if pv8:
@@ -59,12 +61,15 @@ def main():
                     help="... and e4m3 P V as well (both MFMAs of self-attention 8-bit); implies --qk8-attention")
     ap.add_argument("--cross8-attention", action="store_true",
                     help="... and cross-attention over the text context in the same e4m3 form; implies --pv8-attention")
+    ap.add_argument("--stacked-cfg", action="store_true",
+                    help="both CFG branches in ONE stacked forward of the DiT per step (implies cfg_merge=True); single GPU, bf16 Linears, "
+                         "no unfused --lora adapters")
     a = ap.parse_args()
     pv8 = a.pv8_attention or a.cross8_attention
-    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or pv8, pv8, a.cross8_attention)
+    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or pv8, pv8, a.cross8_attention, a.stacked_cfg)
     image = Image.open(a.image).convert("RGB").resize((832, 480))
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    video = pipe(prompt=a.prompt, negative_prompt=NEGATIVE, input_image=image, num_frames=81, seed=1, tiled=True)
+    video = pipe(prompt=a.prompt, negative_prompt=NEGATIVE, input_image=image, num_frames=81, seed=1, tiled=True, cfg_merge=a.stacked_cfg)
     print("wrote", save_video(video, a.out, fps=15, quality=5))
 
 

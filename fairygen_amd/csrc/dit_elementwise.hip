@@ -4,7 +4,8 @@
 // barrier) and touches every byte exactly once with 16-byte coalesced accesses.
 // Rounding points mirror the reference's bf16 tensor arithmetic op by op (see include/fairygen_hip.h).
 #include "common.h"
-#include "rmsnorm_rope_row.h"      // Row, load_row, ld8, st8 and the RMSNorm+RoPE row arithmetic
+#include "../../include/fairygen_hip_rowbatch.h"      // the batched forms of the row kernels that read a per-row table
+#include "rmsnorm_rope_row.h"     // Row, load_row, ld8, st8 and the RMSNorm+RoPE row arithmetic
 
 // Row kernels (one wave per token row held in registers): second launch-bound = minimum waves per SIMD the register
 // allocation must allow (FG_ROW_MIN_WAVES; measured in tools/microbench.py elementwise).
@@ -161,13 +162,19 @@ __global__ FG_ROW_BOUNDS void ln_modulate_kernel(const bf16* __restrict__ x, con
                                                           const bf16* __restrict__ scale, bf16* __restrict__ out,
                                                           int64_t rows, int C, float eps, int64_t mod_rows,
                                                           int64_t first_rows, int64_t mod_ld) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    Row r;
-    load_row(x + row * C, C, lane, r);
-    const int64_t m = mod_row(row, mod_rows, first_rows);
-    norm_store<0>(r, C, lane, eps, shift + m * mod_ld, scale + m * mod_ld, out + row * C);
+#include "ln_modulate_body.inc"
+}
+
+// The batched forms (include/fairygen_hip_rowbatch.h): x / y / the outputs are the B * rows rows of one matrix, the last grid dimension
+// picks the batch element, and the element runs the body of the single-element kernel on its own pointers — the modulation / RoPE table
+// is ONE element's, read by the row inside the element.  No workgroup holds rows of two elements.
+__global__ FG_ROW_BOUNDS void ln_modulate_b_kernel(const bf16* __restrict__ x, const bf16* __restrict__ shift,
+                                                   const bf16* __restrict__ scale, bf16* __restrict__ out,
+                                                   int64_t rows, int C, float eps, int64_t mod_rows,
+                                                   int64_t first_rows, int64_t mod_ld) {
+    const int64_t e0 = (int64_t)blockIdx.y * rows * C;
+    x += e0; out += e0;
+#include "ln_modulate_body.inc"
 }
 
 __global__ FG_ROW_BOUNDS void ln_affine_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
@@ -190,39 +197,23 @@ __global__ FG_ROW_BOUNDS void residual_kernel(const bf16* __restrict__ x, const 
                                                        int64_t mod_rows, int64_t first_rows, int64_t mod_ld,
                                                        uint8_t* __restrict__ norm_fp8 = nullptr, float* __restrict__ norm_scale = nullptr,
                                                        float fp8_max = 0.f) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = C >> 3;
-    const int64_t m = mod_row(row, mod_rows, first_rows);
-    Row r;
-#pragma unroll
-    for (int i = 0; i < kMaxVec; ++i) {
-        const int vi = lane + i * 64;
-        if (vi < nvec) {
-            const bf16x8 xv = ld8(x + row * C + (int64_t)vi * 8);
-            const bf16x8 yv = ld8(y + row * C + (int64_t)vi * 8);
-            if (gate != nullptr) {
-                const bf16x8 gv = ld8(gate + m * mod_ld + (int64_t)vi * 8);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) r.v[i][j] = rbf((float)xv[j] + rbf((float)gv[j] * (float)yv[j]));
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) r.v[i][j] = rbf((float)xv[j] + (float)yv[j]);
-            }
-            st8(x_out + row * C + (int64_t)vi * 8, r.v[i]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r.v[i][j] = 0.f;
-        }
-    }
-    if (norm_fp8 != nullptr) {      // the norm feeds an fp8 Linear only: e4m3 row + scale instead of the bf16 row
-        if (MODE == 0) norm_store_fp8<0>(r, C, lane, eps, p0 + m * mod_ld, p1 + m * mod_ld, norm_fp8 + row * C, norm_scale + row, fp8_max);
-        if (MODE == 1) norm_store_fp8<1>(r, C, lane, eps, p0, p1, norm_fp8 + row * C, norm_scale + row, fp8_max);
-        return;
-    }
-    if (MODE == 0) norm_store<0>(r, C, lane, eps, p0 + m * mod_ld, p1 + m * mod_ld, norm_out + row * C);
-    if (MODE == 1) norm_store<1>(r, C, lane, eps, p0, p1, norm_out + row * C);
+#include "residual_body.inc"
+}
+
+// batched (bf16 norm output only: the fp8 forms have no batched entry point); MODE -1 has no norm_out
+template <int MODE>
+__global__ FG_ROW_BOUNDS void residual_b_kernel(const bf16* __restrict__ x, const bf16* __restrict__ y,
+                                                const bf16* __restrict__ gate, bf16* __restrict__ x_out,
+                                                const bf16* __restrict__ p0, const bf16* __restrict__ p1,
+                                                bf16* __restrict__ norm_out, int64_t rows, int C, float eps,
+                                                int64_t mod_rows, int64_t first_rows, int64_t mod_ld) {
+    uint8_t* const norm_fp8 = nullptr;
+    float* const norm_scale = nullptr;
+    const float fp8_max = 0.f;
+    const int64_t e0 = (int64_t)blockIdx.y * rows * C;
+    x += e0; y += e0; x_out += e0;
+    if (MODE >= 0) norm_out += e0;
+#include "residual_body.inc"
 }
 
 // RMSNorm over the whole row, * weight, then RoPE on adjacent pairs: the arithmetic and its table modes are rope_begin's and
@@ -234,24 +225,19 @@ __global__ FG_ROW_BOUNDS void rmsnorm_rope_kernel(const bf16* __restrict__ x, in
                                                            const void* __restrict__ stv, bf16* __restrict__ out,
                                                            int64_t rows, int C, int head_dim, float eps, int group_cols,
                                                            int64_t out_group_stride, int64_t out_ld) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    Row r;
-    load_row(x + row * ldx, C, lane, r);
-    const int nvec = C >> 3;
-    const RopeRow rr = rope_begin<F32TAB, PLAIN>(r, ctv, row, C, head_dim, eps, lane);
-#pragma unroll
-    for (int i = 0; i < kMaxVec; ++i) {
-        const int vi = lane + i * 64;
-        if (vi < nvec) {
-            float o[8];
-            rope_vec<F32TAB, PLAIN>(rr, r.v[i], ld8(w + (int64_t)vi * 8), ctv, stv, row, head_dim, vi, o);
-            // column block g = col / group_cols goes to its own (rows, out_ld) plane (group_cols == C: plain rows)
-            const int col = vi * 8, g = PLAIN ? 0 : col / group_cols;
-            st8(out + g * out_group_stride + row * out_ld + (col - g * group_cols), o);
-        }
-    }
+#include "rmsnorm_rope_body.inc"
+}
+
+// batched, plain rows only (no grouped form): x keeps its leading dimension, out is dense
+template <bool F32TAB, bool PLAIN>
+__global__ FG_ROW_BOUNDS void rmsnorm_rope_b_kernel(const bf16* __restrict__ x, int64_t ldx, const bf16* __restrict__ w,
+                                                    const void* __restrict__ ctv, const void* __restrict__ stv,
+                                                    bf16* __restrict__ out, int64_t rows, int C, int head_dim, float eps) {
+    const int group_cols = C;
+    const int64_t out_group_stride = 0, out_ld = C;
+    const int64_t r0 = (int64_t)blockIdx.y * rows;
+    x += r0 * ldx; out += r0 * C;
+#include "rmsnorm_rope_body.inc"
 }
 
 // dst[g][r][0..cols) = src[g][r][0..cols) with independent group / row strides on both sides (16-byte vectors):
@@ -343,6 +329,14 @@ inline int check_rows(const char* fn, int64_t rows, int C, int64_t mod_rows, int
 }
 
 inline dim3 row_grid(int64_t rows) { return dim3((unsigned)((rows + kRowsPerBlock - 1) / kRowsPerBlock)); }
+
+// the batched forms: the workgroups of one element's rows, times B in the second grid dimension (at most 65535)
+inline dim3 row_grid_b(int64_t rows, int B) { return dim3((unsigned)((rows + kRowsPerBlock - 1) / kRowsPerBlock), (unsigned)B); }
+
+inline int check_batch(const char* fn, int B) {
+    FG_CHECK_ARG(B >= 1 && B <= 65535, "%s: B must be in 1..65535 (got %d)", fn, B);
+    return FG_OK;
+}
 
 }  // namespace
 
@@ -576,6 +570,85 @@ int fg_cfg_euler_dev_bf16(const void* latents, const void* posi, const void* neg
     hipLaunchKernelGGL(cfg_euler_dev_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)latents, (const bf16*)posi,
                        (const bf16*)nega, (bf16*)out, n, nvec, cfg_scale, dsigma_table, step, (const bf16*)first, first_n, frame_stride);
     return fg_launch_status("fg_cfg_euler_dev_bf16");
+}
+
+// ---- include/fairygen_hip_rowbatch.h: the row kernels that read a per-row table, on B elements of `rows` rows each.  The checks are
+// those of the single-element entry point on ONE element (rows, mod_rows, first_rows count inside the element), then B.
+int fg_dit_rowbatch_version(void) { return 1; }
+
+int fg_ln_modulate_bf16_b(const void* x, const void* shift, const void* scale, void* out, int B, int64_t rows, int C, float eps,
+                          int64_t mod_rows, int64_t first_rows, int64_t mod_ld, fg_stream_t stream) {
+    if (int e = check_rows("fg_ln_modulate_bf16_b", rows, C, mod_rows, first_rows)) return e;
+    if (int e = check_batch("fg_ln_modulate_bf16_b", B)) return e;
+    FG_CHECK_ARG(x && shift && scale && out, "fg_ln_modulate_bf16_b: null pointer");
+    FG_CHECK_ARG(FG_ALIGNED16(x) && FG_ALIGNED16(shift) && FG_ALIGNED16(scale) && FG_ALIGNED16(out) && mod_ld % 8 == 0,
+                 "fg_ln_modulate_bf16_b: pointers / mod_ld must be 16-byte aligned");
+    if (rows == 0) return FG_OK;
+    hipLaunchKernelGGL(ln_modulate_b_kernel, row_grid_b(rows, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x,
+                       (const bf16*)shift, (const bf16*)scale, (bf16*)out, rows, C, eps, mod_rows, first_rows, mod_ld);
+    return fg_launch_status("fg_ln_modulate_bf16_b");
+}
+
+int fg_gate_residual_bf16_b(const void* x, const void* y, const void* gate, void* out, int B, int64_t rows, int C, int64_t mod_rows,
+                            int64_t first_rows, int64_t mod_ld, fg_stream_t stream) {
+    if (int e = check_rows("fg_gate_residual_bf16_b", rows, C, gate ? mod_rows : 1, gate ? first_rows : 0)) return e;
+    if (int e = check_batch("fg_gate_residual_bf16_b", B)) return e;
+    FG_CHECK_ARG(x && y && out, "fg_gate_residual_bf16_b: null pointer");
+    FG_CHECK_ARG(FG_ALIGNED16(x) && FG_ALIGNED16(y) && FG_ALIGNED16(gate) && FG_ALIGNED16(out) && mod_ld % 8 == 0,
+                 "fg_gate_residual_bf16_b: pointers / mod_ld must be 16-byte aligned");
+    if (rows == 0) return FG_OK;
+    hipLaunchKernelGGL(residual_b_kernel<-1>, row_grid_b(rows, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x,
+                       (const bf16*)y, (const bf16*)gate, (bf16*)out, (const bf16*)nullptr, (const bf16*)nullptr,
+                       (bf16*)nullptr, rows, C, 0.f, gate ? mod_rows : 1, gate ? first_rows : 0, mod_ld);
+    return fg_launch_status("fg_gate_residual_bf16_b");
+}
+
+int fg_residual_ln_bf16_b(const void* x, const void* y, const void* gate, void* x_out, const void* p0, const void* p1,
+                          void* norm_out, int mode, int B, int64_t rows, int C, float eps, int64_t mod_rows, int64_t first_rows,
+                          int64_t mod_ld, fg_stream_t stream) {
+    FG_CHECK_ARG(mode == 0 || mode == 1, "fg_residual_ln_bf16_b: mode must be 0 (modulate) or 1 (affine)");
+    const bool need_mod = gate != nullptr || mode == 0;
+    if (int e = check_rows("fg_residual_ln_bf16_b", rows, C, need_mod ? mod_rows : 1, need_mod ? first_rows : 0)) return e;
+    if (int e = check_batch("fg_residual_ln_bf16_b", B)) return e;
+    FG_CHECK_ARG(x && y && x_out && p0 && p1 && norm_out, "fg_residual_ln_bf16_b: null pointer");
+    FG_CHECK_ARG(FG_ALIGNED16(x) && FG_ALIGNED16(y) && FG_ALIGNED16(gate) && FG_ALIGNED16(x_out) && FG_ALIGNED16(p0) &&
+                     FG_ALIGNED16(p1) && FG_ALIGNED16(norm_out) && mod_ld % 8 == 0,
+                 "fg_residual_ln_bf16_b: pointers / mod_ld must be 16-byte aligned");
+    if (rows == 0) return FG_OK;
+    if (!need_mod) { mod_rows = 1; first_rows = 0; }
+    if (mode == 0)
+        hipLaunchKernelGGL(residual_b_kernel<0>, row_grid_b(rows, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x,
+                           (const bf16*)y, (const bf16*)gate, (bf16*)x_out, (const bf16*)p0, (const bf16*)p1,
+                           (bf16*)norm_out, rows, C, eps, mod_rows, first_rows, mod_ld);
+    else
+        hipLaunchKernelGGL(residual_b_kernel<1>, row_grid_b(rows, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x,
+                           (const bf16*)y, (const bf16*)gate, (bf16*)x_out, (const bf16*)p0, (const bf16*)p1,
+                           (bf16*)norm_out, rows, C, eps, mod_rows, first_rows, mod_ld);
+    return fg_launch_status("fg_residual_ln_bf16_b");
+}
+
+int fg_rmsnorm_rope_bf16_b(const void* x, int64_t ldx, const void* weight, const void* cos_tab, const void* sin_tab,
+                           int table_f32, void* out, int B, int64_t rows, int C, int num_heads, float eps, fg_stream_t stream) {
+    if (int e = check_rows("fg_rmsnorm_rope_bf16_b", rows, C, 1, 0)) return e;
+    if (int e = check_batch("fg_rmsnorm_rope_bf16_b", B)) return e;
+    FG_CHECK_ARG(x && weight && out, "fg_rmsnorm_rope_bf16_b: null pointer");
+    FG_CHECK_ARG(table_f32 ? (cos_tab != nullptr && sin_tab == nullptr) : ((cos_tab == nullptr) == (sin_tab == nullptr)),
+                 "fg_rmsnorm_rope_bf16_b: fp64 mode takes both tables or neither, fp32 mode ONE interleaved table in cos_tab");
+    FG_CHECK_ARG(num_heads > 0 && C % num_heads == 0 && (C / num_heads) % 8 == 0,
+                 "fg_rmsnorm_rope_bf16_b: head_dim must be a multiple of 8");
+    FG_CHECK_ARG(ldx >= C && ldx % 8 == 0 && FG_ALIGNED16(x) && FG_ALIGNED16(weight) && FG_ALIGNED16(out) &&
+                     FG_ALIGNED16(cos_tab) && FG_ALIGNED16(sin_tab),
+                 "fg_rmsnorm_rope_bf16_b: pointers / ldx must be 16-byte aligned");
+    if (rows == 0) return FG_OK;
+    const int hd = C / num_heads;
+    const bool plain = (hd & (hd - 1)) == 0;          // as fg_rmsnorm_rope_bf16 picks its instantiation
+#define FG_ROPE_B_LAUNCH(TAB, PL)                                                                                                    \
+    hipLaunchKernelGGL((rmsnorm_rope_b_kernel<TAB, PL>), row_grid_b(rows, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, ldx, \
+                       (const bf16*)weight, cos_tab, sin_tab, (bf16*)out, rows, C, hd, eps)
+    if (table_f32) { if (plain) FG_ROPE_B_LAUNCH(true, true); else FG_ROPE_B_LAUNCH(true, false); }
+    else { if (plain) FG_ROPE_B_LAUNCH(false, true); else FG_ROPE_B_LAUNCH(false, false); }
+#undef FG_ROPE_B_LAUNCH
+    return fg_launch_status("fg_rmsnorm_rope_bf16_b");
 }
 
 }  // extern "C"

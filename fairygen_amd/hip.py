@@ -145,6 +145,19 @@ _BATCH8_QUERIES = {
 }
 BATCH8_SYMBOLS = sorted(list(_BATCH8_SIGNATURES) + list(_BATCH8_QUERIES))    # what include/fairygen_hip_batch8.h declares
 
+# The extension of include/fairygen_hip_rowbatch.h (the row kernels that read a per-row table, on a batch that shares the table): a sixth pair.
+ROWBATCH_ABI_VERSION = 1  # fg_dit_rowbatch_version
+_ROWBATCH_SIGNATURES = {
+    "fg_ln_modulate_bf16_b": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _i64, _i64, _i64, _vp],
+    "fg_gate_residual_bf16_b": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i64, _i64, _i64, _vp],
+    "fg_residual_ln_bf16_b": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _f32, _i64, _i64, _i64, _vp],
+    "fg_rmsnorm_rope_bf16_b": [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _f32, _vp],
+}
+_ROWBATCH_QUERIES = {
+    "fg_dit_rowbatch_version": (_i32, []),
+}
+ROWBATCH_SYMBOLS = sorted(list(_ROWBATCH_SIGNATURES) + list(_ROWBATCH_QUERIES))    # what include/fairygen_hip_rowbatch.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -165,17 +178,18 @@ def load():
             "fairygen_amd has no CPU / PyTorch fallback for its kernels.")
     lib = ctypes.CDLL(_LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
-            list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()):
+            list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
-            list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()):
+            list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
                                  ("fg_attn_pv8_version", PV8_ABI_VERSION, " (e4m3 P V extension)"),
                                  ("fg_attn_shard8_version", SHARD8_ABI_VERSION, " (e4m3 operands of a token shard)"),
                                  ("fg_attn_cross8_version", CROSS8_ABI_VERSION, " (e4m3 cross-attention, K8 / V8^T in LDS)"),
-                                 ("fg_attn_batch8_version", BATCH8_ABI_VERSION, " (e4m3 attention on batches)")):
+                                 ("fg_attn_batch8_version", BATCH8_ABI_VERSION, " (e4m3 attention on batches)"),
+                                 ("fg_dit_rowbatch_version", ROWBATCH_ABI_VERSION, " (row kernels on batches that share a table)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -258,10 +272,26 @@ def _mod_args(mod, rows):
     return mod.mod_rows, mod.first_rows, mod.ld
 
 
+def _batch_rows(who, x, batch):
+    """(B, rows, C) of a row-kernel call on a batch that shares its table (include/fairygen_hip_rowbatch.h): x contiguous, its rows B equal
+    runs of `rows`; the table arguments then count inside one element.  batch None / 1: one element, (1, all rows, C)."""
+    total, c = _rows(x, "x")
+    b = 1 if batch is None else int(batch)
+    if b < 1 or total % b:
+        raise HipLibraryError(f"{who}: batch={batch} does not divide the {total} rows of x")
+    return b, total // b, c
+
+
 # ------------------------------------------------------------------------------------- DiT kernels
-def ln_modulate(x, mod, shift_idx, scale_idx, eps, out=None):
-    rows, c = _rows(x, "x")
+def ln_modulate(x, mod, shift_idx, scale_idx, eps, out=None, batch=None):
+    """batch=B > 1: x is B elements of rows / B rows each that share `mod`, whose rows are indexed inside the element
+    (fg_ln_modulate_bf16_b; per element the bytes of the call on that element alone)."""
+    b, rows, c = _batch_rows("ln_modulate", x, batch)
     out = torch.empty_like(x) if out is None else out
+    if b > 1:
+        _call("fg_ln_modulate_bf16_b", _ptr(x), mod.vec(shift_idx), mod.vec(scale_idx), _ptr(out), b, rows, c, eps,
+              *_mod_args(mod, rows), _stream(x))
+        return out
     _call("fg_ln_modulate_bf16", _ptr(x), mod.vec(shift_idx), mod.vec(scale_idx), _ptr(out), rows, c, eps,
           *_mod_args(mod, rows), _stream(x))
     return out
@@ -275,10 +305,15 @@ def ln_affine(x, w, b, eps, out=None):
     return out
 
 
-def gate_residual(x, y, mod=None, gate_idx=None, out=None):
-    rows, c = _rows(x, "x")
+def gate_residual(x, y, mod=None, gate_idx=None, out=None, batch=None):
+    """batch: as ln_modulate's (fg_gate_residual_bf16_b)."""
+    b, rows, c = _batch_rows("gate_residual", x, batch)
     _rows(y, "y")
     out = torch.empty_like(x) if out is None else out
+    if b > 1:
+        margs = (1, 0, 0) if mod is None else _mod_args(mod, rows)
+        _call("fg_gate_residual_bf16_b", _ptr(x), _ptr(y), None if mod is None else mod.vec(gate_idx), _ptr(out), b, rows, c, *margs, _stream(x))
+        return out
     if mod is None:
         _call("fg_gate_residual_bf16", _ptr(x), _ptr(y), None, _ptr(out), rows, c, 1, 0, 0, _stream(x))
     else:
@@ -287,29 +322,36 @@ def gate_residual(x, y, mod=None, gate_idx=None, out=None):
     return out
 
 
-def _ln_modulate_args(who, x, mod, gate_idx, shift_idx, scale_idx, norm_mod):
+def _ln_modulate_args(who, x, mod, gate_idx, shift_idx, scale_idx, norm_mod, batch=None):
     """(gate, shift, scale, affine flag, table args) of a residual + modulate(LN) launch."""
     norm_mod = mod if norm_mod is None else norm_mod
     if (norm_mod.mod_rows, norm_mod.first_rows, norm_mod.ld, norm_mod.per_token) != (mod.mod_rows, mod.first_rows, mod.ld, mod.per_token):
         raise HipLibraryError(f"{who}: gate and norm tables must share rows / first_rows / ld / per_token")
     gate = mod.vec(gate_idx) if gate_idx is not None else None
-    return gate, norm_mod.vec(shift_idx), norm_mod.vec(scale_idx), 0, _mod_args(mod, _rows(x, "x")[0])
+    return gate, norm_mod.vec(shift_idx), norm_mod.vec(scale_idx), 0, _mod_args(mod, _batch_rows(who, x, batch)[1])
 
 
-def _ln_affine_args(x, w, b, mod, gate_idx):
+def _ln_affine_args(x, w, b, mod, gate_idx, batch=None):
     """(gate, weight, bias, affine flag, table args) of a residual + affine LN launch."""
     _dev(w, "w"), _dev(b, "b")
     if mod is None:
         return None, _ptr(w), _ptr(b), 1, (1, 0, 0)
-    return mod.vec(gate_idx), _ptr(w), _ptr(b), 1, _mod_args(mod, _rows(x, "x")[0])
+    return mod.vec(gate_idx), _ptr(w), _ptr(b), 1, _mod_args(mod, _batch_rows("residual_ln_affine", x, batch)[1])
 
 
-def _residual_ln(x, y, eps, x_out, norm_out, gate, p1, p2, affine, margs, fp8=False):
+def _residual_ln(x, y, eps, x_out, norm_out, gate, p1, p2, affine, margs, fp8=False, batch=None):
     """x_out = x + gate*y, then LN(x_out) with the operands p1, p2 (shift / scale vectors, or weight / bias with affine = 1): as a bf16
-    row in norm_out (fg_residual_ln_bf16) or, fp8, as (e4m3 rows, scales) (fg_residual_ln_fp8_bf16)."""
-    rows, c = _rows(x, "x")
+    row in norm_out (fg_residual_ln_bf16) or, fp8, as (e4m3 rows, scales) (fg_residual_ln_fp8_bf16).  batch=B > 1 (bf16 only): B
+    elements that share the table (fg_residual_ln_bf16_b), margs counted inside one element."""
+    b, rows, c = _batch_rows("residual_ln", x, batch)
     _rows(y, "y")
     x_out = torch.empty_like(x) if x_out is None else x_out
+    if b > 1:
+        if fp8:
+            raise HipLibraryError("residual_ln: the fp8-output norms have no batched form (include/fairygen_hip_rowbatch.h)")
+        norm_out = torch.empty_like(x) if norm_out is None else norm_out
+        _call("fg_residual_ln_bf16_b", _ptr(x), _ptr(y), gate, _ptr(x_out), p1, p2, _ptr(norm_out), affine, b, rows, c, eps, *margs, _stream(x))
+        return x_out, norm_out
     if fp8:
         q, sc = _fp8_rows_out(x)
         _call("fg_residual_ln_fp8_bf16", _ptr(x), _ptr(y), gate, _ptr(x_out), p1, p2, _ptr(q), _ptr(sc), affine, rows, c, eps, *margs,
@@ -320,17 +362,18 @@ def _residual_ln(x, y, eps, x_out, norm_out, gate, p1, p2, affine, margs, fp8=Fa
     return x_out, norm_out
 
 
-def residual_ln_modulate(x, y, mod, gate_idx, shift_idx, scale_idx, eps, x_out=None, norm_out=None, norm_mod=None):
+def residual_ln_modulate(x, y, mod, gate_idx, shift_idx, scale_idx, eps, x_out=None, norm_out=None, norm_mod=None, batch=None):
     """x_out = x + gate*y (gate_idx None: x + y); norm_out = modulate(LN(x_out)).
 
     gate comes from `mod`, shift/scale from `norm_mod` (default: `mod`); both tables must have the same
-    number of rows, first_rows and leading dimension."""
-    return _residual_ln(x, y, eps, x_out, norm_out, *_ln_modulate_args("residual_ln_modulate", x, mod, gate_idx, shift_idx, scale_idx, norm_mod))
+    number of rows, first_rows and leading dimension.  batch: as ln_modulate's."""
+    return _residual_ln(x, y, eps, x_out, norm_out, *_ln_modulate_args("residual_ln_modulate", x, mod, gate_idx, shift_idx, scale_idx, norm_mod, batch),
+                        batch=batch)
 
 
-def residual_ln_affine(x, y, w, b, eps, mod=None, gate_idx=None, x_out=None, norm_out=None):
-    """x_out = x + gate*y (mod None: x + y); norm_out = LN(x_out)*w + b."""
-    return _residual_ln(x, y, eps, x_out, norm_out, *_ln_affine_args(x, w, b, mod, gate_idx))
+def residual_ln_affine(x, y, w, b, eps, mod=None, gate_idx=None, x_out=None, norm_out=None, batch=None):
+    """x_out = x + gate*y (mod None: x + y); norm_out = LN(x_out)*w + b.  batch: as ln_modulate's (the gate table is per element)."""
+    return _residual_ln(x, y, eps, x_out, norm_out, *_ln_affine_args(x, w, b, mod, gate_idx, batch), batch=batch)
 
 
 def _fp8_pair(rows, c, device):
@@ -397,16 +440,31 @@ def _rope_tables(who, cos, sin, rows, half):
     return 0
 
 
-def rmsnorm_rope(x, weight, num_heads, eps, cos=None, sin=None, out=None, grouped=None):
+def rmsnorm_rope(x, weight, num_heads, eps, cos=None, sin=None, out=None, grouped=None, batch=None):
     """x: (..., C) possibly a column slice of a wider row-major buffer (stride(-2) = ld).
 
     RoPE tables: cos and sin fp64 (rows, head_dim/2) -> the reference's fp64 rotation; or cos = ONE fp32 interleaved
     (rows, head_dim/2, 2) table {cos, sin} with sin=None -> fp32 FMA rotation (the fast default of the pipeline).
 
     grouped=(dst, group_cols, group_stride, ld): write column block g of row r to the 1-D view
-    dst[g*group_stride + r*ld : ... + group_cols] instead of a (rows, C) tensor (Ulysses send buffer); returns dst."""
+    dst[g*group_stride + r*ld : ... + group_cols] instead of a (rows, C) tensor (Ulysses send buffer); returns dst.
+
+    batch=B > 1: x (B, rows, C) — B elements that share the RoPE table of `rows` rows, indexed by the row inside the element
+    (fg_rmsnorm_rope_bf16_b); x may be a column slice with batch stride rows * ld; out (B, rows, C) dense; no grouped form."""
     _dev(x, "x"), _dev(weight, "weight")
     c = x.shape[-1]
+    if batch is not None and int(batch) > 1:
+        ld = _ld_rows(x, "x")
+        if grouped is not None or x.shape[0] != int(batch):
+            raise HipLibraryError(f"rmsnorm_rope: batch={batch} needs x (B, rows, C) and no grouped destination")
+        b, rows = x.shape[:2]
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+        if out.shape != x.shape or not out.is_contiguous():
+            raise HipLibraryError("rmsnorm_rope: out of a batch must be contiguous and of x's shape")
+        f32tab = _rope_tables("rmsnorm_rope", cos, sin, rows, c // num_heads // 2)
+        _call("fg_rmsnorm_rope_bf16_b", _ptr(x), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(out), b, rows, c, num_heads, eps,
+              _stream(x))
+        return out
     x2 = _rows2d(x, "rmsnorm_rope")
     rows, ld = x2.shape[0], x2.stride(0)
     if grouped is None:

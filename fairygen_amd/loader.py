@@ -39,6 +39,8 @@ class ModelConfig:
     attention_pv_dtype: Optional[torch.dtype] = None
     # torch.float8_e4m3fn (with both of the above): cross-attention in the e4m3 form too (enable_qk8_attention(pv8=True, cross=True)); None: bf16
     cross_attention_dtype: Optional[torch.dtype] = None
+    # True: a merged CFG call (pipe(..., cfg_merge=True)) runs both branches in ONE stacked forward of the DiT (WanModel.enable_stacked_cfg)
+    stacked_cfg: bool = False
     clear_parameters: bool = False
 
     def check_input(self):
@@ -59,7 +61,7 @@ class ModelConfig:
         return {k: getattr(self, k) for k in (
             "offload_device", "offload_dtype", "onload_device", "onload_dtype",
             "preparing_device", "preparing_dtype", "computation_device", "computation_dtype", "attention_dtype",
-            "attention_pv_dtype", "cross_attention_dtype")}
+            "attention_pv_dtype", "cross_attention_dtype", "stacked_cfg")}
 
 
 # --------------------------------------------------------------------------------- state-dict files
@@ -236,6 +238,10 @@ class ModelPool:
                 if attn_pv is not None:
                     model.enable_qk8_attention(pv8=True, cross=attn_cross is not None)      # P V in e4m3 too, and cross-attention if asked
                 model.qk8_fused_producer = True      # the operands from the RMSNorm+RoPE pass itself: the same bits, k read once
+            if vram_config.get("stacked_cfg"):
+                if not hasattr(model, "enable_stacked_cfg"):
+                    raise NotImplementedError(f"stacked_cfg is only built for the DiT, not for {cfg['model_name']}")
+                model.enable_stacked_cfg()
             self.model.append(model)
             self.model_name.append(cfg["model_name"])
             self.model_path.append(path)

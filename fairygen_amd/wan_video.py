@@ -794,6 +794,49 @@ def time_embedding_rows(dit, timestep, ti2v, dev, dt):
     return t_rows, F.linear(hip.activation(t_rows.clone(), "silu"), proj.weight, proj.bias).unflatten(1, (6, dit.dim))
 
 
+def _kv_entry(kv_cache, context):
+    """The dict of the denoise loop's kv_cache that belongs to the prompt tensor `context`, made on first sight."""
+    # an entry belongs to ONE prompt tensor object at ONE version (it keeps the tensor alive, so its address cannot be reused while the
+    # entry exists); a loop has two prompts, so a handful of entries is a caller re-materialising its context every step: the oldest goes
+    entries = kv_cache.setdefault("entries", [])
+    base = context._base if context._base is not None else context          # the merged call passes views context[b:b+1] of one tensor
+    ident = (context.storage_offset(), tuple(context.shape), tuple(context.stride()), context._version)
+    kv = next((e["kv"] for e in entries if e["base"] is base and e["ident"] == ident), None)
+    if kv is None:
+        kv = {}
+        entries.append({"base": base, "ident": ident, "kv": kv})
+        del entries[:-4]
+    return kv
+
+
+def _stacked_cfg_steps(dit, latents, timestep, context, fuse_vae_embedding_in_latents, gather_output, kv_cache):
+    """The merged CFG call as ONE forward (WanModel.enable_stacked_cfg; checked by the caller): the time rows, the modulation and RoPE
+    tables and the patch embedding are built once — they depend on the timestep, the grid and the latents only — the context is the
+    batch (2, L, dim), and WanModel.forward_tokens_steps runs on the stacked residual stream.  With CFG_SHARE_PREFIX block 0's
+    self-attention half is computed once on N rows (x goes in as one element); without it the whole forward is stacked.  kv_cache then
+    holds the (2, ...) cross-attention operands of the pair under the batched context tensor."""
+    dev, dt = latents.device, latents.dtype
+    ti2v = dit.seperated_timestep and fuse_vae_embedding_in_latents
+    t_rows, mod_rows_t = time_embedding_rows(dit, timestep, ti2v, dev, dt)
+    kv = _kv_entry(kv_cache, context) if kv_cache is not None else None
+    if kv is not None and "ctx" in kv:
+        ctx = kv["ctx"]
+    else:      # element by element: the library GEMMs of the batch-1 forward on the same rows, the same bits; once per loop with a kv_cache
+        tx = dit.text_embedding
+        ctx = torch.cat([F.linear(hip.activation(F.linear(context[b:b + 1], tx[0].weight, tx[0].bias), "gelu_tanh"), tx[2].weight, tx[2].bias)
+                         for b in range(context.shape[0])], dim=0)
+        if kv is not None:
+            kv["ctx"] = ctx
+    x, (f, h, w) = dit.patchify(latents)
+    first_rows = h * w if ti2v else 0
+    if not CFG_SHARE_PREFIX:
+        x = x.expand(context.shape[0], -1, -1).contiguous()
+    out = yield from dit.forward_tokens_steps(x, ctx, mod_rows_t, t_rows, first_rows, dit.rope_tables(f, h, w, dev), kv_cache=kv)
+    if not gather_output:
+        return out, (f, h, w)
+    return dit.unpatchify(out, (f, h, w))
+
+
 def model_fn_wan_video_steps(dit, latents=None, timestep=None, context=None, fuse_vae_embedding_in_latents=False,
                              sequence_shard=None, gather_output=True, tea_cache=None, sliding_window_size=None,
                              sliding_window_stride=None, cfg_prefix=None, kv_cache=None, time_rows=None, owned=None, **kwargs):
@@ -813,6 +856,12 @@ def model_fn_wan_video_steps(dit, latents=None, timestep=None, context=None, fus
         # kernels: identical results, the prediction comes back stacked on dim 0 like the reference's.
         if tea_cache is not None:
             raise NotImplementedError("TeaCache is per CFG branch; the merged call has none (the reference drops it too)")
+        if getattr(dit, "stacked_cfg", False):
+            # opt-in (WanModel.enable_stacked_cfg): ONE forward on the residual stream (2, N, dim); what it does not take raises here
+            dit.check_stacked_cfg(context.shape[0], sequence_shard, sliding_window_size is not None or sliding_window_stride is not None)
+            if cfg_prefix is not None or time_rows is not None or owned is not None:
+                raise NotImplementedError("stacked_cfg: the merged call is not recorded into a graph and shares no prefix with another call")
+            return (yield from _stacked_cfg_steps(dit, latents, timestep, context, fuse_vae_embedding_in_latents, gather_output, kv_cache))
         outs = []
         # the elements differ only in their context: block 0's self-attention half is shared — between exactly two (one producer, one consumer)
         prefix = {} if (CFG_SHARE_PREFIX and sliding_window_size is None and context.shape[0] == 2) else None
@@ -849,16 +898,7 @@ def model_fn_wan_video_steps(dit, latents=None, timestep=None, context=None, fus
     # block in forward_tokens_steps — is kept for the denoise loop that owns kv_cache (keyed by the prompt tensor)
     kv = None
     if kv_cache is not None and sliding_window_size is None:
-        # an entry belongs to ONE prompt tensor object at ONE version (it keeps the tensor alive, so its address cannot be reused while the
-        # entry exists); a loop has two prompts, so a handful of entries is a caller re-materialising its context every step: the oldest goes
-        entries = kv_cache.setdefault("entries", [])
-        base = context._base if context._base is not None else context          # the merged call passes views context[b:b+1] of one tensor
-        ident = (context.storage_offset(), tuple(context.shape), tuple(context.stride()), context._version)
-        kv = next((e["kv"] for e in entries if e["base"] is base and e["ident"] == ident), None)
-        if kv is None:
-            kv = {}
-            entries.append({"base": base, "ident": ident, "kv": kv})
-            del entries[:-4]
+        kv = _kv_entry(kv_cache, context)
     if kv is not None and "ctx" in kv:
         ctx = kv["ctx"]
     else:

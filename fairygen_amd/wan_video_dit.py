@@ -49,8 +49,8 @@ def gemm_bias(x, weight, bias):
 
 
 def gemm_bias_gelu(x, weight, bias):
-    """ffn.0 with GELU(tanh) applied to the fp32 accumulator in the hipBLASLt epilogue; x (1, n, K)."""
-    return torch._addmm_activation(bias, x[0], weight.t(), use_gelu=True).unsqueeze(0)
+    """ffn.0 with GELU(tanh) applied to the fp32 accumulator in the hipBLASLt epilogue; x (b, n, K) contiguous: b * n rows of one GEMM."""
+    return torch._addmm_activation(bias, x.reshape(-1, x.shape[-1]), weight.t(), use_gelu=True).view(x.shape[:-1] + (weight.shape[0],))
 
 
 def gemm_bias_tuned(x, weight, bias):
@@ -135,6 +135,11 @@ class Act(NamedTuple):
     def rows(self):
         return self.bf16.shape[-2] if self.bf16 is not None else self.q8[0].shape[0]
 
+    @property
+    def total_rows(self):
+        """The rows of the GEMM behind it: `rows`, times the batch of a stacked forward (WanModel.enable_stacked_cfg)."""
+        return self.bf16.numel() // self.bf16.shape[-1] if self.bf16 is not None else self.q8[0].shape[0]
+
 
 class _BlockLinears:
     """How the Linears and norms of the blocks run in ONE forward: the mode decisions (bf16 / fp8 Linears, hot-loaded adapters and their
@@ -166,7 +171,13 @@ class _BlockLinears:
             return Act(*hip.ln_modulate_dual(x, mod, shift_idx, scale_idx, self.eps, out=out))
         if self.want_q8:
             return Act(None, hip.ln_modulate_fp8(x, mod, shift_idx, scale_idx, self.eps))
-        return Act(hip.ln_modulate(x, mod, shift_idx, scale_idx, self.eps, out=out))
+        return Act(hip.ln_modulate(x, mod, shift_idx, scale_idx, self.eps, out=out, batch=self.batch_of(x)))
+
+    @staticmethod
+    def batch_of(x):
+        """batch= of the row kernels that read a table by the row inside the element: the leading dimension of a stacked forward
+        (WanModel.enable_stacked_cfg; only the bf16 norms get there), None for the one element every other forward has."""
+        return x.shape[0] if x.dim() == 3 and x.shape[0] > 1 else None
 
     def affine(self, x, norm):
         """norm3 on its own has no fp8-only kernel: the bf16 row, which the fp8 Linear behind it quantises."""
@@ -175,7 +186,7 @@ class _BlockLinears:
         return Act(hip.ln_affine(x, norm.weight, norm.bias, self.eps))
 
     def gate_residual(self, x, y, mod, gate_idx):
-        return hip.gate_residual(x, y, mod if gate_idx is not None else None, gate_idx, out=x)
+        return hip.gate_residual(x, y, mod if gate_idx is not None else None, gate_idx, out=x, batch=self.batch_of(x))
 
     def residual_modulate(self, x, y, mod, gate_idx, norm_mod, shift_idx, scale_idx, out=None):
         if self.want_bf16 and self.want_q8:      # no fused kernel with both outputs
@@ -184,7 +195,8 @@ class _BlockLinears:
         if self.want_q8:
             x, q8 = hip.residual_ln_modulate_fp8(x, y, mod, gate_idx, shift_idx, scale_idx, self.eps, x_out=x, norm_mod=norm_mod)
             return x, Act(None, q8)
-        x, h = hip.residual_ln_modulate(x, y, mod, gate_idx, shift_idx, scale_idx, self.eps, x_out=x, norm_out=out, norm_mod=norm_mod)
+        x, h = hip.residual_ln_modulate(x, y, mod, gate_idx, shift_idx, scale_idx, self.eps, x_out=x, norm_out=out, norm_mod=norm_mod,
+                                        batch=self.batch_of(x))
         return x, Act(h)
 
     def residual_affine(self, x, y, mod, gate_idx, norm):
@@ -194,7 +206,7 @@ class _BlockLinears:
         if self.want_q8:
             x, q8 = hip.residual_ln_affine_fp8(x, y, norm.weight, norm.bias, self.eps, mod, gate_idx, x_out=x)
             return x, Act(None, q8)
-        x, h = hip.residual_ln_affine(x, y, norm.weight, norm.bias, self.eps, mod, gate_idx, x_out=x)
+        x, h = hip.residual_ln_affine(x, y, norm.weight, norm.bias, self.eps, mod, gate_idx, x_out=x, batch=self.batch_of(x))
         return x, Act(h)
 
     # ---- the Linears
@@ -268,7 +280,7 @@ class _BlockLinears:
         nh, eps = sa.attn.num_heads, self.model.eps
         c = qkv.shape[-1] // 3
         n = qkv.shape[1]
-        bufs = self.qk8_bufs(n, nh, c // nh, qkv.device, True) or hip.attention_qk8_fused_scratch(n, nh, c // nh, qkv.device)
+        bufs = self.qk8_bufs(n, nh, c // nh, qkv.device, True) or hip.attention_qk8_fused_scratch(n, nh, c // nh, qkv.device, qkv.shape[0])
         q8, k8, sq, sk, kbar, parts = bufs
         k, _ = hip.rmsnorm_rope_kstats(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, partials=parts)
         hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, q8=q8, sq=sq)
@@ -286,7 +298,8 @@ class _BlockLinears:
         gelu (ffn.0): the result is nn.GELU's output — except with gelu_in_quant, where it is the pre-activation."""
         m, fp8 = self.model, self.fp8
         n, k = weight.shape
-        own = fp8 is None and own and own_gemm_ok(a.rows, n, k)
+        rows = a.total_rows      # a stacked forward: the rows of all elements in one GEMM
+        own = fp8 is None and own and own_gemm_ok(rows, n, k)
         if hip_adapters and self.hip_hot and (fp8 is None or fp8_own_ok(n, k)):
             pack = m._hot_pack(names)
         elif gelu:      # an adapter adds to the pre-activation: only a Linear that has one gives up its fused GELU
@@ -297,15 +310,15 @@ class _BlockLinears:
             own = False      # the reference's ops for this Linear: library GEMM, adapters, GELU
         if gelu and pack is None and not self.gelu_in_quant:      # nothing between the Linear and its GELU: into the GEMM's store where one takes it
             if fp8 is not None and fp8_own_ok(n, k):
-                return hip.gemm_fp8(*a.q8, w8, bias, act="gelu_tanh", lead_shape=(1, a.rows), **self.state(a.rows, n, k))
+                return hip.gemm_fp8(*a.q8, w8, bias, act="gelu_tanh", lead_shape=(1, rows), **self.state(rows, n, k))
             if own:
-                return gemm_bias_gelu_own(a.bf16, weight, bias, **self.state(a.rows, n, 2 * k))
+                return gemm_bias_gelu_own(a.bf16, weight, bias, **self.state(rows, n, 2 * k))
             if fp8 is None and m.gelu_epilogue:      # GELU(tanh) in the hipBLASLt epilogue: one pass less over the (n, ffn) tensor
                 return gemm_bias_gelu(a.bf16, weight, bias)
         if fp8 is not None:
-            y = m._scaled_linear(*self.q8(a), w8, bias, **self.state(a.rows, n, k))
+            y = m._scaled_linear(*self.q8(a), w8, bias, **self.state(rows, n, k))
         else:
-            y = gemm_bias_own(a.bf16, weight, bias, **self.state(a.rows, n, 2 * k)) if own else gemm_bias(a.bf16, weight, bias)
+            y = gemm_bias_own(a.bf16, weight, bias, **self.state(rows, n, 2 * k)) if own else gemm_bias(a.bf16, weight, bias)
         if gelu and pack:      # GELU moves from the GEMM's store into the adapter kernel's
             return hip.lora_apply(a.bf16, pack[0], pack[1], y, mode="gelu_tanh")
         m._hot_apply(names, a.bf16, y, pack)
@@ -319,14 +332,24 @@ class _BlockLinears:
         GateModule; the gate distributes over Linear + adapter): the add in the GEMM's store (fg_gemm_epilogue_bf16 / fg_gemm_fp8_bf16)
         and in fg_lora_apply_bf16, then the norm alone; or a plain GEMM, the adapters, and the fused residual + norm kernel.
         a: bf16; gelu: it is ffn.0's pre-activation (gelu_in_quant).  tuned / store_ok: ffn.2's library GEMM comes from the tuning table,
-        and FAIRYGEN_GEMM=fused-ffn2 keeps it there."""
+        and FAIRYGEN_GEMM=fused-ffn2 keeps it there.
+        A stacked forward (a: (B, rows, K), B > 1; bf16 Linears without unfused adapters only): the store picks its gate row by
+        `row >= first_rows` over the rows of the launch, so with a two-row gate table it is launched once per element on the element's
+        rows — the batch-1 forward's launch, the batch-1 forward's bits; with one gate row or none, one launch takes all B * rows rows.
+        The other form runs its GEMM on B * rows rows and the batched row kernels (include/fairygen_hip_rowbatch.h) do the gate."""
         m, fp8 = self.model, self.fp8
         n, k = weight.shape
         gmod = mod if gate_idx is not None else None
         pack = m._hot_pack((name,)) if self.hip_hot else False if name in m.hot_loras else None
-        if self.own and store_ok and pack is not False and (own_gemm_ok(a.shape[1], n, k) if fp8 is None else fp8_own_ok(n, k)):
-            if fp8 is None:
-                gemm_residual(x, a, weight, bias, gmod, gate_idx, **self.state(a.shape[1], n, 2 * k))
+        nb = a.shape[0]
+        per_element = nb > 1 and gmod is not None and gmod.mod_rows == 2
+        rows = a.shape[1] if per_element else nb * a.shape[1]      # of one store launch
+        if self.own and store_ok and pack is not False and (own_gemm_ok(rows, n, k) if fp8 is None else fp8_own_ok(n, k)):
+            if per_element:
+                for e in range(nb):
+                    gemm_residual(x[e:e + 1], a[e:e + 1], weight, bias, gmod, gate_idx, **self.state(rows, n, 2 * k))
+            elif fp8 is None:
+                gemm_residual(x, a, weight, bias, gmod, gate_idx, **self.state(rows, n, 2 * k))
             else:
                 hip.gemm_fp8(*hip.fp8_quant_rows(a), w8, bias, out=x, residual=True, mod=gmod, gate_idx=gate_idx, **self.state(a.shape[1], n, k))
             if pack:
@@ -355,13 +378,14 @@ QK8_MIN_KV = 1024
 def takes_cross8_attention(model, attn, n_kv, batch):
     """enable_qk8_attention(cross=True): the stock AttentionModule of cross-attention, one batch element, a context whose K8 and V8^T fit
     the LDS (hip.attention_cross8_max_kv(): 640 keys).  Anything else keeps the bf16 kernel."""
-    return bool(model.cross8_attention) and type(attn) is AttentionModule and batch == 1 and 1 <= n_kv <= hip.attention_cross8_max_kv()
+    return bool(model.cross8_attention) and type(attn) is AttentionModule and (batch == 1 or bool(model.stacked_cfg)) and \
+        1 <= n_kv <= hip.attention_cross8_max_kv()
 
 
 def takes_qk8_attention(model, attn, n_kv, batch):
     """Whether a block's self-attention over n_kv keys runs the e4m3 Q K^T kernel: the mode on, the stock AttentionModule, more than
     QK8_MIN_KV keys, one batch element.  The one predicate of _BlockLinears.attention and of the fused producers in front of it."""
-    return bool(model.qk8_attention) and type(attn) is AttentionModule and n_kv > QK8_MIN_KV and batch == 1
+    return bool(model.qk8_attention) and type(attn) is AttentionModule and n_kv > QK8_MIN_KV and (batch == 1 or bool(model.stacked_cfg))
 
 
 class RMSNorm(nn.Module):
@@ -516,6 +540,8 @@ class WanModel(nn.Module):
         self.qk8_sharded = False
         # ... and cross-attention in the e4m3 form too (enable_qk8_attention(pv8=True, cross=True)); False: cross-attention in bf16
         self.cross8_attention = False
+        # a merged CFG call (cfg_merge=True) as ONE forward on x (2, N, dim) instead of two batch-1 forwards; see enable_stacked_cfg
+        self.stacked_cfg = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -599,6 +625,33 @@ class WanModel(nn.Module):
         self.qk8_sharded = bool(flag) and bool(sharded)
         self.cross8_attention = bool(flag) and bool(pv8) and bool(cross)
         return self
+
+    # ------------------------------------------------------------------ the stacked CFG forward
+    def enable_stacked_cfg(self, flag=True):
+        """Opt-in, off by default: a merged CFG call (cfg_merge=True: the positive and the negative context batched, wan_video.py
+        model_fn_wan_video_steps) runs ONE forward on the residual stream (2, N, dim) instead of two batch-1 forwards one after the other.
+        The time rows, the modulation tables and the RoPE tables are one element's and shared; the row kernels that read them take the
+        batch through include/fairygen_hip_rowbatch.h; the plain Linears, the ungated residual store and the gated one with a single gate
+        row run on 2 N rows in one GEMM; the gated store with two gate rows (TI2V) is launched per element (_BlockLinears.residual);
+        attention runs with B = 2 — bf16, or with the e4m3 modes on the batched entry points of include/fairygen_hip_batch8.h.  Block 0's
+        self-attention half does not see the context and is computed once on N rows (CFG_SHARE_PREFIX).  With the switch off every path
+        is what it was.  What it does not take raises NotImplementedError at the merged call (check_stacked_cfg).  DESIGN.md §5."""
+        self.stacked_cfg = bool(flag)
+        return self
+
+    def check_stacked_cfg(self, context_batch, shard=None, sliding_window=False):
+        """What a merged call must not meet while enable_stacked_cfg is on; decided on the host before anything is launched."""
+        if self.fp8_dtype is not None:
+            raise NotImplementedError("stacked_cfg with enable_fp8_linear: the fp8-output norm kernels have no batched form")
+        if self.hot_loras:
+            raise NotImplementedError(f"stacked_cfg with hot-loaded adapters on hot_backend={self.hot_lora_backend!r}: fg_lora_apply_bf16's gate "
+                                      "has no batched form; hot_backend='fused' adapters are plain weights and work")
+        if shard is not None and shard.active:
+            raise NotImplementedError("stacked_cfg with an active token shard: the stacked forward has no exchange")
+        if sliding_window:
+            raise NotImplementedError("stacked_cfg with sliding windows: windows are not part of the batch")
+        if context_batch != 2:
+            raise NotImplementedError(f"stacked_cfg stacks the CFG pair: a context batch of 2, not {context_batch}")
 
     def check_qk8_layout(self, shard):
         if self.cross8_attention and shard is not None and shard.active:
@@ -794,10 +847,12 @@ class WanModel(nn.Module):
         x = x.view(b, f, h, w, px, py, pz, self.out_dim).permute(0, 7, 1, 4, 2, 5, 3, 6)
         return x.reshape(b, self.out_dim, f * px, h * py, w * pz)
 
-    def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, lin, w8):
+    def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, lin, w8, norm3=True):
         """Block i's self-attention half (reference :139-146, :225-226): h = modulate(norm1(x)) in (an Act); returns the residual stream
         after x += gate_msa * o(attn(...)) and h = norm3(x).  Yields right after each exchange of a token-sharded run has been started.
-        lin: the _BlockLinears of this forward; w8: the block's e4m3 weights (Nones in bf16 mode)."""
+        lin: the _BlockLinears of this forward; w8: the block's e4m3 weights (Nones in bf16 mode).  norm3=False: no h (returns None for it):
+        the stacked forward computes block 0's half once and norms the copies.  x (B, n, dim) with B > 1 (the stacked forward, unsharded):
+        the RoPE tables are one element's, the norm kernels and attention take the batch."""
         c, nh, eps = self.dim, self.num_heads, self.eps
         sharded = shard is not None and shard.active
         wqkv, bqkv, _, _ = blk.fused_weights()
@@ -811,8 +866,9 @@ class WanModel(nn.Module):
         if not sharded and self.qk8_fused_producer and takes_qk8_attention(self, sa.attn, qkv.shape[1], qkv.shape[0]):
             a = lin.attention_qk8_fused(sa, qkv, rq, rk, scale)
         elif not sharded:
-            k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
-            q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)
+            nb = lin.batch_of(qkv)
+            k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, batch=nb)
+            q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, batch=nb)
             a = lin.attention(sa.attn, q, k, v, scale, self_attn=True)
         elif shard.attn_mode == "ulysses":
             # token shard -> head shard (all N tokens of 24/P heads), attention, head shard -> token shard.  The
@@ -847,7 +903,7 @@ class WanModel(nn.Module):
             k, v = pending.wait()
             a = sa.attn(q, k, v) if scale is None else sa.attn(q, k, v, scale=scale)
         # x += gate_msa*y ; h = norm3(x)  (reference :225-226)
-        return lin.residual(x, a, f"blocks.{i}.self_attn.o", sa.o.weight, sa.o.bias, w8[1], mod, 2, affine=blk.norm3)
+        return lin.residual(x, a, f"blocks.{i}.self_attn.o", sa.o.weight, sa.o.bias, w8[1], mod, 2, affine=blk.norm3 if norm3 else None)
 
     def _shard8_attention_steps(self, i, sa, qkv, rq, rk, scale, shard, shard_total):
         """Block i's self-attention in the e4m3 form on the K / V all-gather layout (enable_qk8_attention(sharded=True),
@@ -917,10 +973,18 @@ class WanModel(nn.Module):
         kv_cache: a dict that lives as long as `context` and the weights stay what they are (one denoise loop): block i's
         cross-attention keys (after norm_k) and values depend on nothing else, so they are computed at the first step and read
         back at the others (reference :172-177 recomputes them every step).
-        owned: the scheduler block and scratch of a caller that records this forward into a graph (_BlockLinears.owned; same bits)."""
+        owned: the scheduler block and scratch of a caller that records this forward into a graph (_BlockLinears.owned; same bits).
+        The stacked CFG forward (enable_stacked_cfg): context (2, L, dim), everything else ONE element's.  x (1, n, dim): block 0's
+        self-attention half, which does not see the context, is computed once on n rows and copied into both halves of the (2, n, dim)
+        residual stream; x (2, n, dim): that half runs stacked as well.  Returns the head output (2, n, out)."""
         c, nh, eps = self.dim, self.num_heads, self.eps
         cos, sin = rope
         x = x.contiguous()
+        nb = context.shape[0]
+        if nb > 1 and (not self.stacked_cfg or x.shape[0] not in (1, nb) or tea_cache is not None or (shard is not None and shard.active)
+                       or cfg_prefix is not None or owned is not None):
+            raise ValueError("forward_tokens_steps: a context batch is the stacked CFG forward (enable_stacked_cfg): unsharded, no TeaCache, "
+                             "no cfg_prefix, not recorded")
         blocks = list(self.blocks)
         if skip_blocks:
             blocks, x = [], tea_cache.update(x)
@@ -949,6 +1013,10 @@ class WanModel(nn.Module):
                 x = cfg_prefix.pop("x_sa")
                 cfg_prefix["taken"] = True
                 h = lin.affine(x, blk.norm3)
+            elif x.shape[0] != nb:      # stacked, i == 0: once on n rows, then norm3 over the copies' rows
+                x, _ = yield from self._self_attention_steps(i, blk, mod, x, h, cos, sin, shard, shard_total, lin, w8, norm3=False)
+                x = x.expand(nb, -1, -1).contiguous()
+                h = lin.affine(x, blk.norm3)
             else:
                 if cfg_prefix is not None and i == 0:
                     cfg_prefix["owner"] = True
@@ -975,7 +1043,7 @@ class WanModel(nn.Module):
                     kc, vc = kv_cache[i]
                 else:      # 512 context rows, once per denoise loop with a kv_cache: library GEMM, adapters on the reference's torch ops
                     kvc = lin.plain(ctx, (f"blocks.{i}.cross_attn.k", f"blocks.{i}.cross_attn.v"), wkv_c, bkv_c, w8[3], hip_adapters=False)
-                    kc, vc = hip.rmsnorm_rope(kvc[..., :c], ca.norm_k.weight, nh, eps), kvc[..., c:]
+                    kc, vc = hip.rmsnorm_rope(kvc[..., :c], ca.norm_k.weight, nh, eps, batch=lin.batch_of(kvc)), kvc[..., c:]
                     if kv_cache is not None:
                         kv_cache[i] = (kc, vc)
                 ac = lin.attention(ca.attn, qc, kc, vc)
@@ -991,5 +1059,8 @@ class WanModel(nn.Module):
             tea_cache.store(x)
         # --- head (reference :261-268): table (R,2,C) = modulation + t
         hm = hip.ModTable((self.head.modulation.to(t_rows.dtype) + t_rows.unsqueeze(1)).contiguous(), first_rows)
+        if nb > 1:      # stacked: the head table per element, one Linear on all rows (through the seam, like the blocks' library GEMMs)
+            x = x if x.shape[0] == nb else x.expand(nb, -1, -1).contiguous()
+            return gemm_bias(hip.ln_modulate(x, hm, 0, 1, eps, batch=nb), self.head.head.weight, self.head.head.bias)
         h = hip.ln_modulate(x, hm, 0, 1, eps)
         return F.linear(h, self.head.head.weight, self.head.head.bias)
