@@ -5,6 +5,7 @@
 // Rounding points mirror the reference's bf16 tensor arithmetic op by op (see include/fairygen_hip.h).
 #include "common.h"
 #include "../../include/fairygen_hip_rowbatch.h"      // the batched forms of the row kernels that read a per-row table
+#include "../../include/fairygen_hip_rowbatch8.h"     // ... and of the norms with the fp8 output
 #include "rmsnorm_rope_row.h"     // Row, load_row, ld8, st8 and the RMSNorm+RoPE row arithmetic
 
 // Row kernels (one wave per token row held in registers): second launch-bound = minimum waves per SIMD the register
@@ -134,13 +135,7 @@ __global__ FG_ROW_BOUNDS void ln_modulate_fp8_kernel(const bf16* __restrict__ x,
                                                      const bf16* __restrict__ scale, uint8_t* __restrict__ out8,
                                                      float* __restrict__ scale_out, int64_t rows, int C, float eps, int64_t mod_rows,
                                                      int64_t first_rows, int64_t mod_ld, float fp8_max) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    Row r;
-    load_row(x + row * C, C, lane, r);
-    const int64_t m = mod_row(row, mod_rows, first_rows);
-    norm_store_fp8<0>(r, C, lane, eps, shift + m * mod_ld, scale + m * mod_ld, out8 + row * C, scale_out + row, fp8_max);
+#include "ln_modulate_fp8_body.inc"
 }
 
 // (bf16 row, e4m3 row, scale) of one norm in one pass.  MODE 0: p0 = shift, p1 = scale (modulation rows); 1: p0 = weight, p1 = bias.
@@ -177,6 +172,16 @@ __global__ FG_ROW_BOUNDS void ln_modulate_b_kernel(const bf16* __restrict__ x, c
 #include "ln_modulate_body.inc"
 }
 
+// ... and with the fp8 output (include/fairygen_hip_rowbatch8.h): the e4m3 rows move with x, the row scales by the element's rows
+__global__ FG_ROW_BOUNDS void ln_modulate_fp8_b_kernel(const bf16* __restrict__ x, const bf16* __restrict__ shift,
+                                                       const bf16* __restrict__ scale, uint8_t* __restrict__ out8,
+                                                       float* __restrict__ scale_out, int64_t rows, int C, float eps, int64_t mod_rows,
+                                                       int64_t first_rows, int64_t mod_ld, float fp8_max) {
+    const int64_t e0 = (int64_t)blockIdx.y * rows * C;
+    x += e0; out8 += e0; scale_out += (int64_t)blockIdx.y * rows;
+#include "ln_modulate_fp8_body.inc"
+}
+
 __global__ FG_ROW_BOUNDS void ln_affine_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
                                                         const bf16* __restrict__ b, bf16* __restrict__ out,
                                                         int64_t rows, int C, float eps) {
@@ -200,7 +205,7 @@ __global__ FG_ROW_BOUNDS void residual_kernel(const bf16* __restrict__ x, const 
 #include "residual_body.inc"
 }
 
-// batched (bf16 norm output only: the fp8 forms have no batched entry point); MODE -1 has no norm_out
+// batched (bf16 norm output only: the fp8 output has residual_fp8_b_kernel below); MODE -1 has no norm_out
 template <int MODE>
 __global__ FG_ROW_BOUNDS void residual_b_kernel(const bf16* __restrict__ x, const bf16* __restrict__ y,
                                                 const bf16* __restrict__ gate, bf16* __restrict__ x_out,
@@ -213,6 +218,21 @@ __global__ FG_ROW_BOUNDS void residual_b_kernel(const bf16* __restrict__ x, cons
     const int64_t e0 = (int64_t)blockIdx.y * rows * C;
     x += e0; y += e0; x_out += e0;
     if (MODE >= 0) norm_out += e0;
+#include "residual_body.inc"
+}
+
+// batched with the fp8 norm output only (include/fairygen_hip_rowbatch8.h; MODE 0 or 1): no bf16 norm row, so the body's fp8 branch is
+// the whole kernel — the entry point refuses a null norm_fp8
+template <int MODE>
+__global__ FG_ROW_BOUNDS void residual_fp8_b_kernel(const bf16* __restrict__ x, const bf16* __restrict__ y,
+                                                    const bf16* __restrict__ gate, bf16* __restrict__ x_out,
+                                                    const bf16* __restrict__ p0, const bf16* __restrict__ p1,
+                                                    uint8_t* __restrict__ norm_fp8, float* __restrict__ norm_scale, int64_t rows, int C,
+                                                    float eps, int64_t mod_rows, int64_t first_rows, int64_t mod_ld, float fp8_max) {
+    bf16* const norm_out = nullptr;
+    const int64_t e0 = (int64_t)blockIdx.y * rows * C;
+    x += e0; y += e0; x_out += e0; norm_fp8 += e0; norm_scale += (int64_t)blockIdx.y * rows;
+    __builtin_assume(norm_fp8 != nullptr);
 #include "residual_body.inc"
 }
 
@@ -649,6 +669,48 @@ int fg_rmsnorm_rope_bf16_b(const void* x, int64_t ldx, const void* weight, const
     else { if (plain) FG_ROPE_B_LAUNCH(false, true); else FG_ROPE_B_LAUNCH(false, false); }
 #undef FG_ROPE_B_LAUNCH
     return fg_launch_status("fg_rmsnorm_rope_bf16_b");
+}
+
+// ---- include/fairygen_hip_rowbatch8.h: the norms with the fp8 output on B elements of `rows` rows each; checks as above.
+int fg_dit_rowbatch8_version(void) { return 1; }
+
+int fg_ln_modulate_fp8_bf16_b(const void* x, const void* shift, const void* scale, void* out_fp8, float* out_scale, int B, int64_t rows,
+                              int C, float eps, int64_t mod_rows, int64_t first_rows, int64_t mod_ld, float fp8_max, fg_stream_t stream) {
+    if (int e = check_rows("fg_ln_modulate_fp8_bf16_b", rows, C, mod_rows, first_rows)) return e;
+    if (int e = check_batch("fg_ln_modulate_fp8_bf16_b", B)) return e;
+    FG_CHECK_ARG(x && shift && scale && out_fp8 && out_scale, "fg_ln_modulate_fp8_bf16_b: null pointer");
+    FG_CHECK_ARG(FG_ALIGNED16(x) && FG_ALIGNED16(shift) && FG_ALIGNED16(scale) && (((uintptr_t)out_fp8) & 7) == 0 && mod_ld % 8 == 0 &&
+                     fp8_max > 0.f,
+                 "fg_ln_modulate_fp8_bf16_b: pointers / mod_ld must be 16-byte aligned (out_fp8: 8), fp8_max positive");
+    if (rows == 0) return FG_OK;
+    hipLaunchKernelGGL(ln_modulate_fp8_b_kernel, row_grid_b(rows, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x,
+                       (const bf16*)shift, (const bf16*)scale, (uint8_t*)out_fp8, out_scale, rows, C, eps, mod_rows, first_rows, mod_ld,
+                       fp8_max);
+    return fg_launch_status("fg_ln_modulate_fp8_bf16_b");
+}
+
+int fg_residual_ln_fp8_bf16_b(const void* x, const void* y, const void* gate, void* x_out, const void* p0, const void* p1,
+                              void* norm_fp8, float* norm_scale, int mode, int B, int64_t rows, int C, float eps, int64_t mod_rows,
+                              int64_t first_rows, int64_t mod_ld, float fp8_max, fg_stream_t stream) {
+    FG_CHECK_ARG(mode == 0 || mode == 1, "fg_residual_ln_fp8_bf16_b: mode must be 0 (modulate) or 1 (affine)");
+    const bool need_mod = gate != nullptr || mode == 0;
+    if (int e = check_rows("fg_residual_ln_fp8_bf16_b", rows, C, need_mod ? mod_rows : 1, need_mod ? first_rows : 0)) return e;
+    if (int e = check_batch("fg_residual_ln_fp8_bf16_b", B)) return e;
+    FG_CHECK_ARG(x && y && x_out && p0 && p1 && norm_fp8 && norm_scale, "fg_residual_ln_fp8_bf16_b: null pointer");
+    FG_CHECK_ARG(FG_ALIGNED16(x) && FG_ALIGNED16(y) && FG_ALIGNED16(gate) && FG_ALIGNED16(x_out) && FG_ALIGNED16(p0) &&
+                     FG_ALIGNED16(p1) && (((uintptr_t)norm_fp8) & 7) == 0 && mod_ld % 8 == 0 && fp8_max > 0.f,
+                 "fg_residual_ln_fp8_bf16_b: pointers / mod_ld must be 16-byte aligned (norm_fp8: 8), fp8_max positive");
+    if (rows == 0) return FG_OK;
+    if (!need_mod) { mod_rows = 1; first_rows = 0; }
+    if (mode == 0)
+        hipLaunchKernelGGL(residual_fp8_b_kernel<0>, row_grid_b(rows, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x,
+                           (const bf16*)y, (const bf16*)gate, (bf16*)x_out, (const bf16*)p0, (const bf16*)p1, (uint8_t*)norm_fp8,
+                           norm_scale, rows, C, eps, mod_rows, first_rows, mod_ld, fp8_max);
+    else
+        hipLaunchKernelGGL(residual_fp8_b_kernel<1>, row_grid_b(rows, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x,
+                           (const bf16*)y, (const bf16*)gate, (bf16*)x_out, (const bf16*)p0, (const bf16*)p1, (uint8_t*)norm_fp8,
+                           norm_scale, rows, C, eps, mod_rows, first_rows, mod_ld, fp8_max);
+    return fg_launch_status("fg_residual_ln_fp8_bf16_b");
 }
 
 }  // extern "C"

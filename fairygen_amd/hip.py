@@ -158,6 +158,17 @@ _ROWBATCH_QUERIES = {
 }
 ROWBATCH_SYMBOLS = sorted(list(_ROWBATCH_SIGNATURES) + list(_ROWBATCH_QUERIES))    # what include/fairygen_hip_rowbatch.h declares
 
+# The extension of include/fairygen_hip_rowbatch8.h (the same batches, the norms whose row leaves as e4m3 bytes and a scale): a seventh pair.
+ROWBATCH8_ABI_VERSION = 1  # fg_dit_rowbatch8_version
+_ROWBATCH8_SIGNATURES = {
+    "fg_ln_modulate_fp8_bf16_b": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _i64, _i64, _i64, _f32, _vp],
+    "fg_residual_ln_fp8_bf16_b": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _f32, _i64, _i64, _i64, _f32, _vp],
+}
+_ROWBATCH8_QUERIES = {
+    "fg_dit_rowbatch8_version": (_i32, []),
+}
+ROWBATCH8_SYMBOLS = sorted(list(_ROWBATCH8_SIGNATURES) + list(_ROWBATCH8_QUERIES))    # what include/fairygen_hip_rowbatch8.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -178,10 +189,12 @@ def load():
             "fairygen_amd has no CPU / PyTorch fallback for its kernels.")
     lib = ctypes.CDLL(_LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
-            list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()):
+            list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()) + \
+            list(_ROWBATCH8_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
-            list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()):
+            list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()) + \
+            list(_ROWBATCH8_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
@@ -189,7 +202,8 @@ def load():
                                  ("fg_attn_shard8_version", SHARD8_ABI_VERSION, " (e4m3 operands of a token shard)"),
                                  ("fg_attn_cross8_version", CROSS8_ABI_VERSION, " (e4m3 cross-attention, K8 / V8^T in LDS)"),
                                  ("fg_attn_batch8_version", BATCH8_ABI_VERSION, " (e4m3 attention on batches)"),
-                                 ("fg_dit_rowbatch_version", ROWBATCH_ABI_VERSION, " (row kernels on batches that share a table)")):
+                                 ("fg_dit_rowbatch_version", ROWBATCH_ABI_VERSION, " (row kernels on batches that share a table)"),
+                                 ("fg_dit_rowbatch8_version", ROWBATCH8_ABI_VERSION, " (fp8-output norms on batches that share a table)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -341,14 +355,18 @@ def _ln_affine_args(x, w, b, mod, gate_idx, batch=None):
 
 def _residual_ln(x, y, eps, x_out, norm_out, gate, p1, p2, affine, margs, fp8=False, batch=None):
     """x_out = x + gate*y, then LN(x_out) with the operands p1, p2 (shift / scale vectors, or weight / bias with affine = 1): as a bf16
-    row in norm_out (fg_residual_ln_bf16) or, fp8, as (e4m3 rows, scales) (fg_residual_ln_fp8_bf16).  batch=B > 1 (bf16 only): B
-    elements that share the table (fg_residual_ln_bf16_b), margs counted inside one element."""
+    row in norm_out (fg_residual_ln_bf16) or, fp8, as (e4m3 rows, scales) (fg_residual_ln_fp8_bf16).  batch=B > 1: B elements that
+    share the table (fg_residual_ln_bf16_b; fp8: fg_residual_ln_fp8_bf16_b, the pair on all B * rows rows), margs counted inside one
+    element."""
     b, rows, c = _batch_rows("residual_ln", x, batch)
     _rows(y, "y")
     x_out = torch.empty_like(x) if x_out is None else x_out
     if b > 1:
         if fp8:
-            raise HipLibraryError("residual_ln: the fp8-output norms have no batched form (include/fairygen_hip_rowbatch.h)")
+            q, sc = _fp8_rows_out(x)
+            _call("fg_residual_ln_fp8_bf16_b", _ptr(x), _ptr(y), gate, _ptr(x_out), p1, p2, _ptr(q), _ptr(sc), affine, b, rows, c, eps, *margs,
+                  FP8_E4M3FN_MAX, _stream(x))
+            return x_out, (q, sc)
         norm_out = torch.empty_like(x) if norm_out is None else norm_out
         _call("fg_residual_ln_bf16_b", _ptr(x), _ptr(y), gate, _ptr(x_out), p1, p2, _ptr(norm_out), affine, b, rows, c, eps, *margs, _stream(x))
         return x_out, norm_out
@@ -385,11 +403,16 @@ def _fp8_rows_out(x):
     return _fp8_pair(*_rows(x, "x"), x.device)
 
 
-def ln_modulate_fp8(x, mod, shift_idx, scale_idx, eps):
+def ln_modulate_fp8(x, mod, shift_idx, scale_idx, eps, batch=None):
     """ln_modulate whose result goes to an fp8 Linear only: (x_fp8 (rows, C) e4m3fn, scale (rows, 1) fp32) = what fp8_quant_rows
-    makes of ln_modulate(x, ...), without the bf16 row in HBM."""
-    rows, c = _rows(x, "x")
+    makes of ln_modulate(x, ...), without the bf16 row in HBM.  batch: as ln_modulate's (fg_ln_modulate_fp8_bf16_b); the pair is
+    still that of all the rows of x — the operand of one GEMM."""
+    b, rows, c = _batch_rows("ln_modulate_fp8", x, batch)
     q, sc = _fp8_rows_out(x)
+    if b > 1:
+        _call("fg_ln_modulate_fp8_bf16_b", _ptr(x), mod.vec(shift_idx), mod.vec(scale_idx), _ptr(q), _ptr(sc), b, rows, c, eps,
+              *_mod_args(mod, rows), FP8_E4M3FN_MAX, _stream(x))
+        return q, sc
     _call("fg_ln_modulate_fp8_bf16", _ptr(x), mod.vec(shift_idx), mod.vec(scale_idx), _ptr(q), _ptr(sc), rows, c, eps,
           *_mod_args(mod, rows), FP8_E4M3FN_MAX, _stream(x))
     return q, sc
@@ -416,14 +439,16 @@ def ln_affine_dual(x, w, b, eps, out=None):
     return out, (q, sc)
 
 
-def residual_ln_modulate_fp8(x, y, mod, gate_idx, shift_idx, scale_idx, eps, x_out=None, norm_mod=None):
-    """residual_ln_modulate with the normalised row as (fp8 rows, scales): returns x_out, (x_fp8, scale)."""
-    return _residual_ln(x, y, eps, x_out, None, *_ln_modulate_args("residual_ln_modulate_fp8", x, mod, gate_idx, shift_idx, scale_idx, norm_mod), fp8=True)
+def residual_ln_modulate_fp8(x, y, mod, gate_idx, shift_idx, scale_idx, eps, x_out=None, norm_mod=None, batch=None):
+    """residual_ln_modulate with the normalised row as (fp8 rows, scales): returns x_out, (x_fp8, scale).  batch: as ln_modulate's
+    (fg_residual_ln_fp8_bf16_b)."""
+    return _residual_ln(x, y, eps, x_out, None,
+                        *_ln_modulate_args("residual_ln_modulate_fp8", x, mod, gate_idx, shift_idx, scale_idx, norm_mod, batch), fp8=True, batch=batch)
 
 
-def residual_ln_affine_fp8(x, y, w, b, eps, mod=None, gate_idx=None, x_out=None):
-    """residual_ln_affine with the normalised row as (fp8 rows, scales): returns x_out, (x_fp8, scale)."""
-    return _residual_ln(x, y, eps, x_out, None, *_ln_affine_args(x, w, b, mod, gate_idx), fp8=True)
+def residual_ln_affine_fp8(x, y, w, b, eps, mod=None, gate_idx=None, x_out=None, batch=None):
+    """residual_ln_affine with the normalised row as (fp8 rows, scales): returns x_out, (x_fp8, scale).  batch: as ln_modulate's."""
+    return _residual_ln(x, y, eps, x_out, None, *_ln_affine_args(x, w, b, mod, gate_idx, batch), fp8=True, batch=batch)
 
 
 def _rope_tables(who, cos, sin, rows, half):

@@ -39,7 +39,8 @@ class ModelConfig:
     attention_pv_dtype: Optional[torch.dtype] = None
     # torch.float8_e4m3fn (with both of the above): cross-attention in the e4m3 form too (enable_qk8_attention(pv8=True, cross=True)); None: bf16
     cross_attention_dtype: Optional[torch.dtype] = None
-    # True: a merged CFG call (pipe(..., cfg_merge=True)) runs both branches in ONE stacked forward of the DiT (WanModel.enable_stacked_cfg)
+    # True: a merged CFG call (pipe(..., cfg_merge=True)) runs both branches in ONE stacked forward of the DiT (WanModel.enable_stacked_cfg;
+    # with an fp8 computation_dtype: enable_stacked_cfg(fp8_linear=True))
     stacked_cfg: bool = False
     clear_parameters: bool = False
 
@@ -241,7 +242,8 @@ class ModelPool:
             if vram_config.get("stacked_cfg"):
                 if not hasattr(model, "enable_stacked_cfg"):
                     raise NotImplementedError(f"stacked_cfg is only built for the DiT, not for {cfg['model_name']}")
-                model.enable_stacked_cfg()
+                # with an fp8 computation_dtype the config states both wishes in one place: the stacked forward in the fp8 Linear mode
+                model.enable_stacked_cfg(fp8_linear=fp8)
             self.model.append(model)
             self.model_name.append(cfg["model_name"])
             self.model_path.append(path)

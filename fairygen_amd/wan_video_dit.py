@@ -90,9 +90,10 @@ def gemm_bias_gelu_own(x, weight, bias, **state):
     return hip.gemm_epilogue(x, weight, bias, act="gelu_tanh", **state)
 
 
-def gemm_fp8_own(xq, scale_a, w8, bias, **state):
-    """fp8_linear's matmul on the e4m3 form of the persistent kernel: (rows, K) e4m3 x (N, K) e4m3 -> (1, rows, N) bf16."""
-    return hip.gemm_fp8(xq, scale_a, w8, bias, lead_shape=(1, xq.shape[0]), **state)
+def gemm_fp8_own(xq, scale_a, w8, bias, batch=1, **state):
+    """fp8_linear's matmul on the e4m3 form of the persistent kernel: (rows, K) e4m3 x (N, K) e4m3 -> (1, rows, N) bf16.  batch=B (passed
+    by a stacked forward only): the rows are B elements' and the result is (B, rows / B, N), still one GEMM."""
+    return hip.gemm_fp8(xq, scale_a, w8, bias, lead_shape=(batch, xq.shape[0] // batch), **state)
 
 
 def fp8_own_ok(n, k):
@@ -127,13 +128,19 @@ def stack_hot_loras(per_group, shapes, device, dtype):
 
 class Act(NamedTuple):
     """What a norm hands to the Linears behind it: the bf16 row, its (e4m3 rows, row scales) pair, or both — _BlockLinears decides which
-    once per forward.  An fp8 Linear that gets the bf16 row only quantises it itself (fg_fp8_quant_rows_bf16)."""
+    once per forward.  An fp8 Linear that gets the bf16 row only quantises it itself (fg_fp8_quant_rows_bf16).  nb: the elements of a
+    stacked forward (WanModel.enable_stacked_cfg) behind a pair without a bf16 row — the pair is (nb * rows, C), one GEMM operand."""
     bf16: Optional[torch.Tensor] = None
     q8: Optional[tuple] = None
+    nb: int = 1
+
+    @property
+    def batch(self):
+        return self.bf16.shape[0] if self.bf16 is not None and self.bf16.dim() == 3 else self.nb
 
     @property
     def rows(self):
-        return self.bf16.shape[-2] if self.bf16 is not None else self.q8[0].shape[0]
+        return self.bf16.shape[-2] if self.bf16 is not None else self.q8[0].shape[0] // self.nb
 
     @property
     def total_rows(self):
@@ -170,13 +177,15 @@ class _BlockLinears:
         if self.want_bf16 and self.want_q8:
             return Act(*hip.ln_modulate_dual(x, mod, shift_idx, scale_idx, self.eps, out=out))
         if self.want_q8:
-            return Act(None, hip.ln_modulate_fp8(x, mod, shift_idx, scale_idx, self.eps))
+            nb = self.batch_of(x)
+            return Act(None, hip.ln_modulate_fp8(x, mod, shift_idx, scale_idx, self.eps, batch=nb), nb or 1)
         return Act(hip.ln_modulate(x, mod, shift_idx, scale_idx, self.eps, out=out, batch=self.batch_of(x)))
 
     @staticmethod
     def batch_of(x):
         """batch= of the row kernels that read a table by the row inside the element: the leading dimension of a stacked forward
-        (WanModel.enable_stacked_cfg; only the bf16 norms get there), None for the one element every other forward has."""
+        (WanModel.enable_stacked_cfg; the bf16 norms and the fp8-output ones get there, the two-output ones of unfused adapters do
+        not), None for the one element every other forward has."""
         return x.shape[0] if x.dim() == 3 and x.shape[0] > 1 else None
 
     def affine(self, x, norm):
@@ -193,8 +202,9 @@ class _BlockLinears:
             x = self.gate_residual(x, y, mod, gate_idx)
             return x, self.modulate(x, norm_mod, shift_idx, scale_idx, out)
         if self.want_q8:
-            x, q8 = hip.residual_ln_modulate_fp8(x, y, mod, gate_idx, shift_idx, scale_idx, self.eps, x_out=x, norm_mod=norm_mod)
-            return x, Act(None, q8)
+            nb = self.batch_of(x)
+            x, q8 = hip.residual_ln_modulate_fp8(x, y, mod, gate_idx, shift_idx, scale_idx, self.eps, x_out=x, norm_mod=norm_mod, batch=nb)
+            return x, Act(None, q8, nb or 1)
         x, h = hip.residual_ln_modulate(x, y, mod, gate_idx, shift_idx, scale_idx, self.eps, x_out=x, norm_out=out, norm_mod=norm_mod,
                                         batch=self.batch_of(x))
         return x, Act(h)
@@ -204,8 +214,9 @@ class _BlockLinears:
             x = self.gate_residual(x, y, mod, gate_idx)
             return x, self.affine(x, norm)
         if self.want_q8:
-            x, q8 = hip.residual_ln_affine_fp8(x, y, norm.weight, norm.bias, self.eps, mod, gate_idx, x_out=x)
-            return x, Act(None, q8)
+            nb = self.batch_of(x)
+            x, q8 = hip.residual_ln_affine_fp8(x, y, norm.weight, norm.bias, self.eps, mod, gate_idx, x_out=x, batch=nb)
+            return x, Act(None, q8, nb or 1)
         x, h = hip.residual_ln_affine(x, y, norm.weight, norm.bias, self.eps, mod, gate_idx, x_out=x, batch=self.batch_of(x))
         return x, Act(h)
 
@@ -293,12 +304,14 @@ class _BlockLinears:
         return a.q8 if a.q8 is not None else hip.fp8_quant_rows(a.bf16, None)
 
     def plain(self, a, names, weight, bias, w8, own=False, gelu=False, hip_adapters=True):
-        """Linear (+ the adapters of `names`: the column groups of a fused projection) (+ GELU(tanh)) of the Act `a` -> (1, rows, N) bf16.
+        """Linear (+ the adapters of `names`: the column groups of a fused projection) (+ GELU(tanh)) of the Act `a` -> (1, rows, N) bf16
+        ((B, rows, N) from the Act of a stacked forward: one GEMM on its B * rows rows).
         weight / w8: the bf16 and e4m3 (None in bf16 mode) forms; own: bf16 mode, the own GEMM may take this Linear (FAIRYGEN_GEMM).
         gelu (ffn.0): the result is nn.GELU's output — except with gelu_in_quant, where it is the pre-activation."""
         m, fp8 = self.model, self.fp8
         n, k = weight.shape
         rows = a.total_rows      # a stacked forward: the rows of all elements in one GEMM
+        stacked = {"batch": a.batch} if a.batch > 1 else {}      # ... whose fp8 form returns (B, rows / B, N)
         own = fp8 is None and own and own_gemm_ok(rows, n, k)
         if hip_adapters and self.hip_hot and (fp8 is None or fp8_own_ok(n, k)):
             pack = m._hot_pack(names)
@@ -310,13 +323,13 @@ class _BlockLinears:
             own = False      # the reference's ops for this Linear: library GEMM, adapters, GELU
         if gelu and pack is None and not self.gelu_in_quant:      # nothing between the Linear and its GELU: into the GEMM's store where one takes it
             if fp8 is not None and fp8_own_ok(n, k):
-                return hip.gemm_fp8(*a.q8, w8, bias, act="gelu_tanh", lead_shape=(1, rows), **self.state(rows, n, k))
+                return hip.gemm_fp8(*a.q8, w8, bias, act="gelu_tanh", lead_shape=(a.batch, rows // a.batch), **self.state(rows, n, k))
             if own:
                 return gemm_bias_gelu_own(a.bf16, weight, bias, **self.state(rows, n, 2 * k))
             if fp8 is None and m.gelu_epilogue:      # GELU(tanh) in the hipBLASLt epilogue: one pass less over the (n, ffn) tensor
                 return gemm_bias_gelu(a.bf16, weight, bias)
         if fp8 is not None:
-            y = m._scaled_linear(*self.q8(a), w8, bias, **self.state(rows, n, k))
+            y = m._scaled_linear(*self.q8(a), w8, bias, **stacked, **self.state(rows, n, k))
         else:
             y = gemm_bias_own(a.bf16, weight, bias, **self.state(rows, n, 2 * k)) if own else gemm_bias(a.bf16, weight, bias)
         if gelu and pack:      # GELU moves from the GEMM's store into the adapter kernel's
@@ -333,7 +346,7 @@ class _BlockLinears:
         and in fg_lora_apply_bf16, then the norm alone; or a plain GEMM, the adapters, and the fused residual + norm kernel.
         a: bf16; gelu: it is ffn.0's pre-activation (gelu_in_quant).  tuned / store_ok: ffn.2's library GEMM comes from the tuning table,
         and FAIRYGEN_GEMM=fused-ffn2 keeps it there.
-        A stacked forward (a: (B, rows, K), B > 1; bf16 Linears without unfused adapters only): the store picks its gate row by
+        A stacked forward (a: (B, rows, K), B > 1; no unfused adapters; fp8 Linears take the second form): the store picks its gate row by
         `row >= first_rows` over the rows of the launch, so with a two-row gate table it is launched once per element on the element's
         rows — the batch-1 forward's launch, the batch-1 forward's bits; with one gate row or none, one launch takes all B * rows rows.
         The other form runs its GEMM on B * rows rows and the batched row kernels (include/fairygen_hip_rowbatch.h) do the gate."""
@@ -360,7 +373,9 @@ class _BlockLinears:
         if fp8 is None:
             y = (gemm_bias_tuned if tuned else gemm_bias)(a, weight, bias)
         else:
-            y = m._scaled_linear(*hip.fp8_quant_rows(a, "gelu_tanh" if gelu else None), w8, bias, **self.state(a.shape[1], n, k))
+            # stacked: the quantisation is per row, so all nb * rows rows are one pass and one GEMM, and y comes back (nb, rows, N)
+            y = m._scaled_linear(*hip.fp8_quant_rows(a, "gelu_tanh" if gelu else None), w8, bias, **({"batch": nb} if nb > 1 else {}),
+                                 **self.state(nb * a.shape[1], n, k))
         if pack is not None:      # only then is nn.GELU's bf16 output needed
             m._hot_apply((name,), hip.activation(a.clone(), "gelu_tanh") if gelu else a, y, pack)
         if affine is not None:
@@ -542,6 +557,8 @@ class WanModel(nn.Module):
         self.cross8_attention = False
         # a merged CFG call (cfg_merge=True) as ONE forward on x (2, N, dim) instead of two batch-1 forwards; see enable_stacked_cfg
         self.stacked_cfg = False
+        # ... also when the blocks' Linears run in the fp8 mode (enable_stacked_cfg(fp8_linear=True)); False: that combination raises
+        self.stacked_cfg_fp8 = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -627,7 +644,7 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ the stacked CFG forward
-    def enable_stacked_cfg(self, flag=True):
+    def enable_stacked_cfg(self, flag=True, fp8_linear=False):
         """Opt-in, off by default: a merged CFG call (cfg_merge=True: the positive and the negative context batched, wan_video.py
         model_fn_wan_video_steps) runs ONE forward on the residual stream (2, N, dim) instead of two batch-1 forwards one after the other.
         The time rows, the modulation tables and the RoPE tables are one element's and shared; the row kernels that read them take the
@@ -635,14 +652,23 @@ class WanModel(nn.Module):
         row run on 2 N rows in one GEMM; the gated store with two gate rows (TI2V) is launched per element (_BlockLinears.residual);
         attention runs with B = 2 — bf16, or with the e4m3 modes on the batched entry points of include/fairygen_hip_batch8.h.  Block 0's
         self-attention half does not see the context and is computed once on N rows (CFG_SHARE_PREFIX).  With the switch off every path
-        is what it was.  What it does not take raises NotImplementedError at the merged call (check_stacked_cfg).  DESIGN.md §5."""
+        is what it was.  What it does not take raises NotImplementedError at the merged call (check_stacked_cfg).  DESIGN.md §5.
+        fp8_linear: off by default, and then a model in the fp8 Linear mode (enable_fp8_linear) raises at the merged call.  True lets the
+        stacked forward run in that mode too: the norms that hand their row to an fp8 Linear take the batch through
+        include/fairygen_hip_rowbatch8.h and leave ONE (2 N, C) e4m3 operand with its 2 N row scales, every fp8 Linear is one GEMM on 2 N
+        rows (the context's k | v on 2 L), the per-row quantisation in front of o and ffn.2 is one pass over 2 N rows, and the gates run
+        on the batched row kernels — as in the batch-1 fp8 forward, none of them in a GEMM's store.  FAIRYGEN_FP8_FOLD=0 (bf16 norms, then
+        the quantisation pass) works stacked as well.  enable_stacked_cfg(False) clears both."""
         self.stacked_cfg = bool(flag)
+        self.stacked_cfg_fp8 = bool(flag) and bool(fp8_linear)
         return self
 
     def check_stacked_cfg(self, context_batch, shard=None, sliding_window=False):
-        """What a merged call must not meet while enable_stacked_cfg is on; decided on the host before anything is launched."""
-        if self.fp8_dtype is not None:
-            raise NotImplementedError("stacked_cfg with enable_fp8_linear: the fp8-output norm kernels have no batched form")
+        """What a merged call must not meet while enable_stacked_cfg is on; decided on the host before anything is launched.  The fp8 Linear
+        mode passes only with enable_stacked_cfg(fp8_linear=True); everything else raises with it as without."""
+        if self.fp8_dtype is not None and not self.stacked_cfg_fp8:
+            raise NotImplementedError("stacked_cfg with enable_fp8_linear: the stacked forward takes the fp8 Linear mode only when it is asked "
+                                      "to, enable_stacked_cfg(fp8_linear=True)")
         if self.hot_loras:
             raise NotImplementedError(f"stacked_cfg with hot-loaded adapters on hot_backend={self.hot_lora_backend!r}: fg_lora_apply_bf16's gate "
                                       "has no batched form; hot_backend='fused' adapters are plain weights and work")
@@ -662,17 +688,18 @@ class WanModel(nn.Module):
                                       "Q K^T form span all ranks' tokens and would need a collective; enable_qk8_attention(sharded=True) "
                                       "runs that exchange")
 
-    def _scaled_linear(self, xq, scale_a, w8, bias, **state):
+    def _scaled_linear(self, xq, scale_a, w8, bias, batch=1, **state):
         """fp8_linear's matmul (:347-354: torch._scaled_mm with row-wise scale_a, unit scale_b, bf16 bias, bf16 out): on this repo's e4m3
-        MFMA kernel (fg_gemm_fp8_bf16), or — FAIRYGEN_FP8_GEMM=lib, and for shapes the kernel does not take — the library call itself."""
+        MFMA kernel (fg_gemm_fp8_bf16), or — FAIRYGEN_FP8_GEMM=lib, and for shapes the kernel does not take — the library call itself.
+        (1, rows, N); batch=B (a stacked forward): (B, rows / B, N) from the one matmul on all rows."""
         n = w8.shape[0]
         if fp8_own_ok(n, xq.shape[1]):
-            return gemm_fp8_own(xq, scale_a, w8, bias, **state)
+            return gemm_fp8_own(xq, scale_a, w8, bias, **({"batch": batch} if batch > 1 else {}), **state)
         key = (n, xq.device)
         if key not in self._ones:
             self._ones[key] = torch.ones((1, n), dtype=torch.float32, device=xq.device)
         return torch._scaled_mm(xq, w8.T, scale_a=scale_a, scale_b=self._ones[key], bias=bias,
-                                out_dtype=torch.bfloat16).unsqueeze(0)
+                                out_dtype=torch.bfloat16).view(batch, xq.shape[0] // batch, n)
 
     # ------------------------------------------------------------------ hot-loaded LoRA (core/vram/layers.py:417-436)
     def check_hot_backend(self, backend):

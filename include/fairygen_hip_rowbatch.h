@@ -20,7 +20,8 @@
  * The tables have the rows of ONE element (mod_rows rows of mod_ld; `rows` rows of RoPE) and are indexed by the row inside the element.
  *
  * The row kernels that read no per-row table — fg_ln_affine_bf16, fg_rmsnorm_rope_bf16 with NULL tables — take the B * rows rows as
- * they are and have no form here; nor have the fp8-output norms, the grouped RoPE form and fg_lora_apply_bf16's gate.
+ * they are and have no form here; nor have the grouped RoPE form and fg_lora_apply_bf16's gate.  The fp8-output norms have theirs in
+ * fairygen_hip_rowbatch8.h.
  */
 #ifndef FAIRYGEN_HIP_ROWBATCH_H
 #define FAIRYGEN_HIP_ROWBATCH_H

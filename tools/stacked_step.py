@@ -2,11 +2,13 @@
 
     python tools/stacked_step.py                                  # N = 8 190 and N = 27 280, bf16 attention and pv8 + cross + fused producers
     python tools/stacked_step.py --sizes n8190 --attn bf16 --layers 4      # a short look
+    python tools/stacked_step.py --linear fp8                     # the same legs in the fp8 Linear mode (enable_fp8_linear)
 
 Legs: "two-call" (the default loop: two batch-1 forwards that share block 0's self-attention half), "merged" (cfg_merge=True with the
 switch off: the merged call evaluated element by element — the same launches as two-call) and "stacked" (cfg_merge=True with
 WanModel.enable_stacked_cfg(): one forward on (2, N, dim)).  Sizes: "n8190" (latent (1,48,13,42,60)) and "headline" (704x1280x121, latent
 (1,48,31,44,80), N = 27 280).  Full width, 30 blocks, synthetic weights, TI2V with CFG 5, kv_cache on — the loop the pipeline runs.
+--linear fp8: the blocks' Linears in the fp8 mode in all three legs, the stacked leg with enable_stacked_cfg(fp8_linear=True).
 
 A round runs every leg once, in order; `--rounds` rounds follow each other, so a leg's samples are spread over the run and drift hits all
 legs alike.  A leg is ONE denoise call of `1 + --warmup + --steps` steps; step 0 (tables, kv_cache) and the warm-up steps are not timed,
@@ -65,7 +67,7 @@ class Timed:
         return [a.elapsed_time(b) for a, b in zip(self.events, self.events[1:])]
 
 
-def leg(pipe, shape, mode, warmup, steps, dev):
+def leg(pipe, shape, mode, warmup, steps, dev, fp8=False):
     g = torch.Generator("cpu").manual_seed(0)
     rnd = lambda *s: torch.randn(s, generator=g).to(torch.bfloat16).to(dev)      # noqa: E731
     lat, ctx_p, ctx_n, z0 = rnd(*shape), rnd(1, 512, 4096), rnd(1, 512, 4096), rnd(*shape[:2], 1, *shape[3:])
@@ -76,7 +78,7 @@ def leg(pipe, shape, mode, warmup, steps, dev):
     if mode != "two-call":      # what WanVideoUnit_CfgMerger leaves: the contexts batched in the shared inputs
         shared.update(cfg_merge=True, context=torch.cat([ctx_p, ctx_n], 0))
         posi, nega = {}, {}
-    pipe.dit.enable_stacked_cfg(mode == "stacked")
+    pipe.dit.enable_stacked_cfg(mode == "stacked", fp8_linear=fp8)
     bar = Timed(1 + warmup)
     try:
         with torch.no_grad():
@@ -96,10 +98,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--layers", type=int, default=0, help="debug: fewer DiT layers")
+    ap.add_argument("--linear", default="bf16", choices=("bf16", "fp8"), help="the blocks' Linears: bf16, or the fp8 Linear mode in every leg")
     a = ap.parse_args()
     hip.load()
     dev = "cuda"
     pipe = build(a.layers, dev)
+    fp8 = a.linear == "fp8"
+    if fp8:
+        pipe.dit.enable_fp8_linear()
     rows = []
     for size in a.sizes.split(","):
         n = SIZES[size][2] * (SIZES[size][3] // 2) * (SIZES[size][4] // 2)
@@ -109,7 +115,7 @@ def main():
             samples, outs = {m: [] for m in a.legs.split(",")}, {}
             for _ in range(a.rounds):
                 for mode in samples:
-                    ms, out = leg(pipe, SIZES[size], mode, a.warmup, a.steps, dev)
+                    ms, out = leg(pipe, SIZES[size], mode, a.warmup, a.steps, dev, fp8)
                     samples[mode] += ms
                     outs[mode] = out
             ref = outs.get("two-call")
@@ -124,7 +130,7 @@ def main():
             del outs, ref
             gc.collect()
             torch.cuda.empty_cache()
-    print(json.dumps({"tool": "stacked_step", "layers": a.layers or 30, "rounds": a.rounds, "warmup": a.warmup, "steps": a.steps,
+    print(json.dumps({"tool": "stacked_step", **({"linear": "fp8"} if fp8 else {}), "layers": a.layers or 30, "rounds": a.rounds, "warmup": a.warmup, "steps": a.steps,
                       "device": torch.cuda.get_device_name(0), "legs": rows}))
 
 
