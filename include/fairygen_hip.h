@@ -310,7 +310,8 @@ int fg_conv_pack_weight_bf16(const void* w, void* packed, int Cout, int Cin, int
  * t reads input frames t .. t+kt-1.  out (T,H,W,Cout), or with time_interleave!=0 (Resample.forward :153-156,
  * Cout = 2*Cout2): out (2T,H,W,Cout2) with channel block j of frame t written to frame 2t+j.
  * residual (same shape as out, or NULL) is added after the bf16 rounding of conv+bias (ResidualBlock :301).
- * Cin % 8 == 0; Cout % 4 == 0; input and packed weights < 3.75 GiB each (32-bit buffer offsets). */
+ * Cin % 8 == 0; Cout % 4 == 0; input and packed weights < 3.75 GiB each (32-bit buffer offsets).
+ * The shapes and rounding points are pinned by tests/test_conv_shapes.py. */
 int fg_conv3d_cl_bf16(const void* x, const void* w_packed, const void* bias,
                       const void* residual, void* out,
                       int T, int H, int W, int Cin, int Cout, int kt, int ks,
