@@ -63,7 +63,8 @@ def main():
                     help="... and cross-attention over the text context in the same e4m3 form; implies --pv8-attention")
     ap.add_argument("--stacked-cfg", action="store_true",
                     help="both CFG branches in ONE stacked forward of the DiT per step (implies cfg_merge=True); single GPU, bf16 Linears or, "
-                         "with --fp8, the fp8 Linear mode (the loader then calls enable_stacked_cfg(fp8_linear=True)); no unfused --lora adapters")
+                         "with --fp8, the fp8 Linear mode (the loader then calls enable_stacked_cfg(fp8_linear=True)); --lora here is fused into the weights and works; unfused hot-loaded "
+                         "adapters need hot_backend='hip' and ModelConfig(stacked_cfg_hot_lora=True)")
     a = ap.parse_args()
     pv8 = a.pv8_attention or a.cross8_attention
     pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or pv8, pv8, a.cross8_attention, a.stacked_cfg)

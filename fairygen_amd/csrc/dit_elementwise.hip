@@ -6,6 +6,7 @@
 #include "common.h"
 #include "../../include/fairygen_hip_rowbatch.h"      // the batched forms of the row kernels that read a per-row table
 #include "../../include/fairygen_hip_rowbatch8.h"     // ... and of the norms with the fp8 output
+#include "../../include/fairygen_hip_lorabatch.h"     // ... and of the two-output norm of unfused adapters
 #include "rmsnorm_rope_row.h"     // Row, load_row, ld8, st8 and the RMSNorm+RoPE row arithmetic
 
 // Row kernels (one wave per token row held in registers): second launch-bound = minimum waves per SIMD the register
@@ -144,13 +145,19 @@ __global__ FG_ROW_BOUNDS void ln_dual_kernel(const bf16* __restrict__ x, const b
                                              bf16* __restrict__ out, uint8_t* __restrict__ out8, float* __restrict__ scale_out,
                                              int64_t rows, int C, float eps, int64_t mod_rows, int64_t first_rows, int64_t mod_ld,
                                              float fp8_max) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    Row r;
-    load_row(x + row * C, C, lane, r);
-    const int64_t m = MODE == 0 ? mod_row(row, mod_rows, first_rows) : 0;
-    norm_store_fp8<MODE, true>(r, C, lane, eps, p0 + m * mod_ld, p1 + m * mod_ld, out8 + row * C, scale_out + row, fp8_max, out + row * C);
+#include "ln_dual_body.inc"
+}
+
+// ... on a batch that shares the table (include/fairygen_hip_lorabatch.h; MODE 0 only — the affine form reads no table and runs on all
+// rows as it is): as ln_modulate_fp8_b_kernel, with the bf16 row moving with x as well
+template <int MODE>
+__global__ FG_ROW_BOUNDS void ln_dual_b_kernel(const bf16* __restrict__ x, const bf16* __restrict__ p0, const bf16* __restrict__ p1,
+                                               bf16* __restrict__ out, uint8_t* __restrict__ out8, float* __restrict__ scale_out,
+                                               int64_t rows, int C, float eps, int64_t mod_rows, int64_t first_rows, int64_t mod_ld,
+                                               float fp8_max) {
+    const int64_t e0 = (int64_t)blockIdx.y * rows * C;
+    x += e0; out += e0; out8 += e0; scale_out += (int64_t)blockIdx.y * rows;
+#include "ln_dual_body.inc"
 }
 
 __global__ FG_ROW_BOUNDS void ln_modulate_kernel(const bf16* __restrict__ x, const bf16* __restrict__ shift,
@@ -711,6 +718,23 @@ int fg_residual_ln_fp8_bf16_b(const void* x, const void* y, const void* gate, vo
                            (const bf16*)y, (const bf16*)gate, (bf16*)x_out, (const bf16*)p0, (const bf16*)p1, (uint8_t*)norm_fp8,
                            norm_scale, rows, C, eps, mod_rows, first_rows, mod_ld, fp8_max);
     return fg_launch_status("fg_residual_ln_fp8_bf16_b");
+}
+
+// ---- include/fairygen_hip_lorabatch.h: the two-output modulate norm on B elements of `rows` rows each (its version query is next to
+// fg_lora_apply_bf16_b, lora.hip); checks as above.
+int fg_ln_modulate_dual_bf16_b(const void* x, const void* shift, const void* scale, void* out, void* out_fp8, float* out_scale, int B,
+                               int64_t rows, int C, float eps, int64_t mod_rows, int64_t first_rows, int64_t mod_ld, float fp8_max,
+                               fg_stream_t stream) {
+    if (int e = check_rows("fg_ln_modulate_dual_bf16_b", rows, C, mod_rows, first_rows)) return e;
+    if (int e = check_batch("fg_ln_modulate_dual_bf16_b", B)) return e;
+    FG_CHECK_ARG(x && shift && scale && out && out_fp8 && out_scale, "fg_ln_modulate_dual_bf16_b: null pointer");
+    FG_CHECK_ARG(FG_ALIGNED16(x) && FG_ALIGNED16(shift) && FG_ALIGNED16(scale) && FG_ALIGNED16(out) && (((uintptr_t)out_fp8) & 7) == 0 &&
+                     mod_ld % 8 == 0 && fp8_max > 0.f,
+                 "fg_ln_modulate_dual_bf16_b: pointers / mod_ld must be 16-byte aligned (out_fp8: 8), fp8_max positive");
+    if (rows == 0) return FG_OK;
+    hipLaunchKernelGGL(ln_dual_b_kernel<0>, row_grid_b(rows, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (const bf16*)shift,
+                       (const bf16*)scale, (bf16*)out, (uint8_t*)out_fp8, out_scale, rows, C, eps, mod_rows, first_rows, mod_ld, fp8_max);
+    return fg_launch_status("fg_ln_modulate_dual_bf16_b");
 }
 
 }  // extern "C"

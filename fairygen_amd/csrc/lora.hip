@@ -16,6 +16,7 @@
 //            output row per register quad; one v_permlane32_swap per dword pairs the quads of the two lane halves into 8 consecutive
 //            columns, so the read-modify-write of `out` is dwordx4 per lane.
 #include "common.h"
+#include "../../include/fairygen_hip_lorabatch.h"     // the adapter kernel on batches that share their gate table
 
 namespace {
 
@@ -37,185 +38,7 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 // RT: 32-row tiles of the per-group rank R (R = 32 RT); GC: groups whose t is computed in one pass over x (G % GC == 0).
 template <int RT, int GC>
 __global__ __launch_bounds__(256, RT * GC <= 3 ? 2 : 1) void lora_apply_kernel(const LoraParams P) {
-    constexpr int R = 32 * RT, NT = RT * GC;      // NT rank tiles per pass
-    extern __shared__ __attribute__((aligned(16))) char smem_lora[];
-    constexpr int kRedBytes = 2 * NT * 16 * 64 * 4;                            // one wave's partial sums: 2 * NT tiles x 16 registers x 64 lanes of fp32
-    float* red = reinterpret_cast<float*>(smem_lora);
-    bf16* tl = reinterpret_cast<bf16*>(smem_lora + kRedBytes);                 // t: (64, ldt) bf16
-    const int ldt = P.G * R + kTPad;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 31, lh = lane >> 5;
-    const int64_t m0 = (int64_t)blockIdx.x * kRows;
-
-    // ---------------------------------------------------------------- phase 1: t = bf16(x A^T), rows m0 .. m0 + 63
-    const bf16* xrow[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        int64_t row = m0 + 32 * mt + lr;
-        row = row < P.M ? row : (int64_t)P.M - 1;      // rows past M: a valid address, the results are never stored
-        xrow[mt] = P.x + row * P.ldx + 32 * lh;
-    }
-    const int chunks = P.K / 64;
-    for (int pass = 0; pass < P.G / GC; ++pass) {
-        const bf16* arow = P.a + ((int64_t)pass * NT * 32 + lr) * P.K + 32 * lh;
-        f32x16 acc[2][NT];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int rt = 0; rt < NT; ++rt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[mt][rt][i] = 0.f;
-        // a wave's chunks are c = wave, wave + 4, ...; an iteration takes half a chunk (MFMA steps 2i' and 2i' + 1: 32 bytes per lane and row),
-        // which keeps the double-buffered fragments small enough for two waves per SIMD
-        bf16x8 xf[2][2], af[NT][2];
-        auto load = [&](int it) {
-            const int off = (wave + 4 * (it >> 1)) * 64 + 16 * (it & 1);
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) xf[mt][s] = *reinterpret_cast<const bf16x8*>(xrow[mt] + off + 8 * s);
-#pragma unroll
-                for (int rt = 0; rt < NT; ++rt) af[rt][s] = *reinterpret_cast<const bf16x8*>(arow + (int64_t)rt * 32 * P.K + off + 8 * s);
-            }
-        };
-        const int iters = wave < chunks ? 2 * ((chunks - wave + 3) / 4) : 0;
-        if (iters > 0) load(0);
-        for (int it = 0; it < iters; ++it) {
-            bf16x8 xc[2][2], ac[NT][2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) xc[mt][s] = xf[mt][s];
-#pragma unroll
-                for (int rt = 0; rt < NT; ++rt) ac[rt][s] = af[rt][s];
-            }
-            if (it + 1 < iters) load(it + 1);      // the next half chunk's loads fly under this one's MFMAs
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int rt = 0; rt < NT; ++rt)
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-                        acc[mt][rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ac[rt][s], xc[mt][s], acc[mt][rt], 0, 0, 0);
-        }
-        // wave 0 += wave 1, 2, 3 (fp32, fixed order); the partials keep their register layout, so the buffer is indexed [register][lane]
-        for (int w = 1; w < 4; ++w) {
-            if (wave == w) {
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int rt = 0; rt < NT; ++rt)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const f32x4 v = {acc[mt][rt][4 * q], acc[mt][rt][4 * q + 1], acc[mt][rt][4 * q + 2], acc[mt][rt][4 * q + 3]};
-                            reinterpret_cast<f32x4*>(red)[(((mt * NT + rt) * 4 + q) * 64) + lane] = v;
-                        }
-            }
-            __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int rt = 0; rt < NT; ++rt)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const f32x4 v = reinterpret_cast<const f32x4*>(red)[(((mt * NT + rt) * 4 + q) * 64) + lane];
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) acc[mt][rt][4 * q + i] += v[i];
-                        }
-            }
-            __syncthreads();
-        }
-        // register 4q + i of lane (lr, lh) is t^T[rank 8q + 4lh + i][row lr] of its tile: 4 consecutive ranks of one row -> 8 bytes of t
-        if (wave == 0) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int rt = 0; rt < NT; ++rt)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const u32x2 v = {pack_bf16x2(acc[mt][rt][4 * q], acc[mt][rt][4 * q + 1]), pack_bf16x2(acc[mt][rt][4 * q + 2], acc[mt][rt][4 * q + 3])};
-                        *reinterpret_cast<u32x2*>(tl + (32 * mt + lr) * ldt + (pass * NT + rt) * 32 + 8 * q + 4 * lh) = v;
-                    }
-        }
-    }
-    __syncthreads();
-
-    // ---------------------------------------------------------------- phase 2: out = epi(out, bf16(t B^T)) in 64-column blocks
-    const int nblk = P.Ng / 64, mode = P.mode;
-    int64_t orow[2];
-    bool live[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const int64_t row = m0 + 32 * mt + lr;
-        live[mt] = row < P.M;
-        orow[mt] = (live[mt] ? row : (int64_t)P.M - 1);
-    }
-    for (int u = wave; u < P.G * nblk; u += 4) {
-        const int g = u / nblk, nb = u - g * nblk;
-        const int64_t col0 = (int64_t)g * P.Ng + nb * 64 + 8 * lh;      // this lane's first column after the half-wave swap
-        // the old values at the columns this lane will own after the swap: quad pair q of tile nt = columns 32nt + 16q + 8lh + 0..7
-        u32x4 ov[2][2][2];
-        if (mode != 0) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) ov[mt][nt][q] = *reinterpret_cast<const u32x4*>(P.out + orow[mt] * P.ldc + col0 + 32 * nt + 16 * q);
-        }
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
-        const bf16* brow = P.b + ((int64_t)g * P.Ng + nb * 64 + lr) * R + 8 * lh;
-        const bf16* trow = tl + lr * ldt + g * R + 8 * lh;
-#pragma unroll
-        for (int s = 0; s < 2 * RT; ++s) {
-            bf16x8 bfr[2], tf[2];
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) bfr[nt] = *reinterpret_cast<const bf16x8*>(brow + (int64_t)nt * 32 * R + 16 * s);
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) tf[mt] = *reinterpret_cast<const bf16x8*>(trow + mt * 32 * ldt + 16 * s);
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[nt], tf[mt], acc[mt][nt], 0, 0, 0);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    // quads 2q and 2q + 1 (columns 16q + 4lh + 0..3 and 16q + 8 + 4lh + 0..3 of row lr), rounded to bf16, then paired across the halves
-                    uint32_t a0 = pack_bf16x2(acc[mt][nt][8 * q], acc[mt][nt][8 * q + 1]), a1 = pack_bf16x2(acc[mt][nt][8 * q + 2], acc[mt][nt][8 * q + 3]);
-                    uint32_t b0 = pack_bf16x2(acc[mt][nt][8 * q + 4], acc[mt][nt][8 * q + 5]), b1 = pack_bf16x2(acc[mt][nt][8 * q + 6], acc[mt][nt][8 * q + 7]);
-                    const auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                    const auto r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                    const u32x4 lw = {r0[0], r1[0], r0[1], r1[1]};
-                    const bf16x8 l8 = __builtin_bit_cast(bf16x8, lw);
-                    bf16x8 o8 = l8;
-                    if (mode != 0) {
-                        const bf16x8 old = __builtin_bit_cast(bf16x8, ov[mt][nt][q]);
-                        if (mode == 2) {
-                            // the gate table is a few KiB and stays in L2: read here rather than held across the MFMAs
-                            const bf16x8 g8 = *reinterpret_cast<const bf16x8*>(P.gate + (orow[mt] >= P.first_rows ? P.gate_ld : 0) + col0 + 32 * nt + 16 * q);
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) o8[j] = (bf16)((float)old[j] + rbf((float)g8[j] * (float)l8[j]));
-                        } else if (mode == 4) {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) o8[j] = (bf16)gelu_tanh_epilogue(rbf((float)old[j] + (float)l8[j]));
-                        } else {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) o8[j] = (bf16)((float)old[j] + (float)l8[j]);
-                        }
-                    }
-                    if (live[mt]) *reinterpret_cast<bf16x8*>(P.out + orow[mt] * P.ldc + col0 + 32 * nt + 16 * q) = o8;
-                }
-    }
+#include "lora_apply_body.inc"
 }
 
 template <int RT, int GC>
@@ -226,6 +49,28 @@ int launch_lora(const LoraParams& P, hipStream_t stream) {
     FG_CHECK_ARG(attr == hipSuccess, "fg_lora_apply_bf16: cannot reserve LDS: %s", hipGetErrorString(attr));
     hipLaunchKernelGGL((lora_apply_kernel<RT, GC>), dim3((unsigned)((P.M + kRows - 1) / kRows)), dim3(256), lds, stream, P);
     return fg_launch_status("fg_lora_apply_bf16");
+}
+
+// The batched form (include/fairygen_hip_lorabatch.h): x / out are the B * M rows of one matrix each, the second grid dimension picks the
+// element, and the element runs the body above on its own pointers — M, first_rows and the gate's row rule are ONE element's, A, B and
+// the gate table are shared.  No workgroup holds rows of two elements.  The element offset is 64-bit; everything behind it is the
+// single-element kernel's addressing.
+template <int RT, int GC>
+__global__ __launch_bounds__(256, RT * GC <= 3 ? 2 : 1) void lora_apply_b_kernel(const LoraParams PB) {
+    LoraParams P = PB;
+    P.x += (int64_t)blockIdx.y * PB.M * PB.ldx;
+    P.out += (int64_t)blockIdx.y * PB.M * PB.ldc;
+#include "lora_apply_body.inc"
+}
+
+template <int RT, int GC>
+int launch_lora_b(const LoraParams& P, int B, hipStream_t stream) {
+    const int lds = 2 * RT * GC * 16 * 64 * 4 + kRows * (P.G * 32 * RT + kTPad) * 2;
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(lora_apply_b_kernel<RT, GC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       2 * RT * GC * 16 * 64 * 4 + kRows * (kMaxGroups * 32 * RT + kTPad) * 2);
+    FG_CHECK_ARG(attr == hipSuccess, "fg_lora_apply_bf16_b: cannot reserve LDS: %s", hipGetErrorString(attr));
+    hipLaunchKernelGGL((lora_apply_b_kernel<RT, GC>), dim3((unsigned)((P.M + kRows - 1) / kRows), (unsigned)B), dim3(256), lds, stream, P);
+    return fg_launch_status("fg_lora_apply_bf16_b");
 }
 
 // ---------------------------------------------------------------- fg_lora_fuse_bf16: w' = bf16(w + bf16(alpha * bf16(B A)))
@@ -324,10 +169,10 @@ int launch_fuse(const FuseParams& P, hipStream_t stream) {
 
 }  // namespace
 
-extern "C" int fg_lora_apply_bf16(const void* x, int64_t ldx, const void* a, const void* b, void* out, int64_t ldc, int64_t M, int64_t K,
-                                  int64_t Ng, int64_t R, int64_t G, int mode, const void* gate, int64_t gate_rows, int64_t gate_ld,
-                                  int64_t first_rows, fg_stream_t stream) {
-    const char* what = "fg_lora_apply_bf16";
+// The checks of fg_lora_apply_bf16 on one element of M rows, and its parameters; shared with the batched entry point.
+static int lora_params(const char* what, LoraParams& P, const void* x, int64_t ldx, const void* a, const void* b, void* out, int64_t ldc,
+                       int64_t M, int64_t K, int64_t Ng, int64_t R, int64_t G, int mode, const void* gate, int64_t gate_rows,
+                       int64_t gate_ld, int64_t first_rows) {
     FG_CHECK_ARG(x && a && b && out, "%s: null pointer", what);
     FG_CHECK_ARG(mode == 0 || mode == 1 || mode == 2 || mode == 4, "%s: mode must be 0 (write), 1 (out + l), 2 (out + gate*l) or 4 (gelu_tanh(out + l))", what);
     FG_CHECK_ARG(M > 0 && K > 0 && Ng > 0 && G >= 1 && G <= kMaxGroups && K % 64 == 0 && Ng % 64 == 0,
@@ -339,11 +184,18 @@ extern "C" int fg_lora_apply_bf16(const void* x, int64_t ldx, const void* a, con
                  "%s: leading dimensions must cover the rows, rows and pointers 16-byte aligned", what);
     FG_CHECK_ARG(kRows * ldx * 2 < (1ll << 31) && kRows * ldc * 2 < (1ll << 31) && G * R * K * 2 < (1ll << 31) && G * Ng * R * 2 < (1ll << 31) && M < (1ll << 31),
                  "%s: tile spans must fit 31 bits", what);
-    LoraParams P;
     P.x = (const bf16*)x; P.a = (const bf16*)a; P.b = (const bf16*)b; P.out = (bf16*)out; P.gate = (const bf16*)gate;
     P.ldx = ldx; P.ldc = ldc; P.gate_ld = gate_rows == 2 ? gate_ld : 0;
     P.M = (int)M; P.K = (int)K; P.Ng = (int)Ng; P.G = (int)G; P.mode = mode;
     P.first_rows = gate_rows == 2 ? (int)(first_rows < 0 ? 0 : first_rows > M ? M : first_rows) : 0;
+    return FG_OK;
+}
+
+extern "C" int fg_lora_apply_bf16(const void* x, int64_t ldx, const void* a, const void* b, void* out, int64_t ldc, int64_t M, int64_t K,
+                                  int64_t Ng, int64_t R, int64_t G, int mode, const void* gate, int64_t gate_rows, int64_t gate_ld,
+                                  int64_t first_rows, fg_stream_t stream) {
+    LoraParams P;
+    if (int e = lora_params("fg_lora_apply_bf16", P, x, ldx, a, b, out, ldc, M, K, Ng, R, G, mode, gate, gate_rows, gate_ld, first_rows)) return e;
     hipStream_t s = (hipStream_t)stream;
     // q | k | v at rank 32 (the common adapter) share one pass over x; every other pack takes one pass per group
     if (R == 32 && G == 3) return launch_lora<1, 3>(P, s);
@@ -352,6 +204,29 @@ extern "C" int fg_lora_apply_bf16(const void* x, int64_t ldx, const void* a, con
         case 2: return launch_lora<2, 1>(P, s);
         case 3: return launch_lora<3, 1>(P, s);
         default: return launch_lora<4, 1>(P, s);
+    }
+}
+
+// ---- include/fairygen_hip_lorabatch.h: fg_lora_apply_bf16 on B elements of M rows each that share A, B and the gate table.  The checks
+// are the single-element entry point's on ONE element (M, first_rows count inside it), then B and the rows of the whole matrix.  The
+// batch needs no span check of its own: the kernel reaches an element's first row with a 64-bit offset and addresses rows in 64 bits.
+extern "C" int fg_dit_lorabatch_version(void) { return 1; }
+
+extern "C" int fg_lora_apply_bf16_b(const void* x, int64_t ldx, const void* a, const void* b, void* out, int64_t ldc, int B, int64_t M,
+                                    int64_t K, int64_t Ng, int64_t R, int64_t G, int mode, const void* gate, int64_t gate_rows,
+                                    int64_t gate_ld, int64_t first_rows, fg_stream_t stream) {
+    const char* what = "fg_lora_apply_bf16_b";
+    LoraParams P;
+    if (int e = lora_params(what, P, x, ldx, a, b, out, ldc, M, K, Ng, R, G, mode, gate, gate_rows, gate_ld, first_rows)) return e;
+    FG_CHECK_ARG(B >= 1 && B <= 65535, "%s: B must be in 1..65535 (got %d)", what, B);
+    FG_CHECK_ARG((int64_t)B * M < (1ll << 31), "%s: B * M must fit 31 bits (B=%d M=%lld)", what, B, (long long)M);
+    hipStream_t s = (hipStream_t)stream;
+    if (R == 32 && G == 3) return launch_lora_b<1, 3>(P, B, s);      // the instantiation fg_lora_apply_bf16 picks, per element
+    switch (R / 32) {
+        case 1: return launch_lora_b<1, 1>(P, B, s);
+        case 2: return launch_lora_b<2, 1>(P, B, s);
+        case 3: return launch_lora_b<3, 1>(P, B, s);
+        default: return launch_lora_b<4, 1>(P, B, s);
     }
 }
 

@@ -169,6 +169,18 @@ _ROWBATCH8_QUERIES = {
 }
 ROWBATCH8_SYMBOLS = sorted(list(_ROWBATCH8_SIGNATURES) + list(_ROWBATCH8_QUERIES))    # what include/fairygen_hip_rowbatch8.h declares
 
+# The extension of include/fairygen_hip_lorabatch.h (the same batches, what unfused hot-loaded adapters need: the adapter kernel and the
+# two-output modulate norm): an eighth pair.
+LORABATCH_ABI_VERSION = 1  # fg_dit_lorabatch_version
+_LORABATCH_SIGNATURES = {
+    "fg_lora_apply_bf16_b": [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp],
+    "fg_ln_modulate_dual_bf16_b": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _i64, _i64, _i64, _f32, _vp],
+}
+_LORABATCH_QUERIES = {
+    "fg_dit_lorabatch_version": (_i32, []),
+}
+LORABATCH_SYMBOLS = sorted(list(_LORABATCH_SIGNATURES) + list(_LORABATCH_QUERIES))    # what include/fairygen_hip_lorabatch.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -190,11 +202,11 @@ def load():
     lib = ctypes.CDLL(_LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
             list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()) + \
-            list(_ROWBATCH8_SIGNATURES.items()):
+            list(_ROWBATCH8_SIGNATURES.items()) + list(_LORABATCH_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
             list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()) + \
-            list(_ROWBATCH8_QUERIES.items()):
+            list(_ROWBATCH8_QUERIES.items()) + list(_LORABATCH_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
@@ -203,7 +215,8 @@ def load():
                                  ("fg_attn_cross8_version", CROSS8_ABI_VERSION, " (e4m3 cross-attention, K8 / V8^T in LDS)"),
                                  ("fg_attn_batch8_version", BATCH8_ABI_VERSION, " (e4m3 attention on batches)"),
                                  ("fg_dit_rowbatch_version", ROWBATCH_ABI_VERSION, " (row kernels on batches that share a table)"),
-                                 ("fg_dit_rowbatch8_version", ROWBATCH8_ABI_VERSION, " (fp8-output norms on batches that share a table)")):
+                                 ("fg_dit_rowbatch8_version", ROWBATCH8_ABI_VERSION, " (fp8-output norms on batches that share a table)"),
+                                 ("fg_dit_lorabatch_version", LORABATCH_ABI_VERSION, " (hot-loaded adapters on batches that share a table)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -418,12 +431,17 @@ def ln_modulate_fp8(x, mod, shift_idx, scale_idx, eps, batch=None):
     return q, sc
 
 
-def ln_modulate_dual(x, mod, shift_idx, scale_idx, eps, out=None):
+def ln_modulate_dual(x, mod, shift_idx, scale_idx, eps, out=None, batch=None):
     """ln_modulate for a norm that feeds an fp8 Linear AND a hot-loaded adapter: returns (out, (x_fp8, scale)) — the bf16 row of
-    ln_modulate and the pair of ln_modulate_fp8, bit for bit, in one pass over x."""
-    rows, c = _rows(x, "x")
+    ln_modulate and the pair of ln_modulate_fp8, bit for bit, in one pass over x.  batch: as ln_modulate's (fg_ln_modulate_dual_bf16_b,
+    include/fairygen_hip_lorabatch.h); the pair is that of all the rows of x."""
+    b, rows, c = _batch_rows("ln_modulate_dual", x, batch)
     out = torch.empty_like(x) if out is None else _dev(out, "out")
     q, sc = _fp8_rows_out(x)
+    if b > 1:
+        _call("fg_ln_modulate_dual_bf16_b", _ptr(x), mod.vec(shift_idx), mod.vec(scale_idx), _ptr(out), _ptr(q), _ptr(sc), b, rows, c, eps,
+              *_mod_args(mod, rows), FP8_E4M3FN_MAX, _stream(x))
+        return out, (q, sc)
     _call("fg_ln_modulate_dual_bf16", _ptr(x), mod.vec(shift_idx), mod.vec(scale_idx), _ptr(out), _ptr(q), _ptr(sc), rows, c, eps,
           *_mod_args(mod, rows), FP8_E4M3FN_MAX, _stream(x))
     return out, (q, sc)
@@ -686,20 +704,51 @@ LORA_RANK_TILE, LORA_MAX_RANK, LORA_MAX_GROUPS = 32, 128, 4      # fg_lora_apply
 _LORA_MODES = {"write": 0, "add": 1, "gate": 2, "gelu_tanh": 4}
 
 
-def lora_apply(x, a, b, out, groups=1, mode="add", mod=None, gate_idx=None):
+def _rows2d_b(t, who, batch):
+    """(2-D view, rows of one element) of a lora_apply operand on a batch of `batch` elements: (B, rows, C) — or its (B * rows, C) view —
+    with a dense last dim and ONE row stride across the elements, so that it is the B * rows rows of one strided matrix: a contiguous
+    tensor, or a column slice of one.  `who` prefixes the error."""
+    if not isinstance(t, torch.Tensor) or t.dim() < 2 or t.stride(-1) != 1:
+        raise HipLibraryError(f"{who}: expected (B, rows, C) with a dense last dim")
+    if t.is_contiguous():
+        t2 = t.reshape(-1, t.shape[-1])
+    elif t.dim() == 2:
+        t2 = t
+    elif t.dim() == 3 and (t.shape[0] == 1 or t.shape[1] == 1 or t.stride(0) == t.shape[1] * t.stride(1)):
+        # the stride of a dimension of size 1 says nothing: one row per element, the elements ARE the rows
+        t2 = t.as_strided((t.shape[0] * t.shape[1], t.shape[2]), (t.stride(1) if t.shape[1] > 1 else t.stride(0), 1))
+    else:
+        raise HipLibraryError(f"{who}: batch={batch} needs the elements at one row stride — the B * rows rows of one strided matrix "
+                              f"(shape {tuple(t.shape)}, strides {tuple(t.stride())})")
+    if t2.shape[0] % batch:
+        raise HipLibraryError(f"{who}: batch={batch} does not divide the {t2.shape[0]} rows")
+    return t2, t2.shape[0] // batch
+
+
+def lora_apply(x, a, b, out, groups=1, mode="add", mod=None, gate_idx=None, batch=None):
     """Hot-loaded LoRA adapters of one Linear (AutoWrappedLinear.lora_forward, core/vram/layers.py:417-436) on fg_lora_apply_bf16, in place
     on `out`: with l_g = bf16(bf16(x @ a_g^T) @ b_g^T) for each of the `groups` column groups of `out` (3: q | k | v of the fused
     projection), mode "write": out_g = l_g; "add": out_g += l_g; "gate": out_g += gate * l_g (gate = vector gate_idx of `mod`, as
     gemm_epilogue's residual form); "gelu_tanh": out_g = gelu_tanh(out_g + l_g).  x (..., K) with a dense last dim (2-D / (1, rows, K)
     when strided), out likewise with groups * Ng columns; a: (groups * R, K) the stacked alpha * A, b: (groups * Ng, R) the stacked B,
-    R a multiple of 32 up to 128 (WanModel pads with zeros)."""
+    R a multiple of 32 up to 128 (WanModel pads with zeros).
+    batch=B > 1: x and out are (B, rows, .) — B elements that share a, b and `mod`, whose first_rows counts inside the element — each
+    with a dense last dim and one row stride across the elements (a contiguous tensor or a column slice of one; anything else raises);
+    every mode goes to fg_lora_apply_bf16_b (include/fairygen_hip_lorabatch.h): per element the bytes of the call on that element alone.
+    batch None / 1: the call as it has always been."""
+    nb = 1 if batch is None else int(batch)
+    if nb < 1:
+        raise HipLibraryError(f"lora_apply: batch={batch}")
+    if nb > 1:      # the layout first: what the batch means is decided before anything else is looked at
+        (x2, rows_e), (o2, rows_o) = _rows2d_b(x, "lora_apply x", nb), _rows2d_b(out, "lora_apply out", nb)
     _dev(x, "x"), _dev(a, "a"), _dev(b, "b"), _dev(out, "out")
     if mode not in _LORA_MODES:
         raise HipLibraryError(f"lora_apply: mode must be one of {sorted(_LORA_MODES)}")
     k, n = x.shape[-1], out.shape[-1]
     if not a.is_contiguous() or not b.is_contiguous() or a.dim() != 2 or b.dim() != 2:
         raise HipLibraryError("lora_apply: a and b must be contiguous matrices")
-    x2, o2 = _rows2d(x, "lora_apply x"), _rows2d(out, "lora_apply out")
+    if nb == 1:
+        x2, o2 = _rows2d(x, "lora_apply x"), _rows2d(out, "lora_apply out")
     if x2.shape[0] != o2.shape[0]:
         raise HipLibraryError("lora_apply: x and out must have the same rows")
     r = b.shape[1]
@@ -710,6 +759,10 @@ def lora_apply(x, a, b, out, groups=1, mode="add", mod=None, gate_idx=None):
         if mod is None or mod.mod_rows not in (1, 2) or mod.c != n or mod.per_token:
             raise HipLibraryError("lora_apply: mode 'gate' needs a ModTable of 1 or 2 rows of N values (no per-token table)")
         gate, gate_rows, gate_ld, first = mod.vec(gate_idx), mod.mod_rows, mod.ld, mod.first_rows
+    if nb > 1:
+        _call("fg_lora_apply_bf16_b", _ptr(x2), x2.stride(0), _ptr(a), _ptr(b), _ptr(o2), o2.stride(0), nb, rows_e, k, n // groups, r, groups,
+              _LORA_MODES[mode], gate, gate_rows, gate_ld, first, _stream(x))
+        return out
     _call("fg_lora_apply_bf16", _ptr(x2), x2.stride(0), _ptr(a), _ptr(b), _ptr(o2), o2.stride(0), x2.shape[0], k, n // groups, r, groups,
           _LORA_MODES[mode], gate, gate_rows, gate_ld, first, _stream(x))
     return out

@@ -129,7 +129,9 @@ def stack_hot_loras(per_group, shapes, device, dtype):
 class Act(NamedTuple):
     """What a norm hands to the Linears behind it: the bf16 row, its (e4m3 rows, row scales) pair, or both — _BlockLinears decides which
     once per forward.  An fp8 Linear that gets the bf16 row only quantises it itself (fg_fp8_quant_rows_bf16).  nb: the elements of a
-    stacked forward (WanModel.enable_stacked_cfg) behind a pair without a bf16 row — the pair is (nb * rows, C), one GEMM operand."""
+    stacked forward (WanModel.enable_stacked_cfg) behind a pair without a bf16 row — the pair is (nb * rows, C), one GEMM operand.  With
+    both fields on a stacked activation (unfused adapters in the fp8 mode) the bf16 row is (B, rows, C) and says the batch; the pair is
+    still that of all B * rows rows."""
     bf16: Optional[torch.Tensor] = None
     q8: Optional[tuple] = None
     nb: int = 1
@@ -174,8 +176,8 @@ class _BlockLinears:
 
     # ---- the norms: modulate(LN(x)), LN(x) * w + b, each alone or behind x += gate * y, and the bare x += gate * y
     def modulate(self, x, mod, shift_idx, scale_idx, out=None):
-        if self.want_bf16 and self.want_q8:
-            return Act(*hip.ln_modulate_dual(x, mod, shift_idx, scale_idx, self.eps, out=out))
+        if self.want_bf16 and self.want_q8:      # a stacked forward: both fields of all rows, the bf16 one (B, rows, C)
+            return Act(*hip.ln_modulate_dual(x, mod, shift_idx, scale_idx, self.eps, out=out, batch=self.batch_of(x)))
         if self.want_q8:
             nb = self.batch_of(x)
             return Act(None, hip.ln_modulate_fp8(x, mod, shift_idx, scale_idx, self.eps, batch=nb), nb or 1)
@@ -184,12 +186,13 @@ class _BlockLinears:
     @staticmethod
     def batch_of(x):
         """batch= of the row kernels that read a table by the row inside the element: the leading dimension of a stacked forward
-        (WanModel.enable_stacked_cfg; the bf16 norms and the fp8-output ones get there, the two-output ones of unfused adapters do
-        not), None for the one element every other forward has."""
+        (WanModel.enable_stacked_cfg; the bf16 norms, the fp8-output ones and — enable_stacked_cfg(hot_lora=True) — the two-output one
+        of unfused adapters get there), None for the one element every other forward has."""
         return x.shape[0] if x.dim() == 3 and x.shape[0] > 1 else None
 
     def affine(self, x, norm):
-        """norm3 on its own has no fp8-only kernel: the bf16 row, which the fp8 Linear behind it quantises."""
+        """norm3 on its own has no fp8-only kernel: the bf16 row, which the fp8 Linear behind it quantises.  It reads no table by row
+        number, so a stacked activation is simply all its rows, in either form."""
         if self.want_bf16 and self.want_q8:
             return Act(*hip.ln_affine_dual(x, norm.weight, norm.bias, self.eps))
         return Act(hip.ln_affine(x, norm.weight, norm.bias, self.eps))
@@ -332,9 +335,10 @@ class _BlockLinears:
             y = m._scaled_linear(*self.q8(a), w8, bias, **stacked, **self.state(rows, n, k))
         else:
             y = gemm_bias_own(a.bf16, weight, bias, **self.state(rows, n, 2 * k)) if own else gemm_bias(a.bf16, weight, bias)
+        nb = a.batch if a.batch > 1 else None      # stacked: the adapter kernel takes the batch (include/fairygen_hip_lorabatch.h)
         if gelu and pack:      # GELU moves from the GEMM's store into the adapter kernel's
-            return hip.lora_apply(a.bf16, pack[0], pack[1], y, mode="gelu_tanh")
-        m._hot_apply(names, a.bf16, y, pack)
+            return hip.lora_apply(a.bf16, pack[0], pack[1], y, mode="gelu_tanh", batch=nb)
+        m._hot_apply(names, a.bf16, y, pack, batch=nb)
         return hip.activation(y, "gelu_tanh") if gelu and not self.gelu_in_quant else y
 
     def residual(self, x, a, name, weight, bias, w8, mod, gate_idx, affine=None, modulate=None, out=None, tuned=False, store_ok=True,
@@ -346,9 +350,11 @@ class _BlockLinears:
         and in fg_lora_apply_bf16, then the norm alone; or a plain GEMM, the adapters, and the fused residual + norm kernel.
         a: bf16; gelu: it is ffn.0's pre-activation (gelu_in_quant).  tuned / store_ok: ffn.2's library GEMM comes from the tuning table,
         and FAIRYGEN_GEMM=fused-ffn2 keeps it there.
-        A stacked forward (a: (B, rows, K), B > 1; no unfused adapters; fp8 Linears take the second form): the store picks its gate row by
+        A stacked forward (a: (B, rows, K), B > 1; fp8 Linears without adapters take the second form): the store picks its gate row by
         `row >= first_rows` over the rows of the launch, so with a two-row gate table it is launched once per element on the element's
-        rows — the batch-1 forward's launch, the batch-1 forward's bits; with one gate row or none, one launch takes all B * rows rows.
+        rows (fp8: and on the element's quantised rows) — the batch-1 forward's launch, the batch-1 forward's bits; with one gate row or
+        none, one launch takes all B * rows rows.  The adapters behind the stores are ONE fg_lora_apply_bf16_b launch either way: its
+        gate rule counts inside the element (enable_stacked_cfg(hot_lora=True)).
         The other form runs its GEMM on B * rows rows and the batched row kernels (include/fairygen_hip_rowbatch.h) do the gate."""
         m, fp8 = self.model, self.fp8
         n, k = weight.shape
@@ -358,15 +364,22 @@ class _BlockLinears:
         per_element = nb > 1 and gmod is not None and gmod.mod_rows == 2
         rows = a.shape[1] if per_element else nb * a.shape[1]      # of one store launch
         if self.own and store_ok and pack is not False and (own_gemm_ok(rows, n, k) if fp8 is None else fp8_own_ok(n, k)):
-            if per_element:
+            if fp8 is not None:      # the quantisation is per row: one pass over all rows, whichever way the store is launched
+                aq, asc = hip.fp8_quant_rows(a)
+            if per_element and fp8 is None:
                 for e in range(nb):
                     gemm_residual(x[e:e + 1], a[e:e + 1], weight, bias, gmod, gate_idx, **self.state(rows, n, 2 * k))
+            elif per_element:
+                for e in range(nb):
+                    hip.gemm_fp8(aq[e * rows:(e + 1) * rows], asc[e * rows:(e + 1) * rows], w8, bias, out=x[e:e + 1], residual=True, mod=gmod,
+                                 gate_idx=gate_idx, **self.state(rows, n, k))
             elif fp8 is None:
                 gemm_residual(x, a, weight, bias, gmod, gate_idx, **self.state(rows, n, 2 * k))
             else:
-                hip.gemm_fp8(*hip.fp8_quant_rows(a), w8, bias, out=x, residual=True, mod=gmod, gate_idx=gate_idx, **self.state(a.shape[1], n, k))
+                hip.gemm_fp8(aq, asc, w8, bias, out=x, residual=True, mod=gmod, gate_idx=gate_idx, **self.state(rows, n, k))
             if pack:
-                hip.lora_apply(a, pack[0], pack[1], x, mode="add" if gmod is None else "gate", mod=gmod, gate_idx=gate_idx)
+                hip.lora_apply(a, pack[0], pack[1], x, mode="add" if gmod is None else "gate", mod=gmod, gate_idx=gate_idx,
+                               batch=nb if nb > 1 else None)
             if affine is not None:
                 return x, self.affine(x, affine)
             return x, self.modulate(x, *modulate, out=out) if modulate is not None else None
@@ -377,7 +390,7 @@ class _BlockLinears:
             y = m._scaled_linear(*hip.fp8_quant_rows(a, "gelu_tanh" if gelu else None), w8, bias, **({"batch": nb} if nb > 1 else {}),
                                  **self.state(nb * a.shape[1], n, k))
         if pack is not None:      # only then is nn.GELU's bf16 output needed
-            m._hot_apply((name,), hip.activation(a.clone(), "gelu_tanh") if gelu else a, y, pack)
+            m._hot_apply((name,), hip.activation(a.clone(), "gelu_tanh") if gelu else a, y, pack, batch=nb if nb > 1 else None)
         if affine is not None:
             return self.residual_affine(x, y, mod, gate_idx, affine)
         if modulate is not None:
@@ -559,6 +572,8 @@ class WanModel(nn.Module):
         self.stacked_cfg = False
         # ... also when the blocks' Linears run in the fp8 mode (enable_stacked_cfg(fp8_linear=True)); False: that combination raises
         self.stacked_cfg_fp8 = False
+        # ... also with unfused adapters on hot_backend="hip" (enable_stacked_cfg(hot_lora=True)); False: that combination raises
+        self.stacked_cfg_hot_lora = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -644,7 +659,7 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ the stacked CFG forward
-    def enable_stacked_cfg(self, flag=True, fp8_linear=False):
+    def enable_stacked_cfg(self, flag=True, fp8_linear=False, hot_lora=False):
         """Opt-in, off by default: a merged CFG call (cfg_merge=True: the positive and the negative context batched, wan_video.py
         model_fn_wan_video_steps) runs ONE forward on the residual stream (2, N, dim) instead of two batch-1 forwards one after the other.
         The time rows, the modulation tables and the RoPE tables are one element's and shared; the row kernels that read them take the
@@ -658,20 +673,33 @@ class WanModel(nn.Module):
         include/fairygen_hip_rowbatch8.h and leave ONE (2 N, C) e4m3 operand with its 2 N row scales, every fp8 Linear is one GEMM on 2 N
         rows (the context's k | v on 2 L), the per-row quantisation in front of o and ffn.2 is one pass over 2 N rows, and the gates run
         on the batched row kernels — as in the batch-1 fp8 forward, none of them in a GEMM's store.  FAIRYGEN_FP8_FOLD=0 (bf16 norms, then
-        the quantisation pass) works stacked as well.  enable_stacked_cfg(False) clears both."""
+        the quantisation pass) works stacked as well.
+        hot_lora: off by default, and then a model with unfused hot-loaded adapters raises at the merged call.  True lets the stacked
+        forward run with adapters on hot_backend="hip" (hot_backend="torch" keeps raising): the adapter kernel and the two-output
+        modulate norm take the batch through include/fairygen_hip_lorabatch.h — one fg_lora_apply_bf16_b launch per adapted Linear, its
+        gate rule counted inside the element — and in the fp8 Linear mode (with fp8_linear=True) the gated store of fg_gemm_fp8_bf16 is
+        launched per element where the gate table has two rows (_BlockLinears.residual).  Linears whose shapes the kernel refuses take
+        the reference's torch ops, which are row-wise.  Like fp8_linear it is stated with every call: a call that does not restate it
+        clears it, and enable_stacked_cfg(False) clears all three."""
         self.stacked_cfg = bool(flag)
         self.stacked_cfg_fp8 = bool(flag) and bool(fp8_linear)
+        self.stacked_cfg_hot_lora = bool(flag) and bool(hot_lora)
         return self
 
     def check_stacked_cfg(self, context_batch, shard=None, sliding_window=False):
         """What a merged call must not meet while enable_stacked_cfg is on; decided on the host before anything is launched.  The fp8 Linear
-        mode passes only with enable_stacked_cfg(fp8_linear=True); everything else raises with it as without."""
+        mode passes only with enable_stacked_cfg(fp8_linear=True), unfused adapters only on hot_backend="hip" with
+        enable_stacked_cfg(hot_lora=True); everything else raises with them as without."""
         if self.fp8_dtype is not None and not self.stacked_cfg_fp8:
             raise NotImplementedError("stacked_cfg with enable_fp8_linear: the stacked forward takes the fp8 Linear mode only when it is asked "
                                       "to, enable_stacked_cfg(fp8_linear=True)")
-        if self.hot_loras:
+        if self.hot_loras and not self.stacked_cfg_hot_lora:
             raise NotImplementedError(f"stacked_cfg with hot-loaded adapters on hot_backend={self.hot_lora_backend!r}: fg_lora_apply_bf16's gate "
                                       "has no batched form; hot_backend='fused' adapters are plain weights and work")
+        if self.hot_loras and self.hot_lora_backend != "hip":
+            raise NotImplementedError(f"stacked_cfg(hot_lora=True) with hot-loaded adapters on hot_backend={self.hot_lora_backend!r}: the stacked "
+                                      "forward takes unfused adapters on hot_backend='hip' only (fg_lora_apply_bf16_b); hot_backend='fused' "
+                                      "adapters are plain weights and work")
         if shard is not None and shard.active:
             raise NotImplementedError("stacked_cfg with an active token shard: the stacked forward has no exchange")
         if sliding_window:
@@ -816,11 +844,12 @@ class WanModel(nn.Module):
             self._hot_packs[names] = pack
         return self._hot_packs[names]
 
-    def _hot_apply(self, names, x, out, pack):
+    def _hot_apply(self, names, x, out, pack, batch=None):
         """out += the adapters of the Linears `names` (column groups of out) applied to x.  pack: what _hot_pack(names) gave — one
-        fg_lora_apply_bf16 launch; False — _hot per Linear on its column slice; None — nothing to add."""
+        fg_lora_apply_bf16 launch (batch=B, a stacked forward: fg_lora_apply_bf16_b on x, out (B, rows, .)); False — _hot per Linear on
+        its column slice (row-wise torch ops, any leading shape); None — nothing to add."""
         if pack:
-            return hip.lora_apply(x, pack[0], pack[1], out, groups=len(names), mode="add")
+            return hip.lora_apply(x, pack[0], pack[1], out, groups=len(names), mode="add", batch=batch)
         if pack is False:
             c = out.shape[-1] // len(names)
             for j, nm in enumerate(names):

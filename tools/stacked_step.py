@@ -9,6 +9,9 @@ switch off: the merged call evaluated element by element — the same launches a
 WanModel.enable_stacked_cfg(): one forward on (2, N, dim)).  Sizes: "n8190" (latent (1,48,13,42,60)) and "headline" (704x1280x121, latent
 (1,48,31,44,80), N = 27 280).  Full width, 30 blocks, synthetic weights, TI2V with CFG 5, kv_cache on — the loop the pipeline runs.
 --linear fp8: the blocks' Linears in the fp8 mode in all three legs, the stacked leg with enable_stacked_cfg(fp8_linear=True).
+--hot-lora hip: rank-32 adapters on self_attn.q / k / v / o, ffn.0 and ffn.2 of every block, unfused on hot_backend="hip" in the three legs
+(the stacked one with enable_stacked_cfg(hot_lora=True): fg_lora_apply_bf16_b), and a fourth leg "stacked-fused": the stacked forward with
+the same adapters on hot_backend="fused" (folded into the weights before the leg, outside the timed steps) — the price of not fusing.
 
 A round runs every leg once, in order; `--rounds` rounds follow each other, so a leg's samples are spread over the run and drift hits all
 legs alike.  A leg is ONE denoise call of `1 + --warmup + --steps` steps; step 0 (tables, kv_cache) and the warm-up steps are not timed,
@@ -32,6 +35,20 @@ from fairygen_amd.wan_video_dit import WanModel  # noqa: E402
 
 SIZES = {"n8190": (1, 48, 13, 42, 60), "headline": (1, 48, 31, 44, 80)}
 LEGS = ("two-call", "merged", "stacked")
+HOT_LEGS = LEGS + ("stacked-fused",)
+HOT_TARGETS = ("self_attn.q", "self_attn.k", "self_attn.v", "self_attn.o", "ffn.0", "ffn.2")
+
+
+def hot_adapters(dit, rank, dev):
+    """[(name, A (rank, in), B (out, rank))] for HOT_TARGETS of every block, x A^T B^T of O(0.1)."""
+    g = torch.Generator("cpu").manual_seed(4321)
+    out = []
+    for i in range(len(dit.blocks)):
+        for nm in HOT_TARGETS:
+            n, k = dit.get_submodule(f"blocks.{i}.{nm}").weight.shape
+            out.append((f"blocks.{i}.{nm}", (torch.randn((rank, k), generator=g) * k ** -0.5).to(torch.bfloat16).to(dev),
+                        (torch.randn((n, rank), generator=g) * 0.1 * rank ** -0.5).to(torch.bfloat16).to(dev)))
+    return out
 
 
 def build(layers, dev):
@@ -67,7 +84,14 @@ class Timed:
         return [a.elapsed_time(b) for a, b in zip(self.events, self.events[1:])]
 
 
-def leg(pipe, shape, mode, warmup, steps, dev, fp8=False):
+def leg(pipe, shape, mode, warmup, steps, dev, fp8=False, adapters=None):
+    fused = mode == "stacked-fused"
+    if adapters is not None:
+        pipe.dit.clear_hot_loras()
+        pipe.dit.hot_lora_backend = "fused" if fused else "hip"
+        for name, a, b in adapters:
+            pipe.dit.add_hot_lora(name, a, b)
+        mode = "stacked" if fused else mode
     g = torch.Generator("cpu").manual_seed(0)
     rnd = lambda *s: torch.randn(s, generator=g).to(torch.bfloat16).to(dev)      # noqa: E731
     lat, ctx_p, ctx_n, z0 = rnd(*shape), rnd(1, 512, 4096), rnd(1, 512, 4096), rnd(*shape[:2], 1, *shape[3:])
@@ -78,7 +102,7 @@ def leg(pipe, shape, mode, warmup, steps, dev, fp8=False):
     if mode != "two-call":      # what WanVideoUnit_CfgMerger leaves: the contexts batched in the shared inputs
         shared.update(cfg_merge=True, context=torch.cat([ctx_p, ctx_n], 0))
         posi, nega = {}, {}
-    pipe.dit.enable_stacked_cfg(mode == "stacked", fp8_linear=fp8)
+    pipe.dit.enable_stacked_cfg(mode == "stacked", fp8_linear=fp8, hot_lora=adapters is not None and not fused)
     bar = Timed(1 + warmup)
     try:
         with torch.no_grad():
@@ -86,6 +110,8 @@ def leg(pipe, shape, mode, warmup, steps, dev, fp8=False):
         torch.cuda.synchronize()
     finally:
         pipe.dit.enable_stacked_cfg(False)
+        if adapters is not None:
+            pipe.dit.clear_hot_loras()
     return bar.step_ms(), out.clone()
 
 
@@ -93,7 +119,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="n8190,headline")
     ap.add_argument("--attn", default="bf16,e4m3", help="bf16, and e4m3 = enable_qk8_attention(pv8=True, cross=True, fused_producer=True)")
-    ap.add_argument("--legs", default=",".join(LEGS))
+    ap.add_argument("--legs", default=None, help="default: %s; with --hot-lora: %s" % (",".join(LEGS), ",".join(HOT_LEGS)))
+    ap.add_argument("--hot-lora", default=None, choices=("hip",), help="rank-32 unfused adapters on six Linears of every block (hot_backend='hip')")
+    ap.add_argument("--rank", type=int, default=32)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4)
@@ -106,6 +134,8 @@ def main():
     fp8 = a.linear == "fp8"
     if fp8:
         pipe.dit.enable_fp8_linear()
+    adapters = hot_adapters(pipe.dit, a.rank, dev) if a.hot_lora else None
+    a.legs = a.legs or ",".join(HOT_LEGS if adapters else LEGS)
     rows = []
     for size in a.sizes.split(","):
         n = SIZES[size][2] * (SIZES[size][3] // 2) * (SIZES[size][4] // 2)
@@ -115,7 +145,7 @@ def main():
             samples, outs = {m: [] for m in a.legs.split(",")}, {}
             for _ in range(a.rounds):
                 for mode in samples:
-                    ms, out = leg(pipe, SIZES[size], mode, a.warmup, a.steps, dev, fp8)
+                    ms, out = leg(pipe, SIZES[size], mode, a.warmup, a.steps, dev, fp8, adapters)
                     samples[mode] += ms
                     outs[mode] = out
             ref = outs.get("two-call")
@@ -130,7 +160,7 @@ def main():
             del outs, ref
             gc.collect()
             torch.cuda.empty_cache()
-    print(json.dumps({"tool": "stacked_step", **({"linear": "fp8"} if fp8 else {}), "layers": a.layers or 30, "rounds": a.rounds, "warmup": a.warmup, "steps": a.steps,
+    print(json.dumps({"tool": "stacked_step", **({"linear": "fp8"} if fp8 else {}), **({"hot_lora": a.hot_lora, "rank": a.rank} if adapters else {}), "layers": a.layers or 30, "rounds": a.rounds, "warmup": a.warmup, "steps": a.steps,
                       "device": torch.cuda.get_device_name(0), "legs": rows}))
 
 
