@@ -181,6 +181,18 @@ _LORABATCH_QUERIES = {
 }
 LORABATCH_SYMBOLS = sorted(list(_LORABATCH_SIGNATURES) + list(_LORABATCH_QUERIES))    # what include/fairygen_hip_lorabatch.h declares
 
+# The extension of include/fairygen_hip_up2phase.h (the VAE decoder's nearest-2x upsample + 3x3 conv as four 2x2 phase convs): a ninth pair.
+UP2PHASE_ABI_VERSION = 1  # fg_conv_up2phase_version
+_UP2PHASE_SIGNATURES = {
+    "fg_conv_up2phase_pack_bf16": [_vp, _vp, _i32, _i32, _vp],
+    "fg_conv3d_up2_phase_bf16": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+}
+_UP2PHASE_QUERIES = {
+    "fg_conv_up2phase_version": (_i32, []),
+    "fg_conv_up2phase_packed_bytes": (_i64, [_i32] * 2),
+}
+UP2PHASE_SYMBOLS = sorted(list(_UP2PHASE_SIGNATURES) + list(_UP2PHASE_QUERIES))    # what include/fairygen_hip_up2phase.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -202,11 +214,11 @@ def load():
     lib = ctypes.CDLL(_LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
             list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()) + \
-            list(_ROWBATCH8_SIGNATURES.items()) + list(_LORABATCH_SIGNATURES.items()):
+            list(_ROWBATCH8_SIGNATURES.items()) + list(_LORABATCH_SIGNATURES.items()) + list(_UP2PHASE_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
             list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()) + \
-            list(_ROWBATCH8_QUERIES.items()) + list(_LORABATCH_QUERIES.items()):
+            list(_ROWBATCH8_QUERIES.items()) + list(_LORABATCH_QUERIES.items()) + list(_UP2PHASE_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
@@ -216,7 +228,8 @@ def load():
                                  ("fg_attn_batch8_version", BATCH8_ABI_VERSION, " (e4m3 attention on batches)"),
                                  ("fg_dit_rowbatch_version", ROWBATCH_ABI_VERSION, " (row kernels on batches that share a table)"),
                                  ("fg_dit_rowbatch8_version", ROWBATCH8_ABI_VERSION, " (fp8-output norms on batches that share a table)"),
-                                 ("fg_dit_lorabatch_version", LORABATCH_ABI_VERSION, " (hot-loaded adapters on batches that share a table)")):
+                                 ("fg_dit_lorabatch_version", LORABATCH_ABI_VERSION, " (hot-loaded adapters on batches that share a table)"),
+                                 ("fg_conv_up2phase_version", UP2PHASE_ABI_VERSION, " (upsample conv as four 2x2 phase convs)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -1311,6 +1324,51 @@ def conv3d_cl(x, w_packed, bias, cout, kt, ks, residual=None, upsample2x=False, 
     _call("fg_conv3d_cl_bf16", _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(residual), _ptr(out), t, h, w,
           cin, cout, kt, ks, 1 if upsample2x else (2 if downsample2x else 0), int(time_interleave), _stream(x))
     return out
+
+
+def conv_up2_phase_ok(cin, kt, ks):
+    """Whether the nearest-2x upsample conv of these sizes has the phase form (include/fairygen_hip_up2phase.h): the 1x3x3 conv, Cin % 64 == 0."""
+    return kt == 1 and ks == 3 and cin % 64 == 0
+
+
+def conv_up2_phase_pack_weight(w):
+    """(Cout,Cin,1,3,3) or (Cout,Cin,3,3) bf16 -> the 16 summed tap matrices (4 phases x 2x2 taps) for conv3d_up2_phase."""
+    _dev(w, "w")
+    w = w.contiguous()
+    if w.dim() == 5:
+        assert w.shape[2] == 1
+        w = w.squeeze(2)
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    nbytes = load().fg_conv_up2phase_packed_bytes(cout, cin)
+    if nbytes <= 0:
+        raise HipLibraryError(f"conv_up2_phase_pack_weight: no phase form for Cout={cout} Cin={cin}")
+    packed = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=w.device)
+    _call("fg_conv_up2phase_pack_bf16", _ptr(w), _ptr(packed), cout, cin, _stream(w))
+    return packed
+
+
+def conv3d_up2_phase(x, w_phase, bias, cout, kt=1, ks=3, out=None):
+    """x (T, Hin, Win, Cin) channels-last -> (T, 2 Hin, 2 Win, Cout): conv3d_cl(upsample2x=True) as four 2x2 convs over x, one per
+    output phase, on conv_up2_phase_pack_weight's weights."""
+    _dev(x, "x"), _dev(w_phase, "w_phase"), _dev(bias, "bias")
+    assert x.dim() == 4 and x.is_contiguous()
+    t, hin, win, cin = x.shape
+    oshape = (t, 2 * hin, 2 * win, cout)
+    out = torch.empty(oshape, dtype=x.dtype, device=x.device) if out is None else out
+    assert tuple(out.shape) == oshape and out.is_contiguous()
+    if w_phase.numel() * 2 != load().fg_conv_up2phase_packed_bytes(cout, cin):
+        raise HipLibraryError(f"conv3d_up2_phase: w_phase is not the phase-packed weight of a ({cout}, {cin}, 1, 3, 3) conv")
+    _call("fg_conv3d_up2_phase_bf16", _ptr(x), _ptr(w_phase), _ptr(bias), _ptr(out), t, 2 * hin, 2 * win, cin, cout, kt, ks, _stream(x))
+    return out
+
+
+def conv3d_up2(x, w_packed, w_phase, bias, cout, kt, ks, out=None):
+    """The nearest-2x upsample + conv of Resample38: the phase form where the shape has one (conv_up2_phase_ok) and w_phase is given,
+    conv3d_cl(upsample2x=True) on w_packed otherwise."""
+    if w_phase is not None and conv_up2_phase_ok(x.shape[-1], kt, ks):
+        return conv3d_up2_phase(x, w_phase, bias, cout, out=out)
+    return conv3d_cl(x, w_packed, bias, cout, kt, ks, upsample2x=True, out=out)
 
 
 def dupup3d_add(x, main, cout, ft, fs, first_chunk, out=None):

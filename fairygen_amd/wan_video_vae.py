@@ -156,16 +156,23 @@ class _ConvState:
     ring[0:2] = the feature cache (the previous two input frames, zeros at the start), ring[2:2+T] = the chunk's
     input, written in place by the producer kernel, so the conv reads one contiguous (T+2,H,W,C) tensor."""
 
-    __slots__ = ("packed", "bias", "cout", "cin", "kt", "ks", "ring")
+    __slots__ = ("packed", "packed_up2", "bias", "cout", "cin", "kt", "ks", "ring")
 
     def __init__(self, conv):
         w = conv.weight
         self.packed = hip.conv_pack_weight(w)
+        self.packed_up2 = None      # the upsample convs' summed phase weights (pack_up2)
         self.bias = conv.bias.contiguous()
         self.cout, self.cin = w.shape[0], w.shape[1]
         self.kt = w.shape[2] if w.dim() == 5 else 1
         self.ks = w.shape[-1]
         self.ring = None
+
+    def pack_up2(self, conv):
+        """The conv behind a nearest-2x upsample: also its 16 summed tap matrices (4 output phases x 2x2 taps), where the shape has the
+        phase form."""
+        if hip.conv_up2_phase_ok(self.cin, self.kt, self.ks):
+            self.packed_up2 = hip.conv_up2_phase_pack_weight(conv.weight)
 
     def slot(self, t, h, w, dtype, device):
         """View (t,h,w,cin) of the ring where the producer writes this chunk's input."""
@@ -226,6 +233,9 @@ class VideoVAE38_(nn.Module):
                 if mod.weight.shape[-1] == 1 and mod.weight.dim() == 4:
                     continue        # 1x1 Conv2d of the AttentionBlock: plain GEMMs (F.linear)
                 self._conv_states[id(mod)] = _ConvState(mod)
+            if not encoder:
+                for rs in (m for m in root.modules() if isinstance(m, Resample38) and m.mode in ("upsample2d", "upsample3d")):
+                    self._conv_states[id(rs.resample[1])].pack_up2(rs.resample[1])
         return self._conv_states
 
     # ------------------------------------------------------------------ building blocks (channels-last)
@@ -273,7 +283,8 @@ class VideoVAE38_(nn.Module):
         if rs.mode == "upsample3d" and not first_chunk:      # first chunk: 'Rep', no temporal doubling (:125-127)
             self._slot(rs.time_conv, x).copy_(x)
             x = self._cconv(rs.time_conv, x.shape[0], time_interleave=True)
-        return self._conv(rs.resample[1], x, upsample2x=True)
+        st = self._states()[id(rs.resample[1])]      # four 2x2 phase convs over x where the shape has that form, else the 9-tap upsample conv
+        return hip.conv3d_up2(x, st.packed, st.packed_up2, st.bias, st.cout, st.kt, st.ks)
 
     def _decoder_chunk(self, x, first_chunk):
         dec = self.decoder

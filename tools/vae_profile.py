@@ -42,6 +42,8 @@ def main():
 
     wrap("conv3d_cl", lambda x, wp, b, cout, kt, ks, **kw: (tuple(x.shape), cout, kt, ks,
                                                           "up" if kw.get("upsample2x") else "", "interleave" if kw.get("time_interleave") else ""))
+    # the upsample convs in the four-phase form ('up4'); their FLOPs below are counted as the 9-tap conv's, so TF/s compares with 'up'
+    wrap("conv3d_up2_phase", lambda x, wp, b, cout, kt=1, ks=3, **kw: (tuple(x.shape), cout, kt, ks, "up4", ""))
     wrap("vae_rmsnorm_silu", lambda x, g, silu=True, out=None: (tuple(x.shape),))
     wrap("dupup3d_add", lambda x, main, *r, **kw: (tuple(x.shape), tuple(main.shape)))
     wrap("vae_unpatchify", lambda x, *r, **kw: (tuple(x.shape),))
@@ -61,7 +63,7 @@ def main():
     for name, shape, s, e in records:
         ms = s.elapsed_time(e)
         fl = 0.0
-        if name == "conv3d_cl":
+        if name in ("conv3d_cl", "conv3d_up2_phase"):
             (t, h, w, cin), cout, kt, ks = shape[0], shape[1], shape[2], shape[3]
             t_out = t - (kt - 1)
             up = 2 if shape[4] else 1
