@@ -19,10 +19,12 @@ NEGATIVE = ("è‰²è°ƒè‰³ä¸½ï¼Œè¿‡æ›ï¼Œé™æ€ï¼Œç»†èŠ‚æ¨¡ç³Šä¸æ¸…ï¼Œå­—å¹•ï¼Œé£æ
             "ç”»å¾—ä¸å¥½çš„æ‰‹éƒ¨ï¼Œç”»å¾—ä¸å¥½çš„è„¸éƒ¨ï¼Œç•¸å½¢çš„ï¼Œæ¯å®¹çš„ï¼Œå½¢æ€ç•¸å½¢çš„è‚¢ä½“ï¼Œæ‰‹æŒ‡èåˆï¼Œé™æ­¢ä¸åŠ¨çš„ç”»é¢ï¼Œæ‚ä¹±çš„èƒŒæ™¯ï¼Œä¸‰æ¡è…¿ï¼ŒèƒŒæ™¯äººå¾ˆå¤šï¼Œå€’ç€èµ°")
 
 
-def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False, cross8=False, stacked_cfg=False):
+def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False, cross8=False, stacked_cfg=False, periodic_gate=False):
     dit_cfg = dict(computation_dtype=torch.float8_e4m3fn) if fp8 else {}
     if stacked_cfg:
         dit_cfg["stacked_cfg"] = True
+    if periodic_gate:
+        dit_cfg["stacked_cfg_periodic_gate"] = True
     if qk8 or pv8:
         dit_cfg["attention_dtype"] = torch.float8_e4m3fn
     if pv8:
@@ -65,9 +67,15 @@ def main():
                     help="both CFG branches in ONE stacked forward of the DiT per step (implies cfg_merge=True); single GPU, bf16 Linears or, "
                          "with --fp8, the fp8 Linear mode (the loader then calls enable_stacked_cfg(fp8_linear=True)); --lora here is fused into the weights and works; unfused hot-loaded "
                          "adapters need hot_backend='hip' and ModelConfig(stacked_cfg_hot_lora=True)")
+    ap.add_argument("--stacked-cfg-periodic-gate", action="store_true",
+                    help="with --stacked-cfg: the gated Linears of a block (self_attn.o, ffn.2) as ONE GEMM launch on the rows of both CFG "
+                         "branches instead of one per branch (ModelConfig(stacked_cfg_periodic_gate=True))")
     a = ap.parse_args()
+    if a.stacked_cfg_periodic_gate and not a.stacked_cfg:
+        ap.error("--stacked-cfg-periodic-gate is a form of --stacked-cfg")
     pv8 = a.pv8_attention or a.cross8_attention
-    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or pv8, pv8, a.cross8_attention, a.stacked_cfg)
+    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or pv8, pv8, a.cross8_attention, a.stacked_cfg,
+                          a.stacked_cfg_periodic_gate)
     image = Image.open(a.image).convert("RGB").resize((832, 480))
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     video = pipe(prompt=a.prompt, negative_prompt=NEGATIVE, input_image=image, num_frames=81, seed=1, tiled=True, cfg_merge=a.stacked_cfg)

@@ -64,6 +64,14 @@ V_T = 224          # setup temporaries v224..230
 V_REC = 144        # v144, v146..161: tile record loads (outside the epilogue)
 V_SC = 252         # fp8 form only: v252..255 = the activation row scales of the lane's four 32-row blocks (loaded when the tile starts)
 FP8 = False        # --dtype fp8: e4m3 operands (one byte per element, 128 k per LDS row), v_mfma_f32_32x32x64_f8f6f4, row-scale epilogue
+# --gate-period: the FLAGS 2 store picks its gate row by the row's place inside a batch element of PERIOD rows (class 0 iff row % PERIOD <
+# FIRST) instead of by the row of the launch.  The launcher asks PERIOD >= 256 (or >= M), so a tile meets at most one element boundary:
+# the element offset of a tile's first row (S_E0 = m0 % PERIOD, from the launch's reciprocal and one correction, emit_load_record_b) plus
+# the row inside the tile wraps at most once.  A second instantiation (fg_gemm_*_sp, include/fairygen_hip_gategemm.h); the bodies without
+# the flag are what they were, instruction for instruction.
+GATEP = False
+K_PERIOD = 224     # PERIOD, ceil(2^32 / PERIOD): behind GemmPParams in the kernel arguments (struct GemmGateP in dit_gemm.hip)
+S_E0 = SB + 63     # s99, the last SGPR the compiler leaves alone; PERIOD itself is re-read for the epilogue, into UNIT (dead there)
 
 
 def configure_fp8():
@@ -457,7 +465,17 @@ def emit_load_record_b(E):
     E.e(f"s_mov_b32 {sr(S['M0ROW'])}, {sr(S['REC'] + 11)}")            # m0 of the tile (token class of a row: m0 + row < FIRST)
     E.e(f"s_mov_b32 {sr(S['KIND'])}, {sr(S['REC'] + 10)}")
     E.e(f"s_load_dwordx2 {sr(S['GD'], 2)}, {sr(S['KARG'], 2)}, {K_GATE}")
+    if GATEP:
+        E.e(f"s_load_dwordx2 {sr(S['TMP64'], 2)}, {sr(S['KARG'], 2)}, {K_PERIOD}")
     E.e("s_waitcnt lgkmcnt(0)")
+    if GATEP:      # S_E0 = m0 % PERIOD.  q' = mulhi(m0, ceil(2^32 / PERIOD)) is q or q + 1 for m0, PERIOD < 2^31 (the excess of the
+        # reciprocal times m0 is below PERIOD * 2^31): one correction, no division
+        E.e(f"s_mul_hi_u32 {sr(S['TMP0'])}, {sr(S['M0ROW'])}, {sr(S['TMP64'] + 1)}")
+        E.e(f"s_mul_i32 {sr(S['TMP0'])}, {sr(S['TMP0'])}, {sr(S['TMP64'])}")
+        E.e(f"s_sub_u32 {sr(S_E0)}, {sr(S['M0ROW'])}, {sr(S['TMP0'])}")
+        E.e(f"s_add_u32 {sr(S['TMP0'])}, {sr(S_E0)}, {sr(S['TMP64'])}")
+        E.e(f"s_cmp_lt_i32 {sr(S_E0)}, 0")
+        E.e(f"s_cselect_b32 {sr(S_E0)}, {sr(S['TMP0'])}, {sr(S_E0)}")
     E.e(f"s_add_u32 {sr(S['GD'])}, {sr(S['GD'])}, {sr(S['REC'] + 12)}")     # gate vector at the tile's first column
     E.e(f"s_addc_u32 {sr(S['GD'] + 1)}, {sr(S['GD'] + 1)}, 0")
 
@@ -769,6 +787,10 @@ def emit_epilogue(E, C, n_dma):
     for gated in (True, False):
         if not gated:
             E.e(f"{resid}:")
+        elif GATEP:      # T = place inside its element of the store group's first row (before the wrap): S_E0 + 32mi + 4it; PERIOD -> UNIT
+            # (the next unit's record is made; the lgkmcnt(0) in front of the first store group waits for the load)
+            E.e(f"s_load_dword {sr(S['UNIT'])}, {sr(S['KARG'], 2)}, {K_PERIOD}")
+            E.e(f"s_mov_b32 {sr(S['T'])}, {sr(S_E0)}")
         else:      # class threshold of the row-major rows: row (of the tile, without 32mi + 4it) >= FIRST - m0 - 32mi - 4it -> class 1
             E.e(f"s_sub_i32 {sr(S['T'])}, {sr(S['FIRST'])}, {sr(S['M0ROW'])}")
         write_block(0)
@@ -782,10 +804,18 @@ def emit_epilogue(E, C, n_dma):
             E.e("s_waitcnt lgkmcnt(0)")
             E.e(f"s_waitcnt vmcnt({(8 if mi >= 1 else 0) + (8 if mi < 3 else 0)})")
             for it in range(8):
-                if gated:
+                if gated and GATEP:      # p = T + row < 2 PERIOD; min_u32(p, p - PERIOD) is p % PERIOD (p < PERIOD: the difference wraps high)
+                    E.e(f"v_add_u32 {vr(TB)}, {sr(S['T'])}, {vr(V_RROW)}")
+                    E.e(f"v_subrev_u32 {vr(TB + 1)}, {sr(S['UNIT'])}, {vr(TB)}")
+                    E.e(f"v_min_u32 {vr(TB)}, {vr(TB)}, {vr(TB + 1)}")
+                    E.e(f"v_cmp_le_u32 vcc, {sr(S['FIRST'])}, {vr(TB)}")
+                    E.e(f"s_add_u32 {sr(S['T'])}, {sr(S['T'])}, 4")
+                    E.e("s_nop 0")
+                elif gated:
                     E.e(f"v_cmp_le_i32 vcc, {sr(S['T'])}, {vr(V_RROW)}")
                     E.e(f"s_sub_i32 {sr(S['T'])}, {sr(S['T'])}, 4")
                     E.e("s_nop 0")
+                if gated:
                     for j in range(4):
                         E.e(f"v_cndmask_b32 {vr(GS + j)}, {vr(V_G0 + j)}, {vr(V_G1 + j)}, vcc")
                 for j in range(4):
@@ -849,8 +879,8 @@ def emit_program(E, C, stamp, budget, first, tail):
     the list is exhausted.  first: the body that starts the kernel; a later body re-derives every lane constant for its own tile width."""
     emit_setup(E, C, first)
     E.e(f"s_mov_b32 {sr(S['BD'] + 2)}, {C.nb * 2 * 32 * 2}")
-    if FP8:
-        assert not stamp, "the fp8 form keeps its scale base in the stamp counters' SGPRs"
+    if FP8 or GATEP:
+        assert not stamp, "the fp8 and gate-period forms keep scalars in the stamp counters' SGPRs"
     end = E.label("pend")
     tile_loop = E.label("ptile")
     nodma = E.label("pnodma")
@@ -980,16 +1010,22 @@ def main():
     ap.add_argument("--pf-coop", type=int, default=Cfg.pf_coop)
     ap.add_argument("--serp", type=int, default=Cfg.serp)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--gate-period", action="store_true", help="the FLAGS 2 store picks its gate row by row %% PERIOD (GATEP)")
     a = ap.parse_args()
     if a.dtype == "fp8":
         configure_fp8()
+    if a.gate_period:
+        globals().update(GATEP=True)
     Cfg.dma_step, Cfg.dma_first, Cfg.ablate, Cfg.pf_dist, Cfg.pf_coop = a.dma_step, a.dma_first, a.ablate, a.pf_dist, a.pf_coop
     Cfg.serp = a.serp
     E = generate(a.nb, a.stamp, a.budget, a.tail)
     # not used by the body and left to the compiler (it needs a VGPR for SGPR spills; the stamp build keeps values across the asm statement)
     free_v = (251,) if FP8 else (251, 252, 253, 254)
-    write_inc(E.lines, f"FG_GEMM_{'Q' if FP8 else 'P'}{a.nb}{a.tail or ''}", f"gen_gemm_p.py --nb {a.nb} --tail {a.tail} --dtype {a.dtype}",
-              [i for i in range(256) if i not in free_v], range(256), range(SB, SB + NSREG + (4 if a.stamp else 1 if FP8 else 0)))
+    gp = "G" if GATEP else ""
+    write_inc(E.lines, f"FG_GEMM_{'Q' if FP8 else 'P'}{gp}{a.nb}{a.tail or ''}",
+              f"gen_gemm_p.py --nb {a.nb} --tail {a.tail} --dtype {a.dtype}{' --gate-period' if GATEP else ''}",
+              [i for i in range(256) if i not in free_v], range(256),
+              range(SB, SB + NSREG + (2 if GATEP else 4 if a.stamp else 1 if FP8 else 0)))
 
 
 if __name__ == "__main__":

@@ -193,6 +193,19 @@ _UP2PHASE_QUERIES = {
 }
 UP2PHASE_SYMBOLS = sorted(list(_UP2PHASE_SIGNATURES) + list(_UP2PHASE_QUERIES))    # what include/fairygen_hip_up2phase.h declares
 
+# The extension of include/fairygen_hip_gategemm.h (the persistent GEMM's gated store with its row rule counted inside the elements of a
+# batch that shares a two-row gate table): a tenth pair.  The _s signatures with rows_per_element behind first_rows.
+GATEGEMM_ABI_VERSION = 1  # fg_gemm_gate_period_version
+_GATEGEMM_SIGNATURES = {
+    "fg_gemm_epilogue_bf16_sp": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp],
+    "fg_gemm_fp8_bf16_sp": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp],
+}
+_GATEGEMM_QUERIES = {
+    "fg_gemm_gate_period_version": (_i32, []),
+}
+GATEGEMM_SYMBOLS = sorted(list(_GATEGEMM_SIGNATURES) + list(_GATEGEMM_QUERIES))    # what include/fairygen_hip_gategemm.h declares
+GEMM_GATE_MIN_PERIOD = 256      # rows_per_element below the tile height is refused unless it covers all rows (one element)
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -214,11 +227,13 @@ def load():
     lib = ctypes.CDLL(_LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
             list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()) + \
-            list(_ROWBATCH8_SIGNATURES.items()) + list(_LORABATCH_SIGNATURES.items()) + list(_UP2PHASE_SIGNATURES.items()):
+            list(_ROWBATCH8_SIGNATURES.items()) + list(_LORABATCH_SIGNATURES.items()) + list(_UP2PHASE_SIGNATURES.items()) + \
+            list(_GATEGEMM_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
             list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()) + \
-            list(_ROWBATCH8_QUERIES.items()) + list(_LORABATCH_QUERIES.items()) + list(_UP2PHASE_QUERIES.items()):
+            list(_ROWBATCH8_QUERIES.items()) + list(_LORABATCH_QUERIES.items()) + list(_UP2PHASE_QUERIES.items()) + \
+            list(_GATEGEMM_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
@@ -229,7 +244,8 @@ def load():
                                  ("fg_dit_rowbatch_version", ROWBATCH_ABI_VERSION, " (row kernels on batches that share a table)"),
                                  ("fg_dit_rowbatch8_version", ROWBATCH8_ABI_VERSION, " (fp8-output norms on batches that share a table)"),
                                  ("fg_dit_lorabatch_version", LORABATCH_ABI_VERSION, " (hot-loaded adapters on batches that share a table)"),
-                                 ("fg_conv_up2phase_version", UP2PHASE_ABI_VERSION, " (upsample conv as four 2x2 phase convs)")):
+                                 ("fg_conv_up2phase_version", UP2PHASE_ABI_VERSION, " (upsample conv as four 2x2 phase convs)"),
+                                 ("fg_gemm_gate_period_version", GATEGEMM_ABI_VERSION, " (gated GEMM store on batches that share a gate table)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -664,14 +680,18 @@ def _gemm_mode(name, residual, mod, gate_idx, act, n):
     return (3 if residual else 4 if act else 0), None, 1, n, 0
 
 
-def gemm_epilogue(x, weight, bias, out=None, residual=False, mod=None, gate_idx=None, workspace=True, act=None, sched=None, workgroups=0):
+def gemm_epilogue(x, weight, bias, out=None, residual=False, mod=None, gate_idx=None, workspace=True, act=None, sched=None, workgroups=0,
+                  rows_per_element=None):
     """Linear on the persistent MFMA kernel.  residual=False: out = act(x @ weight^T + bias), act None or "gelu_tanh" (applied to the
     bf16-rounded Linear output and rounded again, like nn.Linear followed by nn.GELU).  residual=True: `out` holds the residual
     stream and becomes out + gate * (x @ weight^T + bias) (gate = vector gate_idx of `mod`, or 1 when mod is None), with the
     reference's rounding points (GateModule, models/wan_video_dit.py:188-193).  workspace=False: no k-split of the last round's tiles
     (every element one k-ordered accumulation, independent of the row count); a tensor: the caller's scratch.  sched: a caller-managed
     scheduler block (hip.gemm_state; default: the block kept for the current (device, stream)); workgroups: how many workgroups to launch
-    (0: one per CU) — same bits for every value.  The launch is fg_gemm_epilogue_bf16_s: nothing but stream-ordered work, capturable."""
+    (0: one per CU) — same bits for every value.  The launch is fg_gemm_epilogue_bf16_s: nothing but stream-ordered work, capturable.
+    rows_per_element=P (None: the call as it has always been, on that entry point): the rows are a batch of elements of P rows each that
+    share a two-row `mod`, whose first_rows counts inside the element — row r takes gate row 0 iff r % P < first_rows
+    (fg_gemm_epilogue_bf16_sp, include/fairygen_hip_gategemm.h: residual=True with a two-row table only, P >= 256 or >= the rows)."""
     _dev(x, "x"), _dev(weight, "weight"), _dev(bias, "bias")
     k = x.shape[-1]
     n = weight.shape[0]
@@ -683,17 +703,22 @@ def gemm_epilogue(x, weight, bias, out=None, residual=False, mod=None, gate_idx=
     mode, gate, gate_rows, gate_ld, first = _gemm_mode("gemm_epilogue", residual, mod, gate_idx, act, n)
     ws = _gemm_ws(x, m, n, 2 * k, workspace)
     block, key = _gemm_block("gemm_epilogue", x, sched)
+    if rows_per_element is not None:
+        _gemm_launch("fg_gemm_epilogue_bf16_sp", key, _ptr(x2), lda, _ptr(weight), _ptr(bias), _ptr(out), n, m, n, k, mode, gate, gate_rows, gate_ld,
+                     first, int(rows_per_element), _ptr(ws), _ptr(block), workgroups, _stream(x))
+        return out
     _gemm_launch("fg_gemm_epilogue_bf16_s", key, _ptr(x2), lda, _ptr(weight), _ptr(bias), _ptr(out), n, m, n, k, mode, gate, gate_rows, gate_ld, first,
                  _ptr(ws), _ptr(block), workgroups, _stream(x))
     return out
 
 
 def gemm_fp8(x_fp8, scale_a, weight_fp8, bias, out=None, residual=False, mod=None, gate_idx=None, workspace=True, act=None, lead_shape=None,
-             sched=None, workgroups=0):
+             sched=None, workgroups=0, rows_per_element=None):
     """torch._scaled_mm(x_fp8, weight_fp8.T, scale_a (rows, 1), ones (1, out), bias, out_dtype=bf16) of AutoWrappedLinear.fp8_linear
     (core/vram/layers.py:343-357) on the persistent kernel's e4m3 form, with the epilogues of gemm_epilogue.  x_fp8: (rows, K)
     float8_e4m3fn, scale_a: (rows, 1) fp32 (both from fp8_quant_rows / the fp8-output norm kernels), weight_fp8: (N, K) float8_e4m3fn.
-    Returns (*lead_shape, N) bf16 (default lead_shape: (rows,)).  workspace / sched / workgroups as gemm_epilogue (fg_gemm_fp8_bf16_s)."""
+    Returns (*lead_shape, N) bf16 (default lead_shape: (rows,)).  workspace / sched / workgroups as gemm_epilogue (fg_gemm_fp8_bf16_s);
+    rows_per_element as gemm_epilogue's (fg_gemm_fp8_bf16_sp)."""
     _dev(x_fp8, "x_fp8", torch.float8_e4m3fn), _dev(weight_fp8, "weight_fp8", torch.float8_e4m3fn), _dev(bias, "bias")
     _dev(scale_a, "scale_a", torch.float32)
     if x_fp8.dim() != 2 or x_fp8.stride(1) != 1 or not weight_fp8.is_contiguous() or weight_fp8.dim() != 2:
@@ -708,6 +733,10 @@ def gemm_fp8(x_fp8, scale_a, weight_fp8, bias, out=None, residual=False, mod=Non
     mode, gate, gate_rows, gate_ld, first = _gemm_mode("gemm_fp8", residual, mod, gate_idx, act, n)
     ws = _gemm_ws(x_fp8, m, n, k, workspace)
     block, key = _gemm_block("gemm_fp8", x_fp8, sched)
+    if rows_per_element is not None:
+        _gemm_launch("fg_gemm_fp8_bf16_sp", key, _ptr(x_fp8), x_fp8.stride(0), _ptr(scale_a), _ptr(weight_fp8), _ptr(bias), _ptr(out), n, m, n, k, mode,
+                     gate, gate_rows, gate_ld, first, int(rows_per_element), _ptr(ws), _ptr(block), workgroups, _stream(x_fp8))
+        return out
     _gemm_launch("fg_gemm_fp8_bf16_s", key, _ptr(x_fp8), x_fp8.stride(0), _ptr(scale_a), _ptr(weight_fp8), _ptr(bias), _ptr(out), n, m, n, k, mode, gate,
                  gate_rows, gate_ld, first, _ptr(ws), _ptr(block), workgroups, _stream(x_fp8))
     return out

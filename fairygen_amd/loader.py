@@ -45,11 +45,16 @@ class ModelConfig:
     # True (with stacked_cfg): that stacked forward also takes unfused hot-loaded adapters on hot_backend="hip"
     # (load_lora(..., hotload=True, hot_backend="hip"); enable_stacked_cfg(hot_lora=True))
     stacked_cfg_hot_lora: bool = False
+    # True (with stacked_cfg): the gated Linears of that stacked forward whose gate table has two rows (TI2V) run as ONE GEMM launch on
+    # the rows of both branches instead of one per branch (enable_stacked_cfg(periodic_gate=True); include/fairygen_hip_gategemm.h)
+    stacked_cfg_periodic_gate: bool = False
     clear_parameters: bool = False
 
     def check_input(self):
         if self.stacked_cfg_hot_lora and not self.stacked_cfg:
             raise ValueError("ModelConfig(stacked_cfg_hot_lora=True) is a form of the stacked CFG forward: it needs stacked_cfg=True")
+        if self.stacked_cfg_periodic_gate and not self.stacked_cfg:
+            raise ValueError("ModelConfig(stacked_cfg_periodic_gate=True) is a form of the stacked CFG forward: it needs stacked_cfg=True")
         if self.path is None and self.model_id is None:
             raise ValueError('No valid model files. Please use `ModelConfig(path="xxx")` or '
                              '`ModelConfig(model_id="xxx/yyy", origin_file_pattern="zzz")`. '
@@ -67,7 +72,8 @@ class ModelConfig:
         return {k: getattr(self, k) for k in (
             "offload_device", "offload_dtype", "onload_device", "onload_dtype",
             "preparing_device", "preparing_dtype", "computation_device", "computation_dtype", "attention_dtype",
-            "attention_pv_dtype", "cross_attention_dtype", "stacked_cfg", "stacked_cfg_hot_lora")}
+            "attention_pv_dtype", "cross_attention_dtype", "stacked_cfg", "stacked_cfg_hot_lora",
+            "stacked_cfg_periodic_gate")}
 
 
 # --------------------------------------------------------------------------------- state-dict files
@@ -248,8 +254,9 @@ class ModelPool:
                 if not hasattr(model, "enable_stacked_cfg"):
                     raise NotImplementedError(f"stacked_cfg is only built for the DiT, not for {cfg['model_name']}")
                 # with an fp8 computation_dtype the config states both wishes in one place: the stacked forward in the fp8 Linear mode;
-                # stacked_cfg_hot_lora rides along: unfused adapters on the "hip" backend
-                model.enable_stacked_cfg(fp8_linear=fp8, hot_lora=bool(vram_config.get("stacked_cfg_hot_lora")))
+                # stacked_cfg_hot_lora rides along: unfused adapters on the "hip" backend; stacked_cfg_periodic_gate: one gated store per pair
+                model.enable_stacked_cfg(fp8_linear=fp8, hot_lora=bool(vram_config.get("stacked_cfg_hot_lora")),
+                                         periodic_gate=bool(vram_config.get("stacked_cfg_periodic_gate")))
             self.model.append(model)
             self.model_name.append(cfg["model_name"])
             self.model_path.append(path)

@@ -106,6 +106,18 @@ def gemm_residual(x, a, weight, bias, mod=None, gate_idx=None, **state):
     return hip.gemm_epilogue(a, weight, bias, out=x, residual=True, mod=mod, gate_idx=gate_idx, **state)
 
 
+# The gated stores of a stacked forward with enable_stacked_cfg(periodic_gate=True): ONE launch on the rows of all elements, the two-row
+# gate table read by the row inside the element (include/fairygen_hip_gategemm.h).  Seams like the ones above.
+def gemm_residual_periodic(x, a, weight, bias, mod, gate_idx, rows_per_element, **state):
+    """x (B, rows, N), in place, += gate * Linear(a), a (B, rows, K); gate row 0 for the first mod.first_rows rows of every element."""
+    return hip.gemm_epilogue(a, weight, bias, out=x, residual=True, mod=mod, gate_idx=gate_idx, rows_per_element=rows_per_element, **state)
+
+
+def gemm_fp8_residual_periodic(x, xq, scale_a, w8, bias, mod, gate_idx, rows_per_element, **state):
+    """... the e4m3 form: xq / scale_a are the quantised rows of all elements."""
+    return hip.gemm_fp8(xq, scale_a, w8, bias, out=x, residual=True, mod=mod, gate_idx=gate_idx, rows_per_element=rows_per_element, **state)
+
+
 def stack_hot_loras(per_group, shapes, device, dtype):
     """The operands of hip.lora_apply for column groups that share an input: per_group[g] = [(alpha * A (r, K), B (Ng, r)), ...] (may be
     empty), shapes[g] = (K, Ng).  Per group the adapters are concatenated along the rank — sum_i (x A_i^T) B_i^T = (x [A_i]^T) [B_i]^T, the
@@ -353,8 +365,11 @@ class _BlockLinears:
         A stacked forward (a: (B, rows, K), B > 1; fp8 Linears without adapters take the second form): the store picks its gate row by
         `row >= first_rows` over the rows of the launch, so with a two-row gate table it is launched once per element on the element's
         rows (fp8: and on the element's quantised rows) — the batch-1 forward's launch, the batch-1 forward's bits; with one gate row or
-        none, one launch takes all B * rows rows.  The adapters behind the stores are ONE fg_lora_apply_bf16_b launch either way: its
-        gate rule counts inside the element (enable_stacked_cfg(hot_lora=True)).
+        none, one launch takes all B * rows rows.  enable_stacked_cfg(periodic_gate=True) replaces the per-element launches by ONE launch
+        of fg_gemm_epilogue_bf16_sp / fg_gemm_fp8_bf16_sp on the B * rows rows, whose gate rule counts inside the element
+        (rows_per_element = rows; elements below the kernel's 256 rows stay per element) — own_gemm_ok is then asked about B * rows.
+        The adapters behind the stores are ONE fg_lora_apply_bf16_b launch either way: its gate rule counts inside the element
+        (enable_stacked_cfg(hot_lora=True)).
         The other form runs its GEMM on B * rows rows and the batched row kernels (include/fairygen_hip_rowbatch.h) do the gate."""
         m, fp8 = self.model, self.fp8
         n, k = weight.shape
@@ -362,11 +377,17 @@ class _BlockLinears:
         pack = m._hot_pack((name,)) if self.hip_hot else False if name in m.hot_loras else None
         nb = a.shape[0]
         per_element = nb > 1 and gmod is not None and gmod.mod_rows == 2
+        periodic = per_element and m.stacked_cfg_periodic_gate and a.shape[1] >= hip.GEMM_GATE_MIN_PERIOD
+        per_element = per_element and not periodic
         rows = a.shape[1] if per_element else nb * a.shape[1]      # of one store launch
         if self.own and store_ok and pack is not False and (own_gemm_ok(rows, n, k) if fp8 is None else fp8_own_ok(n, k)):
             if fp8 is not None:      # the quantisation is per row: one pass over all rows, whichever way the store is launched
                 aq, asc = hip.fp8_quant_rows(a)
-            if per_element and fp8 is None:
+            if periodic and fp8 is None:
+                gemm_residual_periodic(x, a, weight, bias, gmod, gate_idx, a.shape[1], **self.state(rows, n, 2 * k))
+            elif periodic:
+                gemm_fp8_residual_periodic(x, aq, asc, w8, bias, gmod, gate_idx, a.shape[1], **self.state(rows, n, k))
+            elif per_element and fp8 is None:
                 for e in range(nb):
                     gemm_residual(x[e:e + 1], a[e:e + 1], weight, bias, gmod, gate_idx, **self.state(rows, n, 2 * k))
             elif per_element:
@@ -574,6 +595,8 @@ class WanModel(nn.Module):
         self.stacked_cfg_fp8 = False
         # ... also with unfused adapters on hot_backend="hip" (enable_stacked_cfg(hot_lora=True)); False: that combination raises
         self.stacked_cfg_hot_lora = False
+        # ... with the two-row gated stores of the pair in ONE GEMM launch (enable_stacked_cfg(periodic_gate=True)); False: one per element
+        self.stacked_cfg_periodic_gate = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -659,7 +682,7 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ the stacked CFG forward
-    def enable_stacked_cfg(self, flag=True, fp8_linear=False, hot_lora=False):
+    def enable_stacked_cfg(self, flag=True, fp8_linear=False, hot_lora=False, periodic_gate=False):
         """Opt-in, off by default: a merged CFG call (cfg_merge=True: the positive and the negative context batched, wan_video.py
         model_fn_wan_video_steps) runs ONE forward on the residual stream (2, N, dim) instead of two batch-1 forwards one after the other.
         The time rows, the modulation tables and the RoPE tables are one element's and shared; the row kernels that read them take the
@@ -680,10 +703,17 @@ class WanModel(nn.Module):
         gate rule counted inside the element — and in the fp8 Linear mode (with fp8_linear=True) the gated store of fg_gemm_fp8_bf16 is
         launched per element where the gate table has two rows (_BlockLinears.residual).  Linears whose shapes the kernel refuses take
         the reference's torch ops, which are row-wise.  Like fp8_linear it is stated with every call: a call that does not restate it
-        clears it, and enable_stacked_cfg(False) clears all three."""
+        clears it, and enable_stacked_cfg(False) clears all three.
+        periodic_gate: off by default, and then nothing changes.  True runs the gated store with two gate rows (TI2V: self_attn.o and
+        ffn.2) as ONE launch on the 2 N rows instead of one per element: fg_gemm_epilogue_bf16_sp / fg_gemm_fp8_bf16_sp
+        (include/fairygen_hip_gategemm.h) read the gate row by the row inside the element, rows_per_element = N — the same kernel body
+        with another row rule, the same rounding points; the unit plan is that of 2 N rows, so the fp32 summation order of the tiles
+        that end up as k-range pieces may differ from the per-element launches'.  Composes with fp8_linear and hot_lora (the adapter
+        launch behind the store is unchanged); stated with every call like them.  Elements below 256 rows keep the per-element launches."""
         self.stacked_cfg = bool(flag)
         self.stacked_cfg_fp8 = bool(flag) and bool(fp8_linear)
         self.stacked_cfg_hot_lora = bool(flag) and bool(hot_lora)
+        self.stacked_cfg_periodic_gate = bool(flag) and bool(periodic_gate)
         return self
 
     def check_stacked_cfg(self, context_batch, shard=None, sliding_window=False):

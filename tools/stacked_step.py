@@ -12,6 +12,9 @@ WanModel.enable_stacked_cfg(): one forward on (2, N, dim)).  Sizes: "n8190" (lat
 --hot-lora hip: rank-32 adapters on self_attn.q / k / v / o, ffn.0 and ffn.2 of every block, unfused on hot_backend="hip" in the three legs
 (the stacked one with enable_stacked_cfg(hot_lora=True): fg_lora_apply_bf16_b), and a fourth leg "stacked-fused": the stacked forward with
 the same adapters on hot_backend="fused" (folded into the weights before the leg, outside the timed steps) — the price of not fusing.
+--periodic-gate: two legs, "stacked" and "stacked-periodic" — the stacked forward as it is, and with enable_stacked_cfg(periodic_gate=True):
+the two-row gated stores (self_attn.o, ffn.2) as ONE fg_gemm_*_sp launch on 2 N rows instead of one _s launch per element.  Combines with
+--linear fp8 --hot-lora hip (the fp8 form has gated stores only with adapters on the HIP backend).  The cosine is then to "stacked".
 
 A round runs every leg once, in order; `--rounds` rounds follow each other, so a leg's samples are spread over the run and drift hits all
 legs alike.  A leg is ONE denoise call of `1 + --warmup + --steps` steps; step 0 (tables, kv_cache) and the warm-up steps are not timed,
@@ -36,6 +39,7 @@ from fairygen_amd.wan_video_dit import WanModel  # noqa: E402
 SIZES = {"n8190": (1, 48, 13, 42, 60), "headline": (1, 48, 31, 44, 80)}
 LEGS = ("two-call", "merged", "stacked")
 HOT_LEGS = LEGS + ("stacked-fused",)
+PERIODIC_LEGS = ("stacked", "stacked-periodic")
 HOT_TARGETS = ("self_attn.q", "self_attn.k", "self_attn.v", "self_attn.o", "ffn.0", "ffn.2")
 
 
@@ -85,7 +89,8 @@ class Timed:
 
 
 def leg(pipe, shape, mode, warmup, steps, dev, fp8=False, adapters=None):
-    fused = mode == "stacked-fused"
+    fused, periodic = mode == "stacked-fused", mode == "stacked-periodic"
+    mode = "stacked" if periodic else mode
     if adapters is not None:
         pipe.dit.clear_hot_loras()
         pipe.dit.hot_lora_backend = "fused" if fused else "hip"
@@ -102,7 +107,8 @@ def leg(pipe, shape, mode, warmup, steps, dev, fp8=False, adapters=None):
     if mode != "two-call":      # what WanVideoUnit_CfgMerger leaves: the contexts batched in the shared inputs
         shared.update(cfg_merge=True, context=torch.cat([ctx_p, ctx_n], 0))
         posi, nega = {}, {}
-    pipe.dit.enable_stacked_cfg(mode == "stacked", fp8_linear=fp8, hot_lora=adapters is not None and not fused)
+    pipe.dit.enable_stacked_cfg(mode == "stacked", fp8_linear=fp8, hot_lora=adapters is not None and not fused,
+                                periodic_gate=periodic)
     bar = Timed(1 + warmup)
     try:
         with torch.no_grad():
@@ -121,6 +127,7 @@ def main():
     ap.add_argument("--attn", default="bf16,e4m3", help="bf16, and e4m3 = enable_qk8_attention(pv8=True, cross=True, fused_producer=True)")
     ap.add_argument("--legs", default=None, help="default: %s; with --hot-lora: %s" % (",".join(LEGS), ",".join(HOT_LEGS)))
     ap.add_argument("--hot-lora", default=None, choices=("hip",), help="rank-32 unfused adapters on six Linears of every block (hot_backend='hip')")
+    ap.add_argument("--periodic-gate", action="store_true", help="legs stacked and stacked-periodic (enable_stacked_cfg(periodic_gate=True))")
     ap.add_argument("--rank", type=int, default=32)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
@@ -135,7 +142,7 @@ def main():
     if fp8:
         pipe.dit.enable_fp8_linear()
     adapters = hot_adapters(pipe.dit, a.rank, dev) if a.hot_lora else None
-    a.legs = a.legs or ",".join(HOT_LEGS if adapters else LEGS)
+    a.legs = a.legs or ",".join(PERIODIC_LEGS if a.periodic_gate else HOT_LEGS if adapters else LEGS)
     rows = []
     for size in a.sizes.split(","):
         n = SIZES[size][2] * (SIZES[size][3] // 2) * (SIZES[size][4] // 2)
@@ -148,14 +155,16 @@ def main():
                     ms, out = leg(pipe, SIZES[size], mode, a.warmup, a.steps, dev, fp8, adapters)
                     samples[mode] += ms
                     outs[mode] = out
-            ref = outs.get("two-call")
+            ref_leg = "two-call" if "two-call" in outs else "stacked" if a.periodic_gate and "stacked" in outs else None
+            ref = outs.get(ref_leg)
             for mode, ms in samples.items():
                 cos = None if ref is None else torch.nn.functional.cosine_similarity(outs[mode].float().flatten(), ref.float().flatten(), dim=0).item()
                 rows.append({"size": size, "tokens": n, "attn": attn, "leg": mode, "median_ms": round(statistics.median(ms), 3),
                              "sd_ms": round(statistics.pstdev(ms), 3), "samples": len(ms), "cos_vs_two_call": cos,
+                             **({"cos_is_to": ref_leg} if ref_leg not in (None, "two-call") else {}),
                              "same_bits": None if ref is None else bool(torch.equal(outs[mode], ref))})
-                print(f"{size:9s} N={n:6d} {attn:5s} {mode:9s}: median {rows[-1]['median_ms']:9.3f} ms/step, sd {rows[-1]['sd_ms']:7.3f} over {len(ms)} steps "
-                      f"in {a.rounds} rounds; cos to two-call {cos if cos is None else round(cos, 6)}, same bits {rows[-1]['same_bits']}", flush=True)
+                print(f"{size:9s} N={n:6d} {attn:5s} {mode:16s}: median {rows[-1]['median_ms']:9.3f} ms/step, sd {rows[-1]['sd_ms']:7.3f} over {len(ms)} steps "
+                      f"in {a.rounds} rounds; cos to {ref_leg} {cos if cos is None else round(cos, 6)}, same bits {rows[-1]['same_bits']}", flush=True)
             pipe.dit.enable_qk8_attention(False)
             del outs, ref
             gc.collect()
