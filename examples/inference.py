@@ -19,7 +19,8 @@ NEGATIVE = ("è‰²è°ƒè‰³ä¸½ï¼Œè¿‡æ›ï¼Œé™æ€ï¼Œç»†èŠ‚æ¨¡ç³Šä¸æ¸…ï¼Œå­—å¹•ï¼Œé£æ
             "ç”»å¾—ä¸å¥½çš„æ‰‹éƒ¨ï¼Œç”»å¾—ä¸å¥½çš„è„¸éƒ¨ï¼Œç•¸å½¢çš„ï¼Œæ¯å®¹çš„ï¼Œå½¢æ€ç•¸å½¢çš„è‚¢ä½“ï¼Œæ‰‹æŒ‡èåˆï¼Œé™æ­¢ä¸åŠ¨çš„ç”»é¢ï¼Œæ‚ä¹±çš„èƒŒæ™¯ï¼Œä¸‰æ¡è…¿ï¼ŒèƒŒæ™¯äººå¾ˆå¤šï¼Œå€’ç€èµ°")
 
 
-def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False, cross8=False, stacked_cfg=False, periodic_gate=False):
+def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False, cross8=False, stacked_cfg=False, periodic_gate=False,
+                   smooth_v=False):
     dit_cfg = dict(computation_dtype=torch.float8_e4m3fn) if fp8 else {}
     if stacked_cfg:
         dit_cfg["stacked_cfg"] = True
@@ -31,6 +32,8 @@ def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=Fals
         dit_cfg["attention_pv_dtype"] = torch.float8_e4m3fn
     if cross8:
         dit_cfg["cross_attention_dtype"] = torch.float8_e4m3fn
+    if smooth_v:
+        dit_cfg["attention_v_smoothing"] = True
     pipe = WanVideoPipeline.from_pretrained(
         torch_dtype=torch.bfloat16, device="cuda",
         model_configs=[
@@ -41,6 +44,9 @@ def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=Fals
         tokenizer_config=ModelConfig(path=tokenizer))
     if lora:
         pipe.load_lora(pipe.dit, lora, alpha=1)
+    if smooth_v and getattr(pipe, "parallel", None) is not None:
+        raise NotImplementedError("--smooth-v on a token-sharded layout: the key mean of V spans every rank's keys and the sharded mode's "
+                                  "statistics record has no V sum")
     if (qk8 or pv8) and getattr(pipe, "parallel", None) is not None:
         # a token-sharded layout: the e4m3 mode with its statistics exchange (off by default; no multi-GPU hardware run exists); the e4m3
         # cross-attention is not run on token shards and is switched off here
@@ -63,6 +69,9 @@ def main():
                     help="... and e4m3 P V as well (both MFMAs of self-attention 8-bit); implies --qk8-attention")
     ap.add_argument("--cross8-attention", action="store_true",
                     help="... and cross-attention over the text context in the same e4m3 form; implies --pv8-attention")
+    ap.add_argument("--smooth-v", action="store_true",
+                    help="with e4m3 P V: the key mean of every V channel leaves V before it is quantised and joins the output row (sageattn's "
+                         "smooth_v; ModelConfig(attention_v_smoothing=True)); self-attention only; implies --pv8-attention")
     ap.add_argument("--stacked-cfg", action="store_true",
                     help="both CFG branches in ONE stacked forward of the DiT per step (implies cfg_merge=True); single GPU, bf16 Linears or, "
                          "with --fp8, the fp8 Linear mode (the loader then calls enable_stacked_cfg(fp8_linear=True)); --lora here is fused into the weights and works; unfused hot-loaded "
@@ -73,9 +82,9 @@ def main():
     a = ap.parse_args()
     if a.stacked_cfg_periodic_gate and not a.stacked_cfg:
         ap.error("--stacked-cfg-periodic-gate is a form of --stacked-cfg")
-    pv8 = a.pv8_attention or a.cross8_attention
+    pv8 = a.pv8_attention or a.cross8_attention or a.smooth_v
     pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or pv8, pv8, a.cross8_attention, a.stacked_cfg,
-                          a.stacked_cfg_periodic_gate)
+                          a.stacked_cfg_periodic_gate, **({"smooth_v": True} if a.smooth_v else {}))
     image = Image.open(a.image).convert("RGB").resize((832, 480))
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     video = pipe(prompt=a.prompt, negative_prompt=NEGATIVE, input_image=image, num_frames=81, seed=1, tiled=True, cfg_merge=a.stacked_cfg)

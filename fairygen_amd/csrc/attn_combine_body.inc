@@ -1,5 +1,5 @@
-// The body of attn_combine_kernel (attention.hip), included by that kernel and by its batched form attn_combine_b_kernel: both see
-// `const AttnParams P`.
+// The body of attn_combine_kernel (attention.hip), included by that kernel and by its batched form attn_combine_b_kernel and the smoothed-V forms
+// of the two: all see `const AttnParams P`, the constant SMV and (read only with SMV) the pointer mu.
     // one workgroup per 8 rows of a split q-block: 32 lanes x float4 cover d = 128
     const int rows_per_blk = 8, groups = kBM / rows_per_blk;
     const int blk = blockIdx.x / groups, rowgrp = blockIdx.x % groups;      // blk = (bh, rq)
@@ -24,6 +24,12 @@
     }
     const float inv = 1.0f / denom;
     bf16x4 w4;
+    if constexpr (SMV) {      // as the direct store of attn_fwd_body.inc: product, sum, one rounding
+        const f32x4 m4 = *reinterpret_cast<const f32x4*>(mu + (int64_t)h * kD + lane32 * 4);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) w4[j] = (bf16)(acc[j] * inv);
+        for (int j = 0; j < 4; ++j) w4[j] = (bf16)__fadd_rn(__fmul_rn(acc[j], inv), m4[j]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w4[j] = (bf16)(acc[j] * inv);
+    }
     *reinterpret_cast<bf16x4*>(P.out + ((int64_t)b * P.Nq + qrow) * ((int64_t)P.H * kD) + (int64_t)h * kD + lane32 * 4) = w4;

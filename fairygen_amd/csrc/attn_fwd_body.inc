@@ -1,10 +1,12 @@
 // The body of attn_fwd_kernel<QK8, PV8> (attention.hip, which describes it), included by that kernel and by its batched form
-// attn_fwd_b_kernel: both see `const AttnParams P` and the constants QK8 and PV8, and compile the same text.
+// attn_fwd_b_kernel, and by the smoothed-V forms of the two: all see `const AttnParams P`, the constants QK8, PV8 and SMV and (read only
+// with SMV) the pointer mu, and compile the same text.
     const bf16* __restrict__ q = P.q; const bf16* __restrict__ k = P.k; const bf16* __restrict__ v = P.v;
     bf16* __restrict__ out = P.out;
     const int64_t ldq = P.ldq, ldk = P.ldk, ldv = P.ldv, Nq = P.Nq, Nkv = P.Nkv;
     const int H = P.H;
     static_assert(!PV8 || QK8, "the e4m3 P V form extends the e4m3 QK^T form");
+    static_assert(!SMV || PV8, "the smoothed-V form is a form of the e4m3 P V form");
     constexpr float kDefer = PV8 ? kPv8DeferLog2 : kDeferLog2;
     constexpr int kVBuf = PV8 ? kTile8Bytes : kTileBytes;      // bytes of one V buffer in LDS
     constexpr int THREADS = kBM / 32 * 64;         // 8 waves, 32 query rows each
@@ -368,8 +370,14 @@
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         bf16x4 w4;
+                        if constexpr (SMV) {      // + the key mean of the channel: a product, then a sum, then the one rounding to bf16
+                            const f32x4 m4 = *reinterpret_cast<const f32x4*>(mu + (int64_t)h * kD + 32 * db + 8 * g + 4 * hh);
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) w4[j] = (bf16)(o[db][4 * g + j] * inv);
+                            for (int j = 0; j < 4; ++j) w4[j] = (bf16)__fadd_rn(__fmul_rn(o[db][4 * g + j], inv), m4[j]);
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) w4[j] = (bf16)(o[db][4 * g + j] * inv);
+                        }
                         *reinterpret_cast<bf16x4*>(orow + 32 * db + 8 * g + 4 * hh) = w4;
                     }
             }

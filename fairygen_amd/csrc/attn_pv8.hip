@@ -12,9 +12,17 @@
 //      order, so sv is exact -- and converts its tiles: 16-byte reads of v, the dwords of four adjacent keys of one channel into an LDS
 //      image of the transposed tile, 16-byte reads of that image, 16-byte writes of v8t.
 // HBM-bound: v is read twice, half a byte written per byte read.
+//
+// The smoothing form (fg_attn_quant_vt_smooth_bf16, include/fairygen_hip_smoothv.h; DESIGN §5 "e4m3 P V with smoothed V") takes the key
+// mean of every channel out of v before it is quantised:
+//   mu[c] = fl32(fp64 sum over the N keys of v[j][c] / N),  d = fl32(v - mu[c]),  sv[c] = max(max |d| / 448, 2^-20),  v8 = e4m3(d / sv[c]).
+// The same two launches: pass 1 leaves per channel and row stride the fp64 sum, the minimum and the maximum of v (16 bytes a record:
+// fg_attn_smoothv_scratch_bytes); pass 2 adds the sums in a fixed order (below), and since fl32(v - mu) is monotone in v the largest |d|
+// is max(fl32(vmax - mu), fl32(mu - vmin)): no third pass over v.  The attention kernel adds mu back to its output rows.
 #include "common.h"
 #include "../../include/fairygen_hip_pv8.h"
 #include "../../include/fairygen_hip_batch8.h"
+#include "../../include/fairygen_hip_smoothv.h"
 #include "attn_qk8_quant.h"
 #include "attn_pv8_parts.h"
 
@@ -26,8 +34,15 @@ constexpr int kMaxTileBlocks = 32;
 // channels of chunk cl = t & 15 of the 4 keys 4 kg .. 4 kg + 3, kg = t >> 4: 8 dwords, one per channel, to row 8 cl + j of the image at
 // dword pv8_dword(kg) ^ cl (the XOR spreads the 16 chunks of a key group over 16 banks; it permutes the dwords of a 16-byte chunk among
 // themselves and the chunks of a row among themselves, and the read below undoes both).
+// (the body is one text for this form and the smoothing form; FG_QUANT_VT_PLAIN names what only the other form reads)
+#define FG_QUANT_VT_PLAIN                                                                                                       \
+    constexpr bool SMV = false;                                                                                                 \
+    const double* const rsum = nullptr;                                                                                         \
+    const float *const rlo = nullptr, *const rhi = nullptr;                                                                     \
+    float* const mu = nullptr
 __global__ __launch_bounds__(256) void attn_quant_vt_kernel(const bf16* __restrict__ v, int64_t ldv, const float* __restrict__ rec, int parts,
                                                             uint8_t* __restrict__ v8t, float* __restrict__ sv, int64_t N, int64_t Nkp, int H) {
+    FG_QUANT_VT_PLAIN;
 #include "attn_quant_vt_body.inc"
 }
 
@@ -48,6 +63,103 @@ __global__ __launch_bounds__(256) void attn_quant_vt_b_kernel(const bf16* __rest
                                                               const QuantVtStrides bs) {
     const int64_t b = blockIdx.z;
     v += b * bs.v; rec += b * bs.rec; v8t += b * bs.v8t; sv += b * bs.sv;
+    FG_QUANT_VT_PLAIN;
+#include "attn_quant_vt_body.inc"
+}
+#undef FG_QUANT_VT_PLAIN
+
+// ---- the smoothing form.  The records of a launch: rsum [parts][C] fp64, then rlo and rhi [parts][C] fp32 each, in the caller's scratch.
+// Pass 1, workgroup (x, y) of 4 waves as attn_v_stats_body: wave w adds its rows 4 x + w + 4 gridDim.x i in that order in fp64, and the
+// record of the stride is (wave 0 + wave 1) + (wave 2 + wave 3); minimum and maximum do not depend on an order.
+__device__ __forceinline__ void attn_v_stats_smooth_body(const bf16* __restrict__ v, int64_t ldv, double* __restrict__ rsum,
+                                                         float* __restrict__ rlo, float* __restrict__ rhi, int64_t N, int C) {
+    __shared__ double sum_s[3][8][64];
+    __shared__ float lo_s[3][8][64];
+    __shared__ float hi_s[3][8][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int chunk = blockIdx.y * 64 + lane;
+    const bool live = chunk * 8 < C;
+    double sum[8];
+    float lo[8], hi[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        sum[j] = 0.0;
+        lo[j] = INFINITY;
+        hi[j] = -INFINITY;
+    }
+    if (live) {
+        for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < N; row += (int64_t)gridDim.x * 4) {
+            const bf16x8 x = *reinterpret_cast<const bf16x8*>(v + row * ldv + (int64_t)chunk * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float f = (float)x[j];
+                sum[j] += (double)f;
+                lo[j] = fminf(lo[j], f);
+                hi[j] = fmaxf(hi[j], f);
+            }
+        }
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            sum_s[wave - 1][j][lane] = sum[j];
+            lo_s[wave - 1][j][lane] = lo[j];
+            hi_s[wave - 1][j][lane] = hi[j];
+        }
+    }
+    __syncthreads();
+    if (wave > 0 || !live) return;
+    const int64_t at = (int64_t)blockIdx.x * C + (int64_t)chunk * 8;
+    f32x4 l4[2], h4[2];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        rsum[at + j] = (sum[j] + sum_s[0][j][lane]) + (sum_s[1][j][lane] + sum_s[2][j][lane]);
+        l4[j >> 2][j & 3] = fminf(fminf(lo[j], lo_s[0][j][lane]), fminf(lo_s[1][j][lane], lo_s[2][j][lane]));
+        h4[j >> 2][j & 3] = fmaxf(fmaxf(hi[j], hi_s[0][j][lane]), fmaxf(hi_s[1][j][lane], hi_s[2][j][lane]));
+    }
+    *reinterpret_cast<f32x4*>(rlo + at) = l4[0];
+    *reinterpret_cast<f32x4*>(rlo + at + 4) = l4[1];
+    *reinterpret_cast<f32x4*>(rhi + at) = h4[0];
+    *reinterpret_cast<f32x4*>(rhi + at + 4) = h4[1];
+}
+
+// The records of ONE element inside its scratch of `parts` strides of C channels
+struct SmoothRecords {
+    double* rsum;
+    float* rlo;
+    float* rhi;
+};
+__host__ __device__ __forceinline__ SmoothRecords smooth_records(void* scratch, int64_t parts, int64_t C) {
+    double* const rsum = (double*)scratch;
+    float* const rlo = (float*)(rsum + parts * C);
+    return SmoothRecords{rsum, rlo, rlo + parts * C};
+}
+
+struct QuantVtSmoothStrides {
+    int64_t v, v8t, sv, mu, scratch;      // scratch in bytes, the others in elements
+};
+
+// grid dimension z picks the batch element (1 for the single-element entry point: every stride is then unused)
+__global__ __launch_bounds__(256) void attn_v_stats_smooth_kernel(const bf16* __restrict__ v, int64_t ldv, char* __restrict__ scratch, int parts,
+                                                                  int64_t N, int C, const QuantVtSmoothStrides bs) {
+    const int64_t b = blockIdx.z;
+    const SmoothRecords r = smooth_records(scratch + b * bs.scratch, parts, C);
+    attn_v_stats_smooth_body(v + b * bs.v, ldv, r.rsum, r.rlo, r.rhi, N, C);
+}
+
+// Pass 2: attn_quant_vt_kernel's workgroups and tiles.  Thread (c, g) of the 2 x 128 adds the sums of the strides g, g + 2, .. of its
+// channel in that order and the total is half 0 + half 1: with `parts` a function of N alone (v_stat_parts) mu does not depend on a
+// launch grid.
+__global__ __launch_bounds__(256) void attn_quant_vt_smooth_kernel(const bf16* __restrict__ v, int64_t ldv, const char* __restrict__ scratch,
+                                                                   int parts, uint8_t* __restrict__ v8t, float* __restrict__ sv,
+                                                                   float* __restrict__ mu, int64_t N, int64_t Nkp, int H,
+                                                                   const QuantVtSmoothStrides bs) {
+    constexpr bool SMV = true;
+    const int64_t b = blockIdx.z;
+    const SmoothRecords r = smooth_records(const_cast<char*>(scratch) + b * bs.scratch, parts, (int64_t)H * kD);
+    const double* const rsum = r.rsum;
+    const float *const rlo = r.rlo, *const rhi = r.rhi, *const rec = nullptr;
+    v += b * bs.v; v8t += b * bs.v8t; sv += b * bs.sv; mu += b * bs.mu;
 #include "attn_quant_vt_body.inc"
 }
 
@@ -110,4 +222,70 @@ extern "C" int fg_attn_quant_vt_bf16_b(const void* v, int64_t ldv, int64_t bs_v,
     hipLaunchKernelGGL(attn_quant_vt_b_kernel, dim3((unsigned)(nt < kMaxTileBlocks ? nt : kMaxTileBlocks), (unsigned)H, (unsigned)B), dim3(256), 0,
                        (hipStream_t)stream, (const bf16*)v, ldv, (const float*)scratch, (int)parts, (uint8_t*)v8t, sv, N, nkp, H, bs);
     return fg_launch_status("fg_attn_quant_vt_bf16_b");
+}
+
+// ---- the smoothing form (include/fairygen_hip_smoothv.h)
+extern "C" int fg_attn_smoothv_version(void) { return 1; }
+
+extern "C" int64_t fg_attn_smoothv_scratch_bytes(int64_t N, int H) {
+    if (N < 1 || H < 1 || H > 65535) {
+        fg_set_error("fg_attn_smoothv_scratch_bytes: N must be positive, H in 1..65535 (got N=%lld H=%d)", (long long)N, H);
+        return -1;
+    }
+    return v_stat_parts(N) * H * kD * 16;
+}
+
+namespace {
+
+int launch_quant_vt_smooth(const char* who, const void* v, int64_t ldv, void* v8t, float* sv, float* mu, void* scratch, int B, int64_t N, int H,
+                           const QuantVtSmoothStrides& bs, fg_stream_t stream) {
+    const int64_t hd = (int64_t)H * kD, nt = (N + kTileKeys - 1) / kTileKeys, parts = v_stat_parts(N);
+    hipLaunchKernelGGL(attn_v_stats_smooth_kernel, dim3((unsigned)parts, (unsigned)((hd / 8 + 63) / 64), (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, (const bf16*)v, ldv, (char*)scratch, (int)parts, N, (int)hd, bs);
+    if (int e = fg_launch_status(who)) return e;
+    hipLaunchKernelGGL(attn_quant_vt_smooth_kernel, dim3((unsigned)(nt < kMaxTileBlocks ? nt : kMaxTileBlocks), (unsigned)H, (unsigned)B), dim3(256),
+                       0, (hipStream_t)stream, (const bf16*)v, ldv, (const char*)scratch, (int)parts, (uint8_t*)v8t, sv, mu, N, nt * kTileKeys, H, bs);
+    return fg_launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int fg_attn_quant_vt_smooth_bf16(const void* v, int64_t ldv, void* v8t, float* sv, float* mu, void* scratch, int64_t scratch_bytes,
+                                            int64_t N, int H, int D, fg_stream_t stream) {
+    FG_CHECK_ARG(v && v8t && sv && scratch, "fg_attn_quant_vt_smooth_bf16: null pointer");
+    FG_CHECK_ARG(mu && FG_ALIGNED16(mu), "fg_attn_quant_vt_smooth_bf16: mu must be a 16-byte aligned pointer to H*128 floats");
+    FG_CHECK_ARG(D == kD, "fg_attn_quant_vt_smooth_bf16: only head_dim 128 is supported (got %d)", D);
+    FG_CHECK_ARG(N > 0 && H > 0 && H <= 65535, "fg_attn_quant_vt_smooth_bf16: N must be positive, H in 1..65535");
+    const int64_t hd = (int64_t)H * D;
+    FG_CHECK_ARG(ldv >= hd && ldv % 8 == 0, "fg_attn_quant_vt_smooth_bf16: ldv must be >= H*D and a multiple of 8");
+    FG_CHECK_ARG(FG_ALIGNED16(v) && FG_ALIGNED16(v8t) && FG_ALIGNED16(sv) && FG_ALIGNED16(scratch),
+                 "fg_attn_quant_vt_smooth_bf16: v, v8t, sv and scratch must be 16-byte aligned");
+    const int64_t need = v_stat_parts(N) * hd * 16;
+    FG_CHECK_ARG(scratch_bytes >= need, "fg_attn_quant_vt_smooth_bf16: scratch must hold %lld bytes (got %lld)", (long long)need,
+                 (long long)scratch_bytes);
+    return launch_quant_vt_smooth("fg_attn_quant_vt_smooth_bf16", v, ldv, v8t, sv, mu, scratch, 1, N, H, QuantVtSmoothStrides{}, stream);
+}
+
+extern "C" int fg_attn_quant_vt_smooth_bf16_b(const void* v, int64_t ldv, int64_t bs_v, void* v8t, int64_t bs_v8t, float* sv, int64_t bs_sv,
+                                              float* mu, int64_t bs_mu, void* scratch, int64_t scratch_bytes, int64_t bs_scratch, int B,
+                                              int64_t N, int H, int D, fg_stream_t stream) {
+    FG_CHECK_ARG(v && v8t && sv && scratch, "fg_attn_quant_vt_smooth_bf16_b: null pointer");
+    FG_CHECK_ARG(mu && FG_ALIGNED16(mu), "fg_attn_quant_vt_smooth_bf16_b: mu must be a 16-byte aligned pointer to H*128 floats per element");
+    FG_CHECK_ARG(D == kD, "fg_attn_quant_vt_smooth_bf16_b: only head_dim 128 is supported (got %d)", D);
+    FG_CHECK_ARG(B >= 1 && B <= 65535, "fg_attn_quant_vt_smooth_bf16_b: B must be in 1..65535 (got %d)", B);
+    FG_CHECK_ARG(N > 0 && H > 0 && H <= 65535, "fg_attn_quant_vt_smooth_bf16_b: N must be positive, H in 1..65535");
+    const int64_t hd = (int64_t)H * D, nkp = (N + kTileKeys - 1) / kTileKeys * kTileKeys;
+    FG_CHECK_ARG(ldv >= hd && ldv % 8 == 0, "fg_attn_quant_vt_smooth_bf16_b: ldv must be >= H*D and a multiple of 8");
+    FG_CHECK_ARG(FG_ALIGNED16(v) && FG_ALIGNED16(v8t) && FG_ALIGNED16(sv) && FG_ALIGNED16(scratch),
+                 "fg_attn_quant_vt_smooth_bf16_b: v, v8t, sv and scratch must be 16-byte aligned");
+    const int64_t need = v_stat_parts(N) * hd * 16;
+    FG_CHECK_ARG(scratch_bytes >= need, "fg_attn_quant_vt_smooth_bf16_b: scratch must hold %lld bytes per element (got %lld)", (long long)need,
+                 (long long)scratch_bytes);
+    FG_CHECK_ARG(bs_v >= (N - 1) * ldv + hd && bs_v8t >= hd * nkp && bs_sv >= hd && bs_mu >= hd && bs_scratch >= need,
+                 "fg_attn_quant_vt_smooth_bf16_b: a batch stride is smaller than one element of its operand");
+    FG_CHECK_ARG(bs_v % 8 == 0 && bs_v8t % 16 == 0 && bs_sv % 4 == 0 && bs_mu % 4 == 0 && bs_scratch % 16 == 0,
+                 "fg_attn_quant_vt_smooth_bf16_b: batch strides must keep the alignment (v: 8 elements; v8t: 16 bytes; sv, mu: 4 floats; "
+                 "scratch: 16 bytes)");
+    return launch_quant_vt_smooth("fg_attn_quant_vt_smooth_bf16_b", v, ldv, v8t, sv, mu, scratch, B, N, H,
+                                  QuantVtSmoothStrides{bs_v, bs_v8t, bs_sv, bs_mu, bs_scratch}, stream);
 }

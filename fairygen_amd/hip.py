@@ -206,6 +206,22 @@ _GATEGEMM_QUERIES = {
 GATEGEMM_SYMBOLS = sorted(list(_GATEGEMM_SIGNATURES) + list(_GATEGEMM_QUERIES))    # what include/fairygen_hip_gategemm.h declares
 GEMM_GATE_MIN_PERIOD = 256      # rows_per_element below the tile height is refused unless it covers all rows (one element)
 
+# The extension of include/fairygen_hip_smoothv.h (the e4m3 P V self-attention with V mean-smoothed: the key mean of every channel leaves V
+# before it is quantised and joins the output row before it is rounded): an eleventh pair.  The pv8 signatures with mu behind sv.
+SMOOTHV_ABI_VERSION = 1   # fg_attn_smoothv_version
+_SMOOTHV_SIGNATURES = {
+    "fg_attn_quant_vt_smooth_bf16": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
+    "fg_attn_quant_vt_smooth_bf16_b": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i64, _i32, _i32, _vp],
+    "fg_attn_fwd_pv8s_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _i64, _vp],
+    "fg_attn_fwd_pv8s_bf16_b": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32,
+                                _i32, _f32, _vp, _i64, _vp],
+}
+_SMOOTHV_QUERIES = {
+    "fg_attn_smoothv_version": (_i32, []),
+    "fg_attn_smoothv_scratch_bytes": (_i64, [_i64, _i32]),
+}
+SMOOTHV_SYMBOLS = sorted(list(_SMOOTHV_SIGNATURES) + list(_SMOOTHV_QUERIES))    # what include/fairygen_hip_smoothv.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -228,12 +244,12 @@ def load():
     for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
             list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()) + \
             list(_ROWBATCH8_SIGNATURES.items()) + list(_LORABATCH_SIGNATURES.items()) + list(_UP2PHASE_SIGNATURES.items()) + \
-            list(_GATEGEMM_SIGNATURES.items()):
+            list(_GATEGEMM_SIGNATURES.items()) + list(_SMOOTHV_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
             list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()) + \
             list(_ROWBATCH8_QUERIES.items()) + list(_LORABATCH_QUERIES.items()) + list(_UP2PHASE_QUERIES.items()) + \
-            list(_GATEGEMM_QUERIES.items()):
+            list(_GATEGEMM_QUERIES.items()) + list(_SMOOTHV_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
@@ -245,7 +261,8 @@ def load():
                                  ("fg_dit_rowbatch8_version", ROWBATCH8_ABI_VERSION, " (fp8-output norms on batches that share a table)"),
                                  ("fg_dit_lorabatch_version", LORABATCH_ABI_VERSION, " (hot-loaded adapters on batches that share a table)"),
                                  ("fg_conv_up2phase_version", UP2PHASE_ABI_VERSION, " (upsample conv as four 2x2 phase convs)"),
-                                 ("fg_gemm_gate_period_version", GATEGEMM_ABI_VERSION, " (gated GEMM store on batches that share a gate table)")):
+                                 ("fg_gemm_gate_period_version", GATEGEMM_ABI_VERSION, " (gated GEMM store on batches that share a gate table)"),
+                                 ("fg_attn_smoothv_version", SMOOTHV_ABI_VERSION, " (e4m3 P V with mean-smoothed V)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -957,50 +974,68 @@ def attn_quant_qk(q, k, num_heads, bufs=None):
     return bufs
 
 
-def attention_pv8_scratch(n, num_heads, head_dim, device, batch=1):
+def attention_pv8_scratch(n, num_heads, head_dim, device, batch=1, smooth=False):
     """The buffers fg_attn_quant_vt_bf16 fills for (n, num_heads * head_dim) v: (v8t (H, 128, n rounded up to 64) e4m3, sv (H, 128) fp32,
-    the statistics scratch).  batch > 1: the same three with a leading batch dimension (include/fairygen_hip_batch8.h)."""
+    the statistics scratch).  batch > 1: the same three with a leading batch dimension (include/fairygen_hip_batch8.h).  smooth: the
+    four of fg_attn_quant_vt_smooth_bf16 (include/fairygen_hip_smoothv.h) — its larger scratch, and mu (H, 128) fp32 behind it."""
     if head_dim != 128:
         raise HipLibraryError(f"attention_pv8_scratch: only head_dim 128 is supported (got {head_dim})")
-    need = load().fg_attn_pv8_scratch_bytes(n, num_heads)
+    need = (load().fg_attn_smoothv_scratch_bytes if smooth else load().fg_attn_pv8_scratch_bytes)(n, num_heads)
     if need < 0:
         raise HipLibraryError(f"attention_pv8_scratch: {load().fg_last_error().decode()}")
     lead = (batch,) if batch > 1 else ()
     return (torch.empty(lead + (num_heads, head_dim, (n + 63) // 64 * 64), dtype=torch.float8_e4m3fn, device=device),
             torch.empty(lead + (num_heads, head_dim), dtype=torch.float32, device=device),
-            torch.empty(lead + (need,), dtype=torch.uint8, device=device))
+            torch.empty(lead + (need,), dtype=torch.uint8, device=device)) + \
+        ((torch.empty(lead + (num_heads, head_dim), dtype=torch.float32, device=device),) if smooth else ())
 
 
-def attn_quant_vt(v, num_heads, bufs=None):
+def attn_quant_vt(v, num_heads, bufs=None, smooth=False):
     """The e4m3 V operand of the e4m3 P V form from v (1, N, H*128) bf16 (a column slice with a leading dimension is fine): one scale per
-    head and channel, the bytes transposed and tile-ordered by PV8_KEY_ORDER (include/fairygen_hip_pv8.h).  bufs: attention_pv8_scratch's."""
+    head and channel, the bytes transposed and tile-ordered by PV8_KEY_ORDER (include/fairygen_hip_pv8.h).  bufs: attention_pv8_scratch's.
+    smooth: the key mean of every channel taken out first (fg_attn_quant_vt_smooth_bf16, include/fairygen_hip_smoothv.h); bufs and the
+    result are then attention_pv8_scratch(smooth=True)'s four, mu last."""
+    if len(bufs if bufs is not None else ()) not in (0, 4 if smooth else 3):
+        raise HipLibraryError(f"attn_quant_vt: bufs must be attention_pv8_scratch(smooth={bool(smooth)})'s")
     ldv = _ld_rows(v, "v")
     b, n, hd = v.shape
     if b > 1:      # a batch: fg_attn_quant_vt_bf16_b, sv per element
-        bufs = attention_pv8_scratch(n, num_heads, hd // num_heads, v.device, b) if bufs is None else bufs
-        v8t, sv, scratch = bufs
+        bufs = attention_pv8_scratch(n, num_heads, hd // num_heads, v.device, b, smooth) if bufs is None else bufs
+        v8t, sv, scratch = bufs[:3]
         nkp = (n + 63) // 64 * 64
         if v8t.shape != (b, num_heads, hd // num_heads, nkp) or sv.shape != (b, num_heads, hd // num_heads) or scratch.dim() != 2 or \
-                scratch.shape[0] != b or not all(t.is_contiguous() for t in bufs):
+                scratch.shape[0] != b or not all(t.is_contiguous() for t in bufs) or (smooth and bufs[3].shape != sv.shape):
             raise HipLibraryError("attn_quant_vt: bufs do not match (B, N, H*D)")
+        if smooth:
+            _call("fg_attn_quant_vt_smooth_bf16_b", _ptr(v), ldv, v.stride(0), _ptr(v8t), hd * nkp, _ptr(sv), hd, _ptr(bufs[3]), hd,
+                  _ptr(scratch), scratch.shape[1], scratch.stride(0), b, n, num_heads, hd // num_heads, _stream(v))
+            return bufs
         _call("fg_attn_quant_vt_bf16_b", _ptr(v), ldv, v.stride(0), _ptr(v8t), hd * nkp, _ptr(sv), hd, _ptr(scratch), scratch.shape[1],
               scratch.stride(0), b, n, num_heads, hd // num_heads, _stream(v))
         return bufs
     if b != 1:
         raise HipLibraryError(f"attn_quant_vt: v must be (1, N, H*D), got {tuple(v.shape)}")
-    bufs = attention_pv8_scratch(n, num_heads, hd // num_heads, v.device) if bufs is None else bufs
-    v8t, sv, scratch = bufs
-    if v8t.shape != (num_heads, hd // num_heads, (n + 63) // 64 * 64) or sv.shape != (num_heads, hd // num_heads) or not v8t.is_contiguous():
+    bufs = attention_pv8_scratch(n, num_heads, hd // num_heads, v.device, 1, smooth) if bufs is None else bufs
+    v8t, sv, scratch = bufs[:3]
+    if v8t.shape != (num_heads, hd // num_heads, (n + 63) // 64 * 64) or sv.shape != (num_heads, hd // num_heads) or not v8t.is_contiguous() or \
+            (smooth and (bufs[3].shape != sv.shape or not bufs[3].is_contiguous())):
         raise HipLibraryError("attn_quant_vt: bufs do not match (N, H*D)")
+    if smooth:
+        _call("fg_attn_quant_vt_smooth_bf16", _ptr(v), ldv, _ptr(v8t), _ptr(sv), _ptr(bufs[3]), _ptr(scratch), scratch.numel(), n, num_heads,
+              hd // num_heads, _stream(v))
+        return bufs
     _call("fg_attn_quant_vt_bf16", _ptr(v), ldv, _ptr(v8t), _ptr(sv), _ptr(scratch), scratch.numel(), n, num_heads, hd // num_heads, _stream(v))
     return bufs
 
 
-def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, workspace=None, pv8=False, pv8_bufs=None):
+def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, workspace=None, pv8=False, pv8_bufs=None, smooth=False):
     """fg_attn_fwd_qk8_bf16 on operands that are quantised already (attn_quant_qk's, or the fused producers'): q8 (Nq, H*128), k8 (Nkv,
     H*128) e4m3, sq (Nq, H), sk (H), v (1, Nkv, H*128) bf16 -> (1, Nq, H*128); the model calls it with Nq = Nkv.  workspace as in
     attention().  pv8: the P V product in e4m3 too — fg_attn_quant_vt_bf16 on v (into pv8_bufs: attention_pv8_scratch's tuple, else
-    allocated), then fg_attn_fwd_pv8_bf16."""
+    allocated), then fg_attn_fwd_pv8_bf16.  smooth (with pv8): V mean-smoothed — attn_quant_vt(smooth=True), then fg_attn_fwd_pv8s_bf16
+    (include/fairygen_hip_smoothv.h); pv8_bufs is then attention_pv8_scratch(smooth=True)'s."""
+    if smooth and not pv8:
+        raise HipLibraryError("attention_qk8_pre: smooth=True is a form of the e4m3 P V product (pv8=True)")
     ldv = _ld_rows(v, "v")
     b, nkv, hd = v.shape
     if b > 1 and q8.dim() == 3:      # a batch of operands (attn_quant_qk's, or the fused producers', on a batch): the _b entry points
@@ -1009,8 +1044,8 @@ def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, worksp
                 not all(t.is_contiguous() for t in (q8, k8, sq, sk)):
             raise HipLibraryError(f"attention_qk8_pre: k8 and sk for v {tuple(v.shape)}, sq for q8 {tuple(q8.shape)}, all contiguous")
         if pv8:
-            v8t, sv, _ = attn_quant_vt(v, num_heads, pv8_bufs)
-            return attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=out, scale=scale, workspace=workspace)
+            v8t, sv, _, *mu = attn_quant_vt(v, num_heads, pv8_bufs, smooth)
+            return attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=out, scale=scale, workspace=workspace, mu=mu[0] if smooth else None)
         out = torch.empty((b, nq, hd), dtype=v.dtype, device=v.device) if out is None else out
         ws, need = _attn_ws(v.device, b, nq, nkv, num_heads, workspace, per_element=True)
         _call("fg_attn_fwd_qk8_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v), ldv,
@@ -1023,7 +1058,11 @@ def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, worksp
     out = torch.empty((b, nq, hd), dtype=v.dtype, device=v.device) if out is None else out
     ws, need = _attn_ws(v.device, 1, nq, nkv, num_heads, workspace)
     if pv8:
-        v8t, sv, _ = attn_quant_vt(v, num_heads, pv8_bufs)
+        v8t, sv, _, *mu = attn_quant_vt(v, num_heads, pv8_bufs, smooth)
+        if smooth:
+            _call("fg_attn_fwd_pv8s_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(mu[0]), _ptr(out), nq, nkv, num_heads,
+                  d, float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
+            return out
         _call("fg_attn_fwd_pv8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
               float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
         return out
@@ -1042,14 +1081,22 @@ def _batch8_check(who, q8, k8, sq, sk, v8t, sv, num_heads):
     return b, nq, hd, nkv, d
 
 
-def attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None, workspace=None):
+def attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None, workspace=None, mu=None):
     """fg_attn_fwd_pv8_bf16 on operands that are ALL ready: q8 (Nq, H*128), k8 (Nkv, H*128) e4m3, sq (Nq, H), sk (H), v8t (H, 128, Nkv
     rounded up to 64) e4m3 and sv (H, 128) as attn_quant_vt or attn_shard8_vt left them -> (1, Nq, H*128) bf16.  Nq need not be Nkv (a
-    token shard's queries against all keys).  workspace as in attention().  With a leading batch dimension on all six: the batched form."""
+    token shard's queries against all keys).  workspace as in attention().  With a leading batch dimension on all six: the batched form.
+    mu: attn_quant_vt(smooth=True)'s key means of v, shaped like sv — fg_attn_fwd_pv8s_bf16 / _b, which add them to the output rows."""
+    if mu is not None and (mu.shape != sv.shape or mu.dtype != torch.float32 or not mu.is_contiguous()):
+        raise HipLibraryError(f"attention_pv8_pre: mu must be fp32, contiguous and shaped like sv {tuple(sv.shape)}")
     if q8.dim() == 3:
         b, nq, hd, nkv, d = _batch8_check("attention_pv8_pre", q8, k8, sq, sk, v8t, sv, num_heads)
         out = torch.empty((b, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
         ws, need = _attn_ws(q8.device, b, nq, nkv, num_heads, workspace, per_element=True)
+        if mu is not None:
+            _call("fg_attn_fwd_pv8s_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
+                  v8t.stride(0), _ptr(sv), hd, _ptr(mu), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d,
+                  float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q8))
+            return out
         _call("fg_attn_fwd_pv8_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
               v8t.stride(0), _ptr(sv), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d, float(d) ** -0.5 if scale is None else float(scale),
               _ptr(ws) if need > 0 else None, need, _stream(q8))
@@ -1061,6 +1108,10 @@ def attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None, 
         raise HipLibraryError(f"attention_pv8_pre: k8, sq, sk, v8t, sv do not match q8 {tuple(q8.shape)} and {nkv} keys")
     out = torch.empty((1, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
     ws, need = _attn_ws(q8.device, 1, nq, nkv, num_heads, workspace)
+    if mu is not None:
+        _call("fg_attn_fwd_pv8s_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(mu), _ptr(out), nq, nkv, num_heads, d,
+              float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q8))
+        return out
     _call("fg_attn_fwd_pv8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q8))
     return out
@@ -1166,14 +1217,14 @@ def attn_shard8_vt(v8, num_heads, v8t=None):
     return v8t
 
 
-def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs=None, pv8=False, pv8_bufs=None):
+def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs=None, pv8=False, pv8_bufs=None, smooth=False):
     """attention() for self-attention of one batch element with the e4m3 Q K^T product (the reference's sageattn branch,
     models/wan_video_dit.py:48-52): fg_attn_quant_qk_bf16, then fg_attn_fwd_qk8_bf16.  workspace as in attention(); bufs: the quantised
-    operands' buffers when the caller owns them (a captured step), else allocated per call.  pv8 / pv8_bufs: attention_qk8_pre's."""
+    operands' buffers when the caller owns them (a captured step), else allocated per call.  pv8 / pv8_bufs / smooth: attention_qk8_pre's."""
     if v.shape != q.shape:
         raise HipLibraryError(f"attention_qk8: self-attention only, q, k, v of one shape (got v {tuple(v.shape)})")
     q8, k8, sq, sk, _ = attn_quant_qk(q, k, num_heads, bufs)
-    return attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=out, scale=scale, workspace=workspace, pv8=pv8, pv8_bufs=pv8_bufs)
+    return attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=out, scale=scale, workspace=workspace, pv8=pv8, pv8_bufs=pv8_bufs, smooth=smooth)
 
 
 def attention_qk8_fused_scratch(n, num_heads, head_dim, device, batch=1):

@@ -256,15 +256,17 @@ class _BlockLinears:
 
     def pv8_kw(self, v, num_heads):
         """The pv8= / pv8_bufs= of the e4m3 attention call on v (1, N, H*D): nothing unless enable_qk8_attention(pv8=True); a captured step
-        owns v8t, sv and the statistics scratch next to the e4m3 q / k buffers."""
+        owns v8t, sv and the statistics scratch next to the e4m3 q / k buffers — with smooth_v=True (smooth= of the call) also mu, next
+        to sv, and the larger scratch of that form."""
         if not self.model.pv8_attention:
             return {}
+        smooth = {"smooth": True} if self.model.smoothv_attention else {}
         if self.owned is None:
-            return {"pv8": True}
-        key = (v.shape[1], num_heads, v.shape[2] // num_heads, v.device, "pv8")
+            return {"pv8": True, **smooth}
+        key = (v.shape[1], num_heads, v.shape[2] // num_heads, v.device, "pv8s" if smooth else "pv8")
         if key not in self.owned.attn_qk8_bufs:
-            self.owned.attn_qk8_bufs[key] = hip.attention_pv8_scratch(*key[:4])
-        return {"pv8": True, "pv8_bufs": self.owned.attn_qk8_bufs[key]}
+            self.owned.attn_qk8_bufs[key] = hip.attention_pv8_scratch(*key[:4], smooth=bool(smooth))
+        return {"pv8": True, "pv8_bufs": self.owned.attn_qk8_bufs[key], **smooth}
 
     def cross8_q(self, qc, norm_q, num_heads):
         """The e4m3 q operand of cross-attention (enable_qk8_attention(cross=True)) from the q Linear's output: the RMSNorm pass without a
@@ -585,6 +587,8 @@ class WanModel(nn.Module):
         self.qk8_fused_producer = False
         # ... and with the P V product in e4m3 too (enable_qk8_attention(pv8=True)); False: P V in bf16
         self.pv8_attention = False
+        # ... with V mean-smoothed in that product (enable_qk8_attention(pv8=True, smooth_v=True)); False: V quantised as it is
+        self.smoothv_attention = False
         # ... and on token-sharded layouts (enable_qk8_attention(sharded=True)); False: an active shard raises
         self.qk8_sharded = False
         # ... and cross-attention in the e4m3 form too (enable_qk8_attention(pv8=True, cross=True)); False: cross-attention in bf16
@@ -633,7 +637,7 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ e4m3 Q K^T self-attention (models/wan_video_dit.py:48-52)
-    def enable_qk8_attention(self, flag=True, fused_producer=False, pv8=False, sharded=False, cross=False):
+    def enable_qk8_attention(self, flag=True, fused_producer=False, pv8=False, sharded=False, cross=False, smooth_v=False):
         """Run self-attention of every block like the reference's flash_attention does when the sageattention package is present
         (sageattn(q, k, v)): Q K^T from e4m3 operands — K mean-smoothed with one scale per head, Q with one scale per row and head
         (fg_attn_quant_qk_bf16) — on fg_attn_fwd_qk8_bf16; softmax and P V as before, v in bf16.  Only the stock AttentionModule of
@@ -667,18 +671,35 @@ class WanModel(nn.Module):
         the query blocks.  Composes with enable_fp8_linear, hot adapters and graph=True (the captured step owns the q8 / sq buffers, the
         context operands live in the loop's kv_cache).  An active token shard raises NotImplementedError, sharded=True or not: the
         query rows are local and the context is whole on every rank, so no collective would be needed, but no sharded run of it has
-        been tested."""
+        been tested.
+        smooth_v: off by default.  The e4m3 P V product with V mean-smoothed, what sageattn ships as smooth_v
+        (include/fairygen_hip_smoothv.h): the key mean of every head and channel leaves v before it is quantised
+        (fg_attn_quant_vt_smooth_bf16 in place of fg_attn_quant_vt_bf16) and joins the output row in fp32 before its rounding to bf16
+        (fg_attn_fwd_pv8s_bf16 in place of fg_attn_fwd_pv8_bf16), so the rounding of P no longer scales the part of V that all keys
+        share and the e4m3 range covers the spread alone.  It needs pv8 (ValueError without), has its routing, works behind either
+        producer path and composes with enable_fp8_linear, hot adapters, graph=True (the captured step owns mu next to sv) and the
+        stacked CFG forward (the batched entry points).  It does NOT run on token shards, sharded=True or not: the mean spans every
+        rank's keys and the statistics record of include/fairygen_hip_shard8.h carries no V sum — together with sharded=True it raises
+        ValueError here, and an active shard raises NotImplementedError at the forward.  With cross=True it smooths self-attention
+        only: the e4m3 cross-attention keeps its unsmoothed V8^T."""
         if pv8 and not flag:
             raise ValueError("enable_qk8_attention(pv8=True) needs the e4m3 Q K^T mode on (flag=True)")
         if sharded and not flag:
             raise ValueError("enable_qk8_attention(sharded=True) needs the e4m3 Q K^T mode on (flag=True)")
         if cross and not (flag and pv8):
             raise ValueError("enable_qk8_attention(cross=True) needs the e4m3 Q K^T mode and its e4m3 P V form on (flag=True, pv8=True)")
+        if smooth_v and not (flag and pv8):
+            raise ValueError("enable_qk8_attention(smooth_v=True) needs the e4m3 Q K^T mode and its e4m3 P V form on (flag=True, pv8=True): "
+                             "it is V of that product that is mean-smoothed")
+        if smooth_v and sharded:
+            raise ValueError("enable_qk8_attention(smooth_v=True, sharded=True): the key mean of V spans every rank's keys and the statistics "
+                             "record of the sharded mode (include/fairygen_hip_shard8.h) has no V sum; run token shards without smooth_v")
         self.qk8_attention = bool(flag)
         self.qk8_fused_producer = bool(flag) and bool(fused_producer)
         self.pv8_attention = bool(flag) and bool(pv8)
         self.qk8_sharded = bool(flag) and bool(sharded)
         self.cross8_attention = bool(flag) and bool(pv8) and bool(cross)
+        self.smoothv_attention = bool(flag) and bool(pv8) and bool(smooth_v)
         return self
 
     # ------------------------------------------------------------------ the stacked CFG forward
@@ -738,6 +759,10 @@ class WanModel(nn.Module):
             raise NotImplementedError(f"stacked_cfg stacks the CFG pair: a context batch of 2, not {context_batch}")
 
     def check_qk8_layout(self, shard):
+        if self.smoothv_attention and shard is not None and shard.active:
+            raise NotImplementedError("enable_qk8_attention(smooth_v=True) with a token-sharded layout: the key mean of V spans every rank's "
+                                      "keys and the statistics record of the sharded mode has no V sum; switch it off (smooth_v=False) for a "
+                                      "sharded run")
         if self.cross8_attention and shard is not None and shard.active:
             raise NotImplementedError("enable_qk8_attention(cross=True) with a token-sharded layout: the e4m3 cross-attention has not been "
                                       "run on token shards; switch it off (cross=False) for a sharded run")

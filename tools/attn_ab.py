@@ -200,6 +200,10 @@ def main():
     ap.add_argument("--pv8", action="store_true", help="implies --qk8; also time, in the same rounds, the form with the P V product in e4m3 too: "
                     "'pv8' = fg_attn_quant_qk_bf16 + fg_attn_quant_vt_bf16 + fg_attn_fwd_pv8_bf16, 'pv8-attn' = the attention launch alone, "
                     "and the quantise passes alone: 'quant-qk', 'quant-vt' (nq == nkv)")
+    ap.add_argument("--smooth-v", action="store_true", help="with --pv8: also time, in the same rounds, the form with V mean-smoothed "
+                    "(include/fairygen_hip_smoothv.h): 'pv8s' = fg_attn_quant_qk_bf16 + fg_attn_quant_vt_smooth_bf16 + fg_attn_fwd_pv8s_bf16, "
+                    "'pv8s-attn' = the attention launch alone, 'quant-vts' = its V producer alone; every leg is then reported with its standard "
+                    "deviation")
     ap.add_argument("--qk8-fused", action="store_true", help="time the whole chain from the q | k | v buffer of the qkv GEMM to the attention "
                     "output (nq == nkv), in three forms: 'chain-bf16' = RMSNorm+RoPE of q and k + fg_attn_fwd_bf16 (the default path, its "
                     "pre-multiplied form), 'chain-qk8' = the same two norms + fg_attn_quant_qk_bf16 + fg_attn_fwd_qk8_bf16, 'chain-qk8-fused' = "
@@ -210,6 +214,7 @@ def main():
         return shard8(a)
     if a.cross8:
         return cross8(a)
+    a.pv8 = a.pv8 or a.smooth_v
     a.qk8 = a.qk8 or a.pv8
     dev = "cuda"
     g = torch.Generator(dev).manual_seed(0)
@@ -292,6 +297,21 @@ def main():
             print(f"check[random] {name}: max|out - ref_f32| = {err.max().item():.5f}, mean {err.mean().item():.6f}", flush=True)
         fns += [("pv8", pv8_chain), ("pv8-attn", pv8_attn_only), ("quant-qk", lambda: hip.attn_quant_qk(q, k, a.heads, bufs)),
                 ("quant-vt", lambda: hip.attn_quant_vt(v, a.heads, pv_bufs))]
+    if a.smooth_v:
+        pvs_bufs, ws_pvs = hip.attention_pv8_scratch(a.nq, a.heads, 128, q.device, smooth=True), []
+
+        def pv8s_attn_only():
+            hip._call("fg_attn_fwd_pv8s_bf16", *[hip._ptr(t) for t in bufs[:4]], hip._ptr(pvs_bufs[0]), hip._ptr(pvs_bufs[1]), hip._ptr(pvs_bufs[3]),
+                      hip._ptr(out), a.nq, a.nq, a.heads, 128, 128 ** -0.5, hip._ptr(wsb) if need else None, need, hip._stream(out))
+
+        def pv8s_chain():
+            hip.attention_qk8(q, k, v, a.heads, out=out, workspace=ws_pvs, bufs=bufs, pv8=True, pv8_bufs=pvs_bufs, smooth=True)
+        out.zero_()
+        pv8s_chain()
+        torch.cuda.synchronize()
+        err = (out[0, rows].float() - reference(q, k, v)).abs()
+        print(f"check[random] pv8s: max|out - ref_f32| = {err.max().item():.5f}, mean {err.mean().item():.6f}", flush=True)
+        fns += [("pv8s", pv8s_chain), ("pv8s-attn", pv8s_attn_only), ("quant-vts", lambda: hip.attn_quant_vt(v, a.heads, pvs_bufs, smooth=True))]
     if a.qk8_fused:
         n, nh = a.nq, a.heads
         qkv = rnd(1, n, 3 * c)
@@ -360,7 +380,12 @@ def main():
             sd = (sum((t - mean) ** 2 for t in ts) / max(len(ts) - 1, 1)) ** 0.5
             print(f"{n}: N={a.nq} H={a.heads}: mean {mean:.4f} ms, sd {sd:.4f}, median {med:.4f}, min {mn:.4f}, max {ts[-1]:.4f} ({len(ts)} runs)", flush=True)
             continue
-        print(f"{n}: nq={a.nq} nkv={a.nkv} H={a.heads}: median {med:.3f} ms = {fl / med / 1e9:.1f} TFLOP/s, min {mn:.3f} ms = {fl / mn / 1e9:.1f}", flush=True)
+        spread = ""
+        if a.smooth_v:
+            mean = sum(ts) / len(ts)
+            spread = f", mean {mean:.3f}, sd {(sum((t - mean) ** 2 for t in ts) / max(len(ts) - 1, 1)) ** 0.5:.4f} ({len(ts)} runs)"
+        print(f"{n}: nq={a.nq} nkv={a.nkv} H={a.heads}: median {med:.3f} ms = {fl / med / 1e9:.1f} TFLOP/s, min {mn:.3f} ms = {fl / mn / 1e9:.1f}"
+              f"{spread}", flush=True)
 
 
 if __name__ == "__main__":
