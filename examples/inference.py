@@ -20,7 +20,7 @@ NEGATIVE = ("Ëâ≤Ë∞ÉËâ≥‰∏ΩÔºåËøáÊõùÔºåÈùôÊÄÅÔºåÁªÜËäÇÊ®°Á≥ä‰∏çÊ∏ÖÔºåÂ≠óÂπïÔºåÈ£éÊ
 
 
 def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=False, cross8=False, stacked_cfg=False, periodic_gate=False,
-                   smooth_v=False):
+                   smooth_v=False, smooth_v_cross=False):
     dit_cfg = dict(computation_dtype=torch.float8_e4m3fn) if fp8 else {}
     if stacked_cfg:
         dit_cfg["stacked_cfg"] = True
@@ -34,6 +34,8 @@ def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=Fals
         dit_cfg["cross_attention_dtype"] = torch.float8_e4m3fn
     if smooth_v:
         dit_cfg["attention_v_smoothing"] = True
+    if smooth_v_cross:
+        dit_cfg["cross_attention_v_smoothing"] = True
     pipe = WanVideoPipeline.from_pretrained(
         torch_dtype=torch.bfloat16, device="cuda",
         model_configs=[
@@ -49,7 +51,7 @@ def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=Fals
                                   "statistics record has no V sum")
     if (qk8 or pv8) and getattr(pipe, "parallel", None) is not None:
         # a token-sharded layout: the e4m3 mode with its statistics exchange (off by default; no multi-GPU hardware run exists); the e4m3
-        # cross-attention is not run on token shards and is switched off here
+        # cross-attention (--smooth-v-cross with it) is not run on token shards and is switched off here
         pipe.dit.enable_qk8_attention(fused_producer=pipe.dit.qk8_fused_producer, pv8=pv8, sharded=True)
     return pipe
 
@@ -72,6 +74,9 @@ def main():
     ap.add_argument("--smooth-v", action="store_true",
                     help="with e4m3 P V: the key mean of every V channel leaves V before it is quantised and joins the output row (sageattn's "
                          "smooth_v; ModelConfig(attention_v_smoothing=True)); self-attention only; implies --pv8-attention")
+    ap.add_argument("--smooth-v-cross", action="store_true",
+                    help="with e4m3 cross-attention: the same smoothing for V of the text context, most of whose 512 keys carry one padding "
+                         "row (ModelConfig(cross_attention_v_smoothing=True)); independent of --smooth-v; implies --cross8-attention")
     ap.add_argument("--stacked-cfg", action="store_true",
                     help="both CFG branches in ONE stacked forward of the DiT per step (implies cfg_merge=True); single GPU, bf16 Linears or, "
                          "with --fp8, the fp8 Linear mode (the loader then calls enable_stacked_cfg(fp8_linear=True)); --lora here is fused into the weights and works; unfused hot-loaded "
@@ -82,9 +87,11 @@ def main():
     a = ap.parse_args()
     if a.stacked_cfg_periodic_gate and not a.stacked_cfg:
         ap.error("--stacked-cfg-periodic-gate is a form of --stacked-cfg")
-    pv8 = a.pv8_attention or a.cross8_attention or a.smooth_v
-    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or pv8, pv8, a.cross8_attention, a.stacked_cfg,
-                          a.stacked_cfg_periodic_gate, **({"smooth_v": True} if a.smooth_v else {}))
+    cross8 = a.cross8_attention or a.smooth_v_cross
+    pv8 = a.pv8_attention or cross8 or a.smooth_v
+    pipe = build_pipeline(a.weights, a.tokenizer, a.lora, a.fp8, a.qk8_attention or pv8, pv8, cross8, a.stacked_cfg,
+                          a.stacked_cfg_periodic_gate, **({"smooth_v": True} if a.smooth_v else {}),
+                          **({"smooth_v_cross": True} if a.smooth_v_cross else {}))
     image = Image.open(a.image).convert("RGB").resize((832, 480))
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     video = pipe(prompt=a.prompt, negative_prompt=NEGATIVE, input_image=image, num_frames=81, seed=1, tiled=True, cfg_merge=a.stacked_cfg)

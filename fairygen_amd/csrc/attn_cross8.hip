@@ -17,9 +17,15 @@
 //     ring, no per-tile load, no further barrier, nothing waits on another workgroup and there are no atomics;
 //   * per tile and wave the step of the template: the 4 MFMAs of S^T(t+1) under the exponentials of tile t, then the 4 of O^T(t).
 // LDS: 256 * Nkp bytes (Nkp = Nkv rounded up to whole tiles) and nothing else: P stays in registers.
+//
+// The smoothed-V forms (fg_attn_fwd_cross8s_bf16 / _b, include/fairygen_hip_cross8s.h; DESIGN §5 "e4m3 cross-attention with smoothed V")
+// compile the same body with SMV: v8t / sv are those of fg_attn_quant_vt_smooth_bf16 (v minus its key mean), and the epilogue adds the mean
+// mu (H, 128) back in fp32 before the one rounding to bf16, as attn_fwd_pv8s_kernel does, whose bits they give.  mu is read from global
+// memory there: at 640 keys the tiles fill the LDS.
 #include "common.h"
 #include "../../include/fairygen_hip_cross8.h"
 #include "../../include/fairygen_hip_batch8.h"
+#include "../../include/fairygen_hip_cross8s.h"
 #include "attn_qk8_quant.h"
 #include "attn_pv8_parts.h"
 #include <math.h>
@@ -83,7 +89,19 @@ struct Cross8Params {
 
 // Workgroup h * G + g: head h, query blocks g, g + G, ..  Lane (r, hh) of wave w owns query row 256 qb + 32 w + r of its block, as in
 // attn_fwd_kernel<true, true>; the operand maps of the two MFMAs are described there.
+// (the body is one text for this form and the smoothed-V form; FG_CROSS8_NO_SMV names what only the other form reads)
+#define FG_CROSS8_NO_SMV            \
+    constexpr bool SMV = false;     \
+    const float* const mu = nullptr
 __global__ __launch_bounds__(512, 2) void attn_cross8_kernel(const Cross8Params P) {
+    FG_CROSS8_NO_SMV;
+#include "attn_cross8_body.inc"
+}
+
+// fg_attn_fwd_cross8s_bf16: attn_cross8_kernel with the key mean of V added in the epilogue; mu is an argument of its own, so that
+// Cross8Params and the kernels that take it stay what they are.
+__global__ __launch_bounds__(512, 2) void attn_cross8s_kernel(const Cross8Params P, const float* __restrict__ mu) {
+    constexpr bool SMV = true;
 #include "attn_cross8_body.inc"
 }
 
@@ -100,6 +118,20 @@ __global__ __launch_bounds__(512, 2) void attn_cross8_b_kernel(const Cross8Param
     Cross8Params Pe = PB.p;
     Pe.q8 += b * PB.bs_q8; Pe.k8 += b * PB.bs_k8; Pe.sq += b * PB.bs_sq; Pe.sk += b * PB.bs_sk;
     Pe.v8t += b * PB.bs_v8t; Pe.sv += b * PB.bs_sv; Pe.out += b * PB.bs_out;
+    const Cross8Params P = Pe;
+    FG_CROSS8_NO_SMV;
+#include "attn_cross8_body.inc"
+}
+#undef FG_CROSS8_NO_SMV
+
+// fg_attn_fwd_cross8s_bf16_b: bs_mu counts floats
+__global__ __launch_bounds__(512, 2) void attn_cross8s_b_kernel(const Cross8ParamsB PB, const float* __restrict__ mu, int64_t bs_mu) {
+    constexpr bool SMV = true;
+    const int64_t b = blockIdx.y;
+    Cross8Params Pe = PB.p;
+    Pe.q8 += b * PB.bs_q8; Pe.k8 += b * PB.bs_k8; Pe.sq += b * PB.bs_sq; Pe.sk += b * PB.bs_sk;
+    Pe.v8t += b * PB.bs_v8t; Pe.sv += b * PB.bs_sv; Pe.out += b * PB.bs_out;
+    mu += b * bs_mu;
     const Cross8Params P = Pe;
 #include "attn_cross8_body.inc"
 }
@@ -189,4 +221,81 @@ extern "C" int fg_attn_fwd_cross8_bf16_b(const void* q8, int64_t bs_q8, const vo
     PB.bs_q8 = bs_q8; PB.bs_k8 = bs_k8; PB.bs_sq = bs_sq; PB.bs_sk = bs_sk; PB.bs_v8t = bs_v8t; PB.bs_sv = bs_sv; PB.bs_out = bs_out;
     hipLaunchKernelGGL(attn_cross8_b_kernel, dim3((unsigned)(H * G), (unsigned)B), dim3(512), (size_t)(2 * kD * nkp), (hipStream_t)stream, PB);
     return fg_launch_status("fg_attn_fwd_cross8_bf16_b");
+}
+
+// ---- the smoothed-V forms (include/fairygen_hip_cross8s.h): the two entry points above on the v8t, sv and mu of the smoothing V producer
+// (include/fairygen_hip_smoothv.h); the same checks, the same grid, the key mean added where an output row is rounded.
+extern "C" int fg_attn_cross8s_version(void) { return 1; }
+
+extern "C" int fg_attn_fwd_cross8s_bf16(const void* q8, const void* k8, const float* sq, const float* sk, const void* v8t, const float* sv,
+                                        const float* mu, void* out, int64_t Nq, int64_t Nkv, int H, int D, float scale, fg_stream_t stream) {
+    FG_CHECK_ARG(q8 && k8 && sq && sk && v8t && sv && out, "fg_attn_fwd_cross8s_bf16: null pointer");
+    FG_CHECK_ARG(mu && FG_ALIGNED16(mu), "fg_attn_fwd_cross8s_bf16: mu must be a 16-byte aligned pointer to H*128 floats");
+    FG_CHECK_ARG(D == kD, "fg_attn_fwd_cross8s_bf16: only head_dim 128 is supported (got %d)", D);
+    FG_CHECK_ARG(H > 0 && Nq > 0, "fg_attn_fwd_cross8s_bf16: H, Nq must be positive");
+    FG_CHECK_ARG(Nkv >= 1 && Nkv <= kMaxKv, "fg_attn_fwd_cross8s_bf16: Nkv must be in 1..%d, the keys whose K8 and V8^T fit the LDS (got %lld)",
+                 kMaxKv, (long long)Nkv);
+    FG_CHECK_ARG(scale > 0.f, "fg_attn_fwd_cross8s_bf16: scale must be positive");
+    const int64_t hd = (int64_t)H * D, nkp = (Nkv + kTileKeys - 1) / kTileKeys * kTileKeys, nqb = (Nq + kBM - 1) / kBM;
+    FG_CHECK_ARG(FG_ALIGNED16(q8) && FG_ALIGNED16(k8) && FG_ALIGNED16(v8t) && FG_ALIGNED16(sv) && FG_ALIGNED16(out) &&
+                     (((uintptr_t)sq | (uintptr_t)sk) & 3) == 0,
+                 "fg_attn_fwd_cross8s_bf16: pointers must be 16-byte aligned (sq, sk: 4)");
+    FG_CHECK_ARG(Nq * hd * 2 < (1ll << 32), "fg_attn_fwd_cross8s_bf16: O must span < 4 GiB");
+    const int cus = device_cus();
+    const int64_t per_head = cus / H > 1 ? cus / H : 1;
+    const int64_t G = nqb < per_head ? nqb : per_head;      // a function of Nq, H and the device only
+    FG_CHECK_ARG((int64_t)H * G < (1ll << 30), "fg_attn_fwd_cross8s_bf16: grid too large");
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_cross8s_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
+    FG_CHECK_ARG(attr == hipSuccess, "fg_attn_fwd_cross8s_bf16: cannot reserve 160 KiB of LDS: %s", hipGetErrorString(attr));
+    Cross8Params P{};
+    P.q8 = (const uint8_t*)q8; P.k8 = (const uint8_t*)k8; P.sq = sq; P.sk = sk; P.v8t = (const uint8_t*)v8t; P.sv = sv;
+    P.out = (bf16*)out;
+    P.Nq = Nq; P.Nkv = Nkv; P.Nkp = nkp;
+    P.H = H; P.G = (int)G; P.nqb = (int)nqb;
+    P.scale_log2e = scale * 1.4426950408889634f;
+    hipLaunchKernelGGL(attn_cross8s_kernel, dim3((unsigned)(H * G)), dim3(512), (size_t)(2 * kD * nkp), (hipStream_t)stream, P, mu);
+    return fg_launch_status("fg_attn_fwd_cross8s_bf16");
+}
+
+extern "C" int fg_attn_fwd_cross8s_bf16_b(const void* q8, int64_t bs_q8, const void* k8, int64_t bs_k8, const float* sq, int64_t bs_sq,
+                                          const float* sk, int64_t bs_sk, const void* v8t, int64_t bs_v8t, const float* sv, int64_t bs_sv,
+                                          const float* mu, int64_t bs_mu, void* out, int64_t bs_out, int B, int64_t Nq, int64_t Nkv, int H,
+                                          int D, float scale, fg_stream_t stream) {
+    FG_CHECK_ARG(q8 && k8 && sq && sk && v8t && sv && out, "fg_attn_fwd_cross8s_bf16_b: null pointer");
+    FG_CHECK_ARG(mu && FG_ALIGNED16(mu), "fg_attn_fwd_cross8s_bf16_b: mu must be a 16-byte aligned pointer to H*128 floats per element");
+    FG_CHECK_ARG(D == kD, "fg_attn_fwd_cross8s_bf16_b: only head_dim 128 is supported (got %d)", D);
+    FG_CHECK_ARG(B >= 1 && B <= 65535, "fg_attn_fwd_cross8s_bf16_b: B must be in 1..65535 (got %d)", B);
+    FG_CHECK_ARG(H > 0 && Nq > 0, "fg_attn_fwd_cross8s_bf16_b: H, Nq must be positive");
+    FG_CHECK_ARG(Nkv >= 1 && Nkv <= kMaxKv, "fg_attn_fwd_cross8s_bf16_b: Nkv must be in 1..%d, the keys whose K8 and V8^T fit the LDS (got %lld)",
+                 kMaxKv, (long long)Nkv);
+    FG_CHECK_ARG(scale > 0.f, "fg_attn_fwd_cross8s_bf16_b: scale must be positive");
+    const int64_t hd = (int64_t)H * D, nkp = (Nkv + kTileKeys - 1) / kTileKeys * kTileKeys, nqb = (Nq + kBM - 1) / kBM;
+    FG_CHECK_ARG(FG_ALIGNED16(q8) && FG_ALIGNED16(k8) && FG_ALIGNED16(v8t) && FG_ALIGNED16(sv) && FG_ALIGNED16(out) &&
+                     (((uintptr_t)sq | (uintptr_t)sk) & 3) == 0,
+                 "fg_attn_fwd_cross8s_bf16_b: pointers must be 16-byte aligned (sq, sk: 4)");
+    FG_CHECK_ARG(bs_q8 >= Nq * hd && bs_k8 >= Nkv * hd && bs_sq >= Nq * H && bs_sk >= H && bs_v8t >= hd * nkp && bs_sv >= hd && bs_mu >= hd &&
+                     bs_out >= Nq * hd,
+                 "fg_attn_fwd_cross8s_bf16_b: a batch stride is smaller than one element of its operand");
+    FG_CHECK_ARG(bs_q8 % 16 == 0 && bs_k8 % 16 == 0 && bs_v8t % 16 == 0 && bs_sv % 4 == 0 && bs_mu % 4 == 0 && bs_out % 8 == 0,
+                 "fg_attn_fwd_cross8s_bf16_b: batch strides must keep the 16-byte alignment of q8, k8, v8t, sv, mu and out");
+    FG_CHECK_ARG(Nq * hd * 2 < (1ll << 32), "fg_attn_fwd_cross8s_bf16_b: O of one batch element must span < 4 GiB");
+    const int cus = device_cus();
+    const int64_t per_head = cus / ((int64_t)B * H) > 1 ? cus / ((int64_t)B * H) : 1;
+    const int64_t G = nqb < per_head ? nqb : per_head;      // a function of Nq, B, H and the device only
+    FG_CHECK_ARG((int64_t)H * G < (1ll << 30), "fg_attn_fwd_cross8s_bf16_b: grid too large");
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_cross8s_b_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
+    FG_CHECK_ARG(attr == hipSuccess, "fg_attn_fwd_cross8s_bf16_b: cannot reserve 160 KiB of LDS: %s", hipGetErrorString(attr));
+    Cross8ParamsB PB{};
+    Cross8Params& P = PB.p;
+    P.q8 = (const uint8_t*)q8; P.k8 = (const uint8_t*)k8; P.sq = sq; P.sk = sk; P.v8t = (const uint8_t*)v8t; P.sv = sv;
+    P.out = (bf16*)out;
+    P.Nq = Nq; P.Nkv = Nkv; P.Nkp = nkp;
+    P.H = H; P.G = (int)G; P.nqb = (int)nqb;
+    P.scale_log2e = scale * 1.4426950408889634f;
+    PB.bs_q8 = bs_q8; PB.bs_k8 = bs_k8; PB.bs_sq = bs_sq; PB.bs_sk = bs_sk; PB.bs_v8t = bs_v8t; PB.bs_sv = bs_sv; PB.bs_out = bs_out;
+    hipLaunchKernelGGL(attn_cross8s_b_kernel, dim3((unsigned)(H * G), (unsigned)B), dim3(512), (size_t)(2 * kD * nkp), (hipStream_t)stream, PB,
+                       mu, bs_mu);
+    return fg_launch_status("fg_attn_fwd_cross8s_bf16_b");
 }

@@ -1,5 +1,6 @@
 // The body of attn_cross8_kernel (attn_cross8.hip, which describes it), included by that kernel and by its batched form
-// attn_cross8_b_kernel: both see `const Cross8Params P`.
+// attn_cross8_b_kernel, and by the smoothed-V forms of the two: all see `const Cross8Params P`, the constant SMV and (read only with SMV)
+// the pointer mu, and compile the same text.
     extern __shared__ __attribute__((aligned(16))) char smem[];      // K8 tiles 0 .. nt - 1, then V8^T tiles 0 .. nt - 1
     const int64_t Nq = P.Nq, Nkv = P.Nkv;
     const int H = P.H;
@@ -233,8 +234,14 @@
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     bf16x4 w4;
+                    if constexpr (SMV) {      // + the key mean of the channel: a product, then a sum, then the one rounding to bf16
+                        const f32x4 m4 = *reinterpret_cast<const f32x4*>(mu + (int64_t)h * kD + 32 * db + 8 * g + 4 * hh);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) w4[j] = (bf16)(o[db][4 * g + j] * inv);
+                        for (int j = 0; j < 4; ++j) w4[j] = (bf16)__fadd_rn(__fmul_rn(o[db][4 * g + j], inv), m4[j]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) w4[j] = (bf16)(o[db][4 * g + j] * inv);
+                    }
                     *reinterpret_cast<bf16x4*>(orow + 32 * db + 8 * g + 4 * hh) = w4;
                 }
         }

@@ -222,6 +222,19 @@ _SMOOTHV_QUERIES = {
 }
 SMOOTHV_SYMBOLS = sorted(list(_SMOOTHV_SIGNATURES) + list(_SMOOTHV_QUERIES))    # what include/fairygen_hip_smoothv.h declares
 
+# The extension of include/fairygen_hip_cross8s.h (the e4m3 cross-attention with V mean-smoothed: the operands of the smoothing V producer,
+# the key mean added where an output row is rounded): a twelfth pair.  The cross8 signatures with mu (and bs_mu) behind sv (and bs_sv).
+CROSS8S_ABI_VERSION = 1   # fg_attn_cross8s_version
+_CROSS8S_SIGNATURES = {
+    "fg_attn_fwd_cross8s_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp],
+    "fg_attn_fwd_cross8s_bf16_b": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _i64,
+                                   _i32, _i32, _f32, _vp],
+}
+_CROSS8S_QUERIES = {
+    "fg_attn_cross8s_version": (_i32, []),
+}
+CROSS8S_SYMBOLS = sorted(list(_CROSS8S_SIGNATURES) + list(_CROSS8S_QUERIES))    # what include/fairygen_hip_cross8s.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -244,12 +257,12 @@ def load():
     for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
             list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()) + \
             list(_ROWBATCH8_SIGNATURES.items()) + list(_LORABATCH_SIGNATURES.items()) + list(_UP2PHASE_SIGNATURES.items()) + \
-            list(_GATEGEMM_SIGNATURES.items()) + list(_SMOOTHV_SIGNATURES.items()):
+            list(_GATEGEMM_SIGNATURES.items()) + list(_SMOOTHV_SIGNATURES.items()) + list(_CROSS8S_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
             list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()) + \
             list(_ROWBATCH8_QUERIES.items()) + list(_LORABATCH_QUERIES.items()) + list(_UP2PHASE_QUERIES.items()) + \
-            list(_GATEGEMM_QUERIES.items()) + list(_SMOOTHV_QUERIES.items()):
+            list(_GATEGEMM_QUERIES.items()) + list(_SMOOTHV_QUERIES.items()) + list(_CROSS8S_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
@@ -262,7 +275,8 @@ def load():
                                  ("fg_dit_lorabatch_version", LORABATCH_ABI_VERSION, " (hot-loaded adapters on batches that share a table)"),
                                  ("fg_conv_up2phase_version", UP2PHASE_ABI_VERSION, " (upsample conv as four 2x2 phase convs)"),
                                  ("fg_gemm_gate_period_version", GATEGEMM_ABI_VERSION, " (gated GEMM store on batches that share a gate table)"),
-                                 ("fg_attn_smoothv_version", SMOOTHV_ABI_VERSION, " (e4m3 P V with mean-smoothed V)")):
+                                 ("fg_attn_smoothv_version", SMOOTHV_ABI_VERSION, " (e4m3 P V with mean-smoothed V)"),
+                                 ("fg_attn_cross8s_version", CROSS8S_ABI_VERSION, " (e4m3 cross-attention with mean-smoothed V)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -1122,13 +1136,22 @@ def attention_cross8_max_kv():
     return int(load().fg_attn_cross8_max_kv())
 
 
-def attention_cross8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None):
+def attention_cross8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None, mu=None):
     """fg_attn_fwd_cross8_bf16 (include/fairygen_hip_cross8.h) on attention_pv8_pre's operands, Nkv <= attention_cross8_max_kv(): every
     workgroup keeps its head's K8 and V8^T in LDS and walks many query blocks against them.  One launch, no workspace; the bits of
-    attention_pv8_pre without one.  With a leading batch dimension on all six: fg_attn_fwd_cross8_bf16_b, each workgroup on ONE element."""
+    attention_pv8_pre without one.  With a leading batch dimension on all six: fg_attn_fwd_cross8_bf16_b, each workgroup on ONE element.
+    mu: attn_quant_vt(smooth=True)'s key means of v, shaped like sv, with that call's v8t and sv — fg_attn_fwd_cross8s_bf16 / _b
+    (include/fairygen_hip_cross8s.h), which add them to the output rows: the bits of attention_pv8_pre(mu=) without a workspace."""
+    if mu is not None and (mu.shape != sv.shape or mu.dtype != torch.float32 or not mu.is_contiguous()):
+        raise HipLibraryError(f"attention_cross8_pre: mu must be fp32, contiguous and shaped like sv {tuple(sv.shape)}")
     if q8.dim() == 3:
         b, nq, hd, nkv, d = _batch8_check("attention_cross8_pre", q8, k8, sq, sk, v8t, sv, num_heads)
         out = torch.empty((b, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
+        if mu is not None:
+            _call("fg_attn_fwd_cross8s_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
+                  v8t.stride(0), _ptr(sv), hd, _ptr(mu), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d,
+                  float(d) ** -0.5 if scale is None else float(scale), _stream(q8))
+            return out
         _call("fg_attn_fwd_cross8_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
               v8t.stride(0), _ptr(sv), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d, float(d) ** -0.5 if scale is None else float(scale),
               _stream(q8))
@@ -1139,6 +1162,10 @@ def attention_cross8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=Non
             v8t.shape != (num_heads, d, (nkv + 63) // 64 * 64):
         raise HipLibraryError(f"attention_cross8_pre: k8, sq, sk, v8t, sv do not match q8 {tuple(q8.shape)} and {nkv} keys")
     out = torch.empty((1, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
+    if mu is not None:
+        _call("fg_attn_fwd_cross8s_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(mu), _ptr(out), nq, nkv, num_heads,
+              d, float(d) ** -0.5 if scale is None else float(scale), _stream(q8))
+        return out
     _call("fg_attn_fwd_cross8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
           float(d) ** -0.5 if scale is None else float(scale), _stream(q8))
     return out

@@ -42,6 +42,9 @@ class ModelConfig:
     # True (with attention_dtype and attention_pv_dtype): V of that P V product mean-smoothed (enable_qk8_attention(pv8=True, smooth_v=True);
     # include/fairygen_hip_smoothv.h); self-attention only, single-GPU layouts only
     attention_v_smoothing: bool = False
+    # True (with cross_attention_dtype): V of the e4m3 cross-attention mean-smoothed (enable_qk8_attention(pv8=True, cross=True,
+    # smooth_v_cross=True); include/fairygen_hip_cross8s.h); independent of attention_v_smoothing, single-GPU layouts only
+    cross_attention_v_smoothing: bool = False
     # True: a merged CFG call (pipe(..., cfg_merge=True)) runs both branches in ONE stacked forward of the DiT (WanModel.enable_stacked_cfg;
     # with an fp8 computation_dtype: enable_stacked_cfg(fp8_linear=True))
     stacked_cfg: bool = False
@@ -57,6 +60,9 @@ class ModelConfig:
         if self.attention_v_smoothing and (self.attention_dtype is None or self.attention_pv_dtype is None):
             raise ValueError("ModelConfig(attention_v_smoothing=True) smooths V of the 8-bit P V self-attention: it needs attention_dtype and "
                              "attention_pv_dtype (both torch.float8_e4m3fn)")
+        if self.cross_attention_v_smoothing and self.cross_attention_dtype != torch.float8_e4m3fn:
+            raise ValueError("ModelConfig(cross_attention_v_smoothing=True) smooths V of the 8-bit cross-attention: it needs "
+                             "cross_attention_dtype=torch.float8_e4m3fn")
         if self.stacked_cfg_hot_lora and not self.stacked_cfg:
             raise ValueError("ModelConfig(stacked_cfg_hot_lora=True) is a form of the stacked CFG forward: it needs stacked_cfg=True")
         if self.stacked_cfg_periodic_gate and not self.stacked_cfg:
@@ -78,8 +84,8 @@ class ModelConfig:
         return {k: getattr(self, k) for k in (
             "offload_device", "offload_dtype", "onload_device", "onload_dtype",
             "preparing_device", "preparing_dtype", "computation_device", "computation_dtype", "attention_dtype",
-            "attention_pv_dtype", "cross_attention_dtype", "attention_v_smoothing", "stacked_cfg", "stacked_cfg_hot_lora",
-            "stacked_cfg_periodic_gate")}
+            "attention_pv_dtype", "cross_attention_dtype", "attention_v_smoothing", "cross_attention_v_smoothing", "stacked_cfg",
+            "stacked_cfg_hot_lora", "stacked_cfg_periodic_gate")}
 
 
 # --------------------------------------------------------------------------------- state-dict files
@@ -251,6 +257,10 @@ class ModelPool:
             if smooth_v and (attn is None or attn_pv is None):
                 raise ValueError("attention_v_smoothing without attention_dtype and attention_pv_dtype: it is V of the 8-bit P V self-attention "
                                  "that is mean-smoothed (both torch.float8_e4m3fn)")
+            smooth_v_cross = bool(vram_config.get("cross_attention_v_smoothing"))
+            if smooth_v_cross and attn_cross is None:
+                raise ValueError("cross_attention_v_smoothing without cross_attention_dtype: it is V of the 8-bit cross-attention that is "
+                                 "mean-smoothed (torch.float8_e4m3fn)")
             if attn is not None:
                 if attn != torch.float8_e4m3fn:
                     raise NotImplementedError(f"attention_dtype={attn}: the 8-bit Q K^T self-attention is built for torch.float8_e4m3fn only")
@@ -259,7 +269,7 @@ class ModelPool:
                 model.enable_qk8_attention()
                 if attn_pv is not None:
                     # P V in e4m3 too; cross-attention and the mean-smoothed V if asked
-                    model.enable_qk8_attention(pv8=True, cross=attn_cross is not None, smooth_v=smooth_v)
+                    model.enable_qk8_attention(pv8=True, cross=attn_cross is not None, smooth_v=smooth_v, smooth_v_cross=smooth_v_cross)
                 model.qk8_fused_producer = True      # the operands from the RMSNorm+RoPE pass itself: the same bits, k read once
             if vram_config.get("stacked_cfg"):
                 if not hasattr(model, "enable_stacked_cfg"):

@@ -284,10 +284,15 @@ class _BlockLinears:
     def cross8_context(self, kvc, norm_k, num_heads):
         """The e4m3 operands of a block's context from its k | v rows (1, L, 2 C): (k8, sk, v8t, sv) — the RMSNorm pass of k that also leaves
         the key statistics, the key conversion behind it, and fg_attn_quant_vt_bf16 on v.  Once per denoise loop with a kv_cache, which
-        then holds these four in place of (k, v); the buffers are the binding's own allocations either way."""
+        then holds these four in place of (k, v); the buffers are the binding's own allocations either way.  With
+        enable_qk8_attention(smooth_v_cross=True) the V producer is the smoothing one (fg_attn_quant_vt_smooth_bf16) and the key means of v
+        follow as a fifth tensor: (k8, sk, v8t, sv, mu)."""
         c = kvc.shape[-1] // 2
         k, parts = hip.rmsnorm_rope_kstats(kvc[..., :c], norm_k.weight, num_heads, self.eps)
         k8, sk, _ = hip.attn_quant_k(k, parts, num_heads)
+        if self.model.smoothv_cross_attention:      # enable_qk8_attention(smooth_v_cross=True): v minus its key mean, and the mean
+            v8t, sv, _, mu = hip.attn_quant_vt(kvc[..., c:], num_heads, smooth=True)
+            return k8, sk, v8t, sv, mu
         v8t, sv, _ = hip.attn_quant_vt(kvc[..., c:], num_heads)
         return k8, sk, v8t, sv
 
@@ -593,6 +598,8 @@ class WanModel(nn.Module):
         self.qk8_sharded = False
         # ... and cross-attention in the e4m3 form too (enable_qk8_attention(pv8=True, cross=True)); False: cross-attention in bf16
         self.cross8_attention = False
+        # ... with V of the context mean-smoothed in it (enable_qk8_attention(pv8=True, cross=True, smooth_v_cross=True)); False: as it is
+        self.smoothv_cross_attention = False
         # a merged CFG call (cfg_merge=True) as ONE forward on x (2, N, dim) instead of two batch-1 forwards; see enable_stacked_cfg
         self.stacked_cfg = False
         # ... also when the blocks' Linears run in the fp8 mode (enable_stacked_cfg(fp8_linear=True)); False: that combination raises
@@ -637,7 +644,8 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ e4m3 Q K^T self-attention (models/wan_video_dit.py:48-52)
-    def enable_qk8_attention(self, flag=True, fused_producer=False, pv8=False, sharded=False, cross=False, smooth_v=False):
+    def enable_qk8_attention(self, flag=True, fused_producer=False, pv8=False, sharded=False, cross=False, smooth_v=False,
+                             smooth_v_cross=False):
         """Run self-attention of every block like the reference's flash_attention does when the sageattention package is present
         (sageattn(q, k, v)): Q K^T from e4m3 operands — K mean-smoothed with one scale per head, Q with one scale per row and head
         (fg_attn_quant_qk_bf16) — on fg_attn_fwd_qk8_bf16; softmax and P V as before, v in bf16.  Only the stock AttentionModule of
@@ -681,7 +689,14 @@ class WanModel(nn.Module):
         stacked CFG forward (the batched entry points).  It does NOT run on token shards, sharded=True or not: the mean spans every
         rank's keys and the statistics record of include/fairygen_hip_shard8.h carries no V sum — together with sharded=True it raises
         ValueError here, and an active shard raises NotImplementedError at the forward.  With cross=True it smooths self-attention
-        only: the e4m3 cross-attention keeps its unsmoothed V8^T."""
+        only: the e4m3 cross-attention has a switch of its own (below).
+        smooth_v_cross: off by default, independent of smooth_v.  The same smoothing for the e4m3 cross-attention
+        (include/fairygen_hip_cross8s.h): the context is zeroed behind the prompt's length and the k / v Linears act row by row, so most
+        of its 512 keys carry one V row, which the unsmoothed recipe returns scaled by P's rounding defect.  With it a block's context
+        goes through fg_attn_quant_vt_smooth_bf16, the kv_cache holds (k8, sk, v8t, sv, mu), still quantised once per denoise loop, and
+        fg_attn_fwd_cross8s_bf16 (batched: _b, the stacked CFG forward) takes the place of fg_attn_fwd_cross8_bf16.  It needs flag, pv8
+        and cross (ValueError without, and nothing changes); composes with what cross composes with, graph=True included (the context
+        is quantised in the eager first step, replays only read it); an active token shard raises as for cross."""
         if pv8 and not flag:
             raise ValueError("enable_qk8_attention(pv8=True) needs the e4m3 Q K^T mode on (flag=True)")
         if sharded and not flag:
@@ -694,12 +709,16 @@ class WanModel(nn.Module):
         if smooth_v and sharded:
             raise ValueError("enable_qk8_attention(smooth_v=True, sharded=True): the key mean of V spans every rank's keys and the statistics "
                              "record of the sharded mode (include/fairygen_hip_shard8.h) has no V sum; run token shards without smooth_v")
+        if smooth_v_cross and not (flag and pv8 and cross):
+            raise ValueError("enable_qk8_attention(smooth_v_cross=True) needs the e4m3 cross-attention on (flag=True, pv8=True, cross=True): "
+                             "it is V of that product that is mean-smoothed")
         self.qk8_attention = bool(flag)
         self.qk8_fused_producer = bool(flag) and bool(fused_producer)
         self.pv8_attention = bool(flag) and bool(pv8)
         self.qk8_sharded = bool(flag) and bool(sharded)
         self.cross8_attention = bool(flag) and bool(pv8) and bool(cross)
         self.smoothv_attention = bool(flag) and bool(pv8) and bool(smooth_v)
+        self.smoothv_cross_attention = self.cross8_attention and bool(smooth_v_cross)
         return self
 
     # ------------------------------------------------------------------ the stacked CFG forward
@@ -1146,8 +1165,8 @@ class WanModel(nn.Module):
                     ops8 = lin.cross8_context(kvc, ca.norm_k, nh)
                     if kv_cache is not None:
                         kv_cache[i] = ops8
-                k8c, skc, v8tc, svc = ops8
-                ac = hip.attention_cross8_pre(q8c, k8c, sqc, skc, v8tc, svc, nh)
+                k8c, skc, v8tc, svc, *muc = ops8      # smooth_v_cross=True: the key means of v behind the four
+                ac = hip.attention_cross8_pre(q8c, k8c, sqc, skc, v8tc, svc, nh, mu=muc[0] if muc else None)
             else:
                 qc = hip.rmsnorm_rope(qc, ca.norm_q.weight, nh, eps)
                 if kv_cache is not None and i in kv_cache:

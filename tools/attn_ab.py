@@ -108,19 +108,40 @@ def shard8(a):
         print(f"{name:24s} {med:8.3f} ms" + (f"   {mbytes / med:7.0f} GB/s ({mbytes:.1f} MB read + written)" if mbytes else ""), flush=True)
 
 
+def padded_context_v(l_text, l=512, heads=24, seed=180, device="cuda"):
+    """V of a text context as the pipeline leaves it (the context rows behind the prompt are zeroed and the v Linear acts row by row):
+    l_text rows ~ N(0, 1), the other l - l_text rows ONE common row ~ 4 N(0, 1) per channel.  (l, heads * 128) bf16; the generator of
+    tests/test_attention_cross8s.py."""
+    c = heads * 128
+    rows = torch.randn((l_text, c), generator=torch.Generator("cpu").manual_seed(seed), dtype=torch.float32).to(torch.bfloat16)
+    pad = (4.0 * torch.randn((1, c), generator=torch.Generator("cpu").manual_seed(seed + 1), dtype=torch.float32)).to(torch.bfloat16)
+    return torch.cat([rows, pad.expand(l - l_text, c)], dim=0).contiguous().to(device)
+
+
 def cross8(a):
     """--cross8: cross-attention from the q Linear's output to the attention output, 24 heads over a context of --nkv rows (512), in ONE
     process with alternating launches, at every --cross8-nq: (a) 'chain-bf16' = rmsnorm_rope + fg_attn_fwd_bf16, (b) 'chain-pv8' = the q8
     producer (fg_rmsnorm_rope_q8_bf16 without a table) + fg_attn_fwd_pv8_bf16, (c) 'chain-cross8' = the q8 producer + fg_attn_fwd_cross8_bf16
     (K8 and V8^T resident in LDS); the three attention launches alone ('attn-*'); and 'quant-context' = the quantisation of a block's
     context (key norm with statistics, fg_attn_quant_k_bf16, fg_attn_quant_vt_bf16), paid once per denoise loop and timed on its own.
-    (b) and (c) are first checked to be the same bytes."""
+    (b) and (c) are first checked to be the same bytes.
+    --smooth-v-cross adds a third e4m3 leg on a context whose V is padded_context_v(--l-text, nkv): (d) 'chain-cross8s' = the q8 producer +
+    fg_attn_fwd_cross8s_bf16 on the operands of the smoothing V producer (include/fairygen_hip_cross8s.h), 'attn-cross8s' and
+    'quant-context-s' (fg_attn_quant_vt_smooth_bf16 in place of fg_attn_quant_vt_bf16); (d) is checked against fg_attn_fwd_pv8s_bf16."""
     dev, heads, nkv = "cuda", a.heads, a.nkv
     c = heads * 128
     g = torch.Generator(dev).manual_seed(0)
     rnd = lambda *s: torch.randn(s, generator=g, device=dev, dtype=torch.float32).to(torch.bfloat16)  # noqa: E731
     wq, wk = (1 + 0.1 * rnd(c).float()).to(torch.bfloat16), (1 + 0.1 * rnd(c).float()).to(torch.bfloat16)
     kvc = rnd(1, nkv, 2 * c)
+    if a.smooth_v_cross:
+        kvc[0, :, c:] = padded_context_v(min(a.l_text, nkv), nkv, heads, device=dev)
+
+    def quant_context_s():
+        k, parts = hip.rmsnorm_rope_kstats(kvc[..., :c], wk, heads, 1e-6)
+        k8, sk, _ = hip.attn_quant_k(k, parts, heads)
+        v8t, sv, _, mu = hip.attn_quant_vt(kvc[..., c:], heads, smooth=True)
+        return k8, sk, v8t, sv, mu
 
     def quant_context():
         k, parts = hip.rmsnorm_rope_kstats(kvc[..., :c], wk, heads, 1e-6)
@@ -129,6 +150,7 @@ def cross8(a):
         return k8, sk, v8t, sv
     k8, sk, v8t, sv = quant_context()
     k16, v16 = hip.rmsnorm_rope(kvc[..., :c], wk, heads, 1e-6), kvc[..., c:]
+    ops_s = quant_context_s() if a.smooth_v_cross else None
     for nq in (int(x) for x in a.cross8_nq.split(",")):
         x = rnd(1, nq, c)
         q16, o16, o8, oc = (torch.empty((1, nq, c), dtype=torch.bfloat16, device=dev) for _ in range(4))
@@ -151,10 +173,21 @@ def cross8(a):
             hip.attention_cross8_pre(q8, k8, sq, sk, v8t, sv, heads, out=oc)
         fns = [("chain-bf16", lambda: (prod16(), attn16())), ("chain-pv8", lambda: (prod8(), attn8())), ("chain-cross8", lambda: (prod8(), attnc())),
                ("attn-bf16", attn16), ("attn-pv8", attn8), ("attn-cross8", attnc), ("quant-context", quant_context)]
+        if a.smooth_v_cross:
+            os_ = torch.empty_like(oc)
+
+            def attns():
+                hip.attention_cross8_pre(q8, ops_s[0], sq, ops_s[1], ops_s[2], ops_s[3], heads, out=os_, mu=ops_s[4])
+            fns += [("chain-cross8s", lambda: (prod8(), attns())), ("attn-cross8s", attns), ("quant-context-s", quant_context_s)]
         for _, fn in fns:
             for _ in range(2):
                 fn()
         torch.cuda.synchronize()
+        if a.smooth_v_cross:
+            same = torch.equal(os_, hip.attention_pv8_pre(q8, ops_s[0], sq, ops_s[1], ops_s[2], ops_s[3], heads, workspace=None, mu=ops_s[4]))
+            e_s, e_c = (os_.float() - o16.float()).abs().mean().item(), (oc.float() - o16.float()).abs().mean().item()
+            print(f"check nq={nq}: fg_attn_fwd_cross8s_bf16 and fg_attn_fwd_pv8s_bf16 {'are the same bytes  OK' if same else 'DIFFER  FAIL'}; padded "
+                  f"context (L_text {min(a.l_text, nkv)} of {nkv}): mean |out - bf16 chain| cross8 {e_c:.6f}, cross8s {e_s:.6f}", flush=True)
         err = (oc.float() - o16.float()).abs()
         print(f"check nq={nq}: fg_attn_fwd_cross8_bf16 and fg_attn_fwd_pv8_bf16 {'are the same bytes  OK' if torch.equal(oc, o8) else 'DIFFER  FAIL'}; "
               f"against the bf16 chain max {err.max().item():.5f}, mean {err.mean().item():.6f}", flush=True)
@@ -183,6 +216,10 @@ def main():
     ap.add_argument("--cross8", action="store_true", help="time cross-attention over --nkv context rows (use --nkv 512) from the q Linear's output "
                     "to the attention output: bf16, the e4m3 kernel of self-attention, and the kernel that keeps K8 / V8^T in LDS; nothing else runs")
     ap.add_argument("--cross8-nq", default="27280,8190")
+    ap.add_argument("--smooth-v-cross", action="store_true", help="with --cross8: V of the context is padded_context_v(--l-text, nkv), and a third "
+                    "e4m3 leg runs in the same rounds: 'chain-cross8s' / 'attn-cross8s' = fg_attn_fwd_cross8s_bf16 on mean-smoothed V "
+                    "(include/fairygen_hip_cross8s.h), 'quant-context-s' = the context quantisation with the smoothing V producer")
+    ap.add_argument("--l-text", type=int, default=40, help="with --smooth-v-cross: the context rows that are text; the others are one common row")
     ap.add_argument("--shard8", action="store_true", help="time one rank's attention chain of the K / V all-gather layout (--world ranks, nkv keys "
                     "in all) for bf16, qk8-sharded and pv8-sharded, and the new passes alone; nothing else runs")
     ap.add_argument("--world", type=int, default=8)
@@ -212,7 +249,7 @@ def main():
     a = ap.parse_args()
     if a.shard8:
         return shard8(a)
-    if a.cross8:
+    if a.cross8 or a.smooth_v_cross:
         return cross8(a)
     a.pv8 = a.pv8 or a.smooth_v
     a.qk8 = a.qk8 or a.pv8

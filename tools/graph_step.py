@@ -78,7 +78,7 @@ def main():
     ap.add_argument("--attn", default="bf16", help="self-attention forms, legs in this order: bf16, qk8 (enable_qk8_attention(), the two-step "
                     "producers), qk8-fused (fused_producer=True), pv8 and pv8-fused (the same with pv8=True: e4m3 P V too), cross8 and "
                     "cross8-fused (pv8 with cross=True: cross-attention in the e4m3 form too), pv8s and pv8s-fused (pv8 with smooth_v=True: V "
-                    "mean-smoothed); the latents of a -fused leg are compared with "
+                    "mean-smoothed), cross8s and cross8s-fused (cross8 with smooth_v_cross=True: V of the context mean-smoothed); the latents of a -fused leg are compared with "
                     "the first leg's of its form")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=10)
@@ -96,7 +96,8 @@ def main():
             first = {}
             for attn, mode in ((at, md) for at in a.attn.split(",") for md in a.modes.split(",")):
                 pipe.dit.enable_qk8_attention(attn != "bf16", fused_producer=attn.endswith("-fused"), pv8=attn.startswith(("pv8", "cross8")),
-                                              cross=attn.startswith("cross8"), smooth_v=attn.split("-")[0] == "pv8s")
+                                              cross=attn.startswith("cross8"), smooth_v=attn.split("-")[0] == "pv8s",
+                                              smooth_v_cross=attn.split("-")[0] == "cross8s")
                 ms, out = leg(pipe, SIZES[size], mode, a.warmup, a.steps, dev)
                 ref = first.setdefault(attn.split("-")[0], out)
                 n = SIZES[size][2] * (SIZES[size][3] // 2) * (SIZES[size][4] // 2)
