@@ -925,6 +925,20 @@ def _attn_ws(device, b, nq, nkv, num_heads, workspace, per_element=False):
     return ws, need
 
 
+def _ws_args(ws, need):
+    """The (scratch pointer, bytes) arguments of an attention launch from _attn_ws's pair: no pointer where the plan wants none."""
+    return _ptr(ws) if need > 0 else None, need
+
+
+def _softmax_scale(d, scale):
+    return float(d) ** -0.5 if scale is None else float(scale)
+
+
+def _flat(pairs, strides):
+    """The C arguments of (tensor, element stride) pairs: the pointers, each followed by its stride for a batched (_b) entry point."""
+    return [a for t, s in pairs for a in ((_ptr(t), s) if strides else (_ptr(t),))]
+
+
 def pow2_softmax_scale(head_dim):
     """(scale', f) with scale' * log2(e) = the power of two next to head_dim^-0.5 * log2(e) and f = their ratio (1.0201 for d = 128):
     softmax(scale' (f q) k^T) = softmax(q k^T / sqrt(d)), and fg_attn_fwd_bf16 runs its pre-multiplied form exactly for scale'."""
@@ -943,48 +957,49 @@ def attention(q, k, v, num_heads, out=None, scale=None, workspace=None):
     nkv = k.shape[1]
     d = hd // num_heads
     out = torch.empty((b, nq, hd), dtype=q.dtype, device=q.device) if out is None else out
-    ws, need = _attn_ws(q.device, b, nq, nkv, num_heads, workspace)
-    _call("fg_attn_fwd_bf16", _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(out), b, nq, nkv, num_heads, d,
-          float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q))
+    _call("fg_attn_fwd_bf16", _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(out), b, nq, nkv, num_heads, d, _softmax_scale(d, scale),
+          *_ws_args(*_attn_ws(q.device, b, nq, nkv, num_heads, workspace)), _stream(q))
     return out
+
+
+# The e4m3 attention wrappers below take one element — operands without a batch dimension, activations (1, N, H*D) — or, with a leading
+# batch dimension B > 1 on all of them, a batch on the _b entry points (include/fairygen_hip_batch8.h).  `lead` is that leading shape,
+# (B,) or (); one body serves both.
+def _lead(b):
+    return (b,) if b > 1 else ()
 
 
 def attention_qk8_scratch(n, num_heads, head_dim, device, batch=1):
     """The buffers fg_attn_quant_qk_bf16 fills for (n, num_heads * head_dim) q and k: (q8, k8, sq, sk, kbar scratch).  batch > 1: the
     same five with a leading batch dimension, for the batched entry points (include/fairygen_hip_batch8.h)."""
-    hd = num_heads * head_dim
-    if batch > 1:
-        f8, f32 = torch.float8_e4m3fn, torch.float32
-        return (torch.empty((batch, n, hd), dtype=f8, device=device), torch.empty((batch, n, hd), dtype=f8, device=device),
-                torch.empty((batch, n, num_heads), dtype=f32, device=device), torch.empty((batch, num_heads), dtype=f32, device=device),
-                torch.empty((batch, hd), dtype=f32, device=device))
-    return (torch.empty((n, hd), dtype=torch.float8_e4m3fn, device=device), torch.empty((n, hd), dtype=torch.float8_e4m3fn, device=device),
-            torch.empty((n, num_heads), dtype=torch.float32, device=device), torch.empty(num_heads, dtype=torch.float32, device=device),
-            torch.empty(hd, dtype=torch.float32, device=device))
+    hd, lead = num_heads * head_dim, _lead(batch)
+    return tuple(torch.empty(lead + shape, dtype=dtype, device=device) for shape, dtype in (
+        ((n, hd), torch.float8_e4m3fn), ((n, hd), torch.float8_e4m3fn), ((n, num_heads), torch.float32), ((num_heads,), torch.float32),
+        ((hd,), torch.float32)))
 
 
 def attn_quant_qk(q, k, num_heads, bufs=None):
     """The e4m3 operands of attention_qk8 from q, k (1, N, H*128) bf16 (column slices with a leading dimension are fine): K mean-smoothed with
-    one scale per head, Q with one scale per row and head (include/fairygen_hip.h).  bufs: attention_qk8_scratch's tuple, else allocated."""
+    one scale per head, Q with one scale per row and head (include/fairygen_hip.h).  bufs: attention_qk8_scratch's tuple, else allocated.
+    A batch (B, N, H*128): fg_attn_quant_qk_bf16_b, every statistic per element."""
     ldq, ldk = _ld_rows(q, "q"), _ld_rows(k, "k")
     b, n, hd = q.shape
-    if b > 1 and k.shape == q.shape:      # a batch: fg_attn_quant_qk_bf16_b, every statistic per element
-        bufs = attention_qk8_scratch(n, num_heads, hd // num_heads, q.device, b) if bufs is None else bufs
-        q8, k8, sq, sk, kbar = bufs
-        if q8.shape != (b, n, hd) or k8.shape != (b, n, hd) or sq.shape != (b, n, num_heads) or sk.shape != (b, num_heads) or \
-                kbar.shape != (b, hd) or not all(t.is_contiguous() for t in bufs):
-            raise HipLibraryError("attn_quant_qk: bufs do not match (B, N, H*D)")
-        _call("fg_attn_quant_qk_bf16_b", _ptr(q), ldq, q.stride(0), _ptr(k), ldk, k.stride(0), _ptr(q8), n * hd, _ptr(k8), n * hd, _ptr(sq),
-              n * num_heads, _ptr(sk), num_heads, _ptr(kbar), hd * 4, hd * 4, b, n, num_heads, hd // num_heads, _stream(q))
-        return bufs
-    if b != 1 or k.shape != q.shape:
+    if b < 1 or k.shape != q.shape:
         raise HipLibraryError(f"attn_quant_qk: q and k must both be (1, N, H*D), got {tuple(q.shape)} and {tuple(k.shape)}")
-    bufs = attention_qk8_scratch(n, num_heads, hd // num_heads, q.device) if bufs is None else bufs
+    lead = _lead(b)
+    bufs = attention_qk8_scratch(n, num_heads, hd // num_heads, q.device, b) if bufs is None else bufs
     q8, k8, sq, sk, kbar = bufs
-    if q8.shape != (n, hd) or k8.shape != (n, hd) or sq.shape != (n, num_heads) or sk.numel() != num_heads or kbar.numel() < hd:
-        raise HipLibraryError("attn_quant_qk: bufs do not match (N, H*D)")
-    _call("fg_attn_quant_qk_bf16", _ptr(q), ldq, _ptr(k), ldk, _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(kbar), kbar.numel() * 4, n,
-          num_heads, hd // num_heads, _stream(q))
+    ok = q8.shape == lead + (n, hd) and k8.shape == lead + (n, hd) and sq.shape == lead + (n, num_heads)
+    if lead:
+        ok = ok and sk.shape == (b, num_heads) and kbar.shape == (b, hd) and all(t.is_contiguous() for t in bufs)
+        args = (_ptr(q), ldq, q.stride(0), _ptr(k), ldk, k.stride(0), *_flat([(q8, n * hd), (k8, n * hd), (sq, n * num_heads), (sk, num_heads)], True),
+                _ptr(kbar), hd * 4, hd * 4, b)
+    else:      # one element: sk and the key-mean scratch go by size, the scratch may be larger
+        ok = ok and sk.numel() == num_heads and kbar.numel() >= hd
+        args = (_ptr(q), ldq, _ptr(k), ldk, _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(kbar), kbar.numel() * 4)
+    if not ok:
+        raise HipLibraryError(f"attn_quant_qk: bufs do not match {'(B, N, H*D)' if lead else '(N, H*D)'}")
+    _call("fg_attn_quant_qk_bf16_b" if lead else "fg_attn_quant_qk_bf16", *args, n, num_heads, hd // num_heads, _stream(q))
     return bufs
 
 
@@ -997,7 +1012,7 @@ def attention_pv8_scratch(n, num_heads, head_dim, device, batch=1, smooth=False)
     need = (load().fg_attn_smoothv_scratch_bytes if smooth else load().fg_attn_pv8_scratch_bytes)(n, num_heads)
     if need < 0:
         raise HipLibraryError(f"attention_pv8_scratch: {load().fg_last_error().decode()}")
-    lead = (batch,) if batch > 1 else ()
+    lead = _lead(batch)
     return (torch.empty(lead + (num_heads, head_dim, (n + 63) // 64 * 64), dtype=torch.float8_e4m3fn, device=device),
             torch.empty(lead + (num_heads, head_dim), dtype=torch.float32, device=device),
             torch.empty(lead + (need,), dtype=torch.uint8, device=device)) + \
@@ -1013,32 +1028,18 @@ def attn_quant_vt(v, num_heads, bufs=None, smooth=False):
         raise HipLibraryError(f"attn_quant_vt: bufs must be attention_pv8_scratch(smooth={bool(smooth)})'s")
     ldv = _ld_rows(v, "v")
     b, n, hd = v.shape
-    if b > 1:      # a batch: fg_attn_quant_vt_bf16_b, sv per element
-        bufs = attention_pv8_scratch(n, num_heads, hd // num_heads, v.device, b, smooth) if bufs is None else bufs
-        v8t, sv, scratch = bufs[:3]
-        nkp = (n + 63) // 64 * 64
-        if v8t.shape != (b, num_heads, hd // num_heads, nkp) or sv.shape != (b, num_heads, hd // num_heads) or scratch.dim() != 2 or \
-                scratch.shape[0] != b or not all(t.is_contiguous() for t in bufs) or (smooth and bufs[3].shape != sv.shape):
-            raise HipLibraryError("attn_quant_vt: bufs do not match (B, N, H*D)")
-        if smooth:
-            _call("fg_attn_quant_vt_smooth_bf16_b", _ptr(v), ldv, v.stride(0), _ptr(v8t), hd * nkp, _ptr(sv), hd, _ptr(bufs[3]), hd,
-                  _ptr(scratch), scratch.shape[1], scratch.stride(0), b, n, num_heads, hd // num_heads, _stream(v))
-            return bufs
-        _call("fg_attn_quant_vt_bf16_b", _ptr(v), ldv, v.stride(0), _ptr(v8t), hd * nkp, _ptr(sv), hd, _ptr(scratch), scratch.shape[1],
-              scratch.stride(0), b, n, num_heads, hd // num_heads, _stream(v))
-        return bufs
-    if b != 1:
+    if b < 1:
         raise HipLibraryError(f"attn_quant_vt: v must be (1, N, H*D), got {tuple(v.shape)}")
-    bufs = attention_pv8_scratch(n, num_heads, hd // num_heads, v.device, 1, smooth) if bufs is None else bufs
+    lead, d, nkp = _lead(b), hd // num_heads, (n + 63) // 64 * 64      # a batch: the _b entry points, sv (and mu) per element
+    bufs = attention_pv8_scratch(n, num_heads, d, v.device, b, smooth) if bufs is None else bufs
     v8t, sv, scratch = bufs[:3]
-    if v8t.shape != (num_heads, hd // num_heads, (n + 63) // 64 * 64) or sv.shape != (num_heads, hd // num_heads) or not v8t.is_contiguous() or \
-            (smooth and (bufs[3].shape != sv.shape or not bufs[3].is_contiguous())):
-        raise HipLibraryError("attn_quant_vt: bufs do not match (N, H*D)")
-    if smooth:
-        _call("fg_attn_quant_vt_smooth_bf16", _ptr(v), ldv, _ptr(v8t), _ptr(sv), _ptr(bufs[3]), _ptr(scratch), scratch.numel(), n, num_heads,
-              hd // num_heads, _stream(v))
-        return bufs
-    _call("fg_attn_quant_vt_bf16", _ptr(v), ldv, _ptr(v8t), _ptr(sv), _ptr(scratch), scratch.numel(), n, num_heads, hd // num_heads, _stream(v))
+    mu = tuple(bufs[3:])
+    if v8t.shape != lead + (num_heads, d, nkp) or any(t.shape != lead + (num_heads, d) for t in (sv,) + mu) or \
+            (lead and (scratch.dim() != 2 or scratch.shape[0] != b)) or not all(t.is_contiguous() for t in (bufs if lead else (v8t,) + mu)):
+        raise HipLibraryError(f"attn_quant_vt: bufs do not match {'(B, N, H*D)' if lead else '(N, H*D)'}")
+    outs = _flat([(v8t, hd * nkp), (sv, hd)] + [(m, hd) for m in mu], lead)
+    _call("fg_attn_quant_vt" + ("_smooth" if smooth else "") + "_bf16" + ("_b" if lead else ""), _ptr(v), ldv, *((v.stride(0),) if lead else ()),
+          *outs, _ptr(scratch), *((scratch.shape[1], scratch.stride(0), b) if lead else (scratch.numel(),)), n, num_heads, d, _stream(v))
     return bufs
 
 
@@ -1052,47 +1053,53 @@ def attention_qk8_pre(q8, k8, sq, sk, v, num_heads, out=None, scale=None, worksp
         raise HipLibraryError("attention_qk8_pre: smooth=True is a form of the e4m3 P V product (pv8=True)")
     ldv = _ld_rows(v, "v")
     b, nkv, hd = v.shape
-    if b > 1 and q8.dim() == 3:      # a batch of operands (attn_quant_qk's, or the fused producers', on a batch): the _b entry points
-        nq, d = q8.shape[1], hd // num_heads
+    lead = _lead(b) if q8.dim() == 3 else ()      # a batch of operands (attn_quant_qk's, or the fused producers', on a batch)
+    nq, d = q8.shape[-2], hd // num_heads
+    if lead:
         if q8.shape != (b, nq, hd) or k8.shape != (b, nkv, hd) or sq.shape != (b, nq, num_heads) or sk.shape != (b, num_heads) or \
                 not all(t.is_contiguous() for t in (q8, k8, sq, sk)):
             raise HipLibraryError(f"attention_qk8_pre: k8 and sk for v {tuple(v.shape)}, sq for q8 {tuple(q8.shape)}, all contiguous")
-        if pv8:
-            v8t, sv, _, *mu = attn_quant_vt(v, num_heads, pv8_bufs, smooth)
-            return attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=out, scale=scale, workspace=workspace, mu=mu[0] if smooth else None)
-        out = torch.empty((b, nq, hd), dtype=v.dtype, device=v.device) if out is None else out
-        ws, need = _attn_ws(v.device, b, nq, nkv, num_heads, workspace, per_element=True)
-        _call("fg_attn_fwd_qk8_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v), ldv,
-              v.stride(0), _ptr(out), nq * hd, b, nq, nkv, num_heads, d, float(d) ** -0.5 if scale is None else float(scale),
-              _ptr(ws) if need > 0 else None, need, _stream(v))
-        return out
-    nq, d = q8.shape[0], hd // num_heads
-    if b != 1 or q8.shape != (nq, hd) or k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads:
+    elif b != 1 or q8.shape != (nq, hd) or k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads:
         raise HipLibraryError(f"attention_qk8_pre: one batch element, k8 and sk for v {tuple(v.shape)}, sq for q8 {tuple(q8.shape)}")
-    out = torch.empty((b, nq, hd), dtype=v.dtype, device=v.device) if out is None else out
-    ws, need = _attn_ws(v.device, 1, nq, nkv, num_heads, workspace)
     if pv8:
-        v8t, sv, _, *mu = attn_quant_vt(v, num_heads, pv8_bufs, smooth)
-        if smooth:
-            _call("fg_attn_fwd_pv8s_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(mu[0]), _ptr(out), nq, nkv, num_heads,
-                  d, float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
-            return out
-        _call("fg_attn_fwd_pv8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
-              float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
-        return out
-    _call("fg_attn_fwd_qk8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v), ldv, _ptr(out), nq, nkv, num_heads, d,
-          float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(v))
+        vbufs = attn_quant_vt(v, num_heads, pv8_bufs, smooth)
+        return attention_pv8_pre(q8, k8, sq, sk, vbufs[0], vbufs[1], num_heads, out=out, scale=scale, workspace=workspace,
+                                 mu=vbufs[3] if smooth else None)
+    out = torch.empty((b, nq, hd), dtype=v.dtype, device=v.device) if out is None else out
+    ws = _attn_ws(v.device, b, nq, nkv, num_heads, workspace, per_element=bool(lead))
+    _call("fg_attn_fwd_qk8_bf16" + ("_b" if lead else ""), *_flat([(q8, nq * hd), (k8, nkv * hd), (sq, nq * num_heads), (sk, num_heads)], lead),
+          _ptr(v), ldv, *((v.stride(0),) if lead else ()), *_flat([(out, nq * hd)], lead), *lead, nq, nkv, num_heads, d, _softmax_scale(d, scale),
+          *_ws_args(*ws), _stream(v))
     return out
 
 
-def _batch8_check(who, q8, k8, sq, sk, v8t, sv, num_heads):
-    """(B, Nq, H*D, Nkv, D) of a batch of ready e4m3 operands, each contiguous with a leading batch dimension."""
-    (b, nq, hd), nkv = q8.shape, k8.shape[1]
+def _operands8(who, q8, k8, sq, sk, v8t, sv, num_heads, mu):
+    """(B or None, Nq, H*D, Nkv, D) of six ready e4m3 operands (and mu, or None, shaped like sv): one element's, or with a leading batch
+    dimension on all of them a batch's, each then contiguous."""
+    if mu is not None and (mu.shape != sv.shape or mu.dtype != torch.float32 or not mu.is_contiguous()):
+        raise HipLibraryError(f"{who}: mu must be fp32, contiguous and shaped like sv {tuple(sv.shape)}")
+    lead = tuple(q8.shape[:1]) if q8.dim() == 3 else ()
+    (nq, hd), nkv = q8.shape[-2:], k8.shape[-2]
     d = hd // num_heads
-    if k8.shape != (b, nkv, hd) or sq.shape != (b, nq, num_heads) or sk.shape != (b, num_heads) or sv.shape != (b, num_heads, d) or \
-            v8t.shape != (b, num_heads, d, (nkv + 63) // 64 * 64) or not all(t.is_contiguous() for t in (q8, k8, sq, sk, v8t, sv)):
-        raise HipLibraryError(f"{who}: k8, sq, sk, v8t, sv do not match the batch q8 {tuple(q8.shape)} and {nkv} keys (all contiguous)")
-    return b, nq, hd, nkv, d
+    ok = k8.shape == lead + (nkv, hd) and sq.shape == lead + (nq, num_heads) and v8t.shape == lead + (num_heads, d, (nkv + 63) // 64 * 64)
+    if lead:
+        ok = ok and sk.shape == lead + (num_heads,) and sv.shape == lead + (num_heads, d) and all(t.is_contiguous() for t in (q8, k8, sq, sk, v8t, sv))
+    else:      # one element: sk and sv go by size (a token shard hands them over flat)
+        ok = ok and sk.numel() == num_heads and sv.numel() == hd and v8t.is_contiguous()
+    if not ok:
+        raise HipLibraryError(f"{who}: k8, sq, sk, v8t, sv do not match " + (f"the batch q8 {tuple(q8.shape)} and {nkv} keys (all contiguous)"
+                                                                              if lead else f"q8 {tuple(q8.shape)} and {nkv} keys"))
+    return (lead[0] if lead else None), nq, hd, nkv, d
+
+
+def _fwd8(base, q8, k8, sq, sk, v8t, sv, mu, out, b, nq, hd, nkv, num_heads, tail):
+    """One launch of fg_attn_fwd_<base>[s]_bf16[_b]: s with mu, _b with a batch b (every operand then followed by its element stride);
+    tail: what follows the head size — the scale, and the workspace pair of the kernels that take one."""
+    ops = [(q8, nq * hd), (k8, nkv * hd), (sq, nq * num_heads), (sk, num_heads), (v8t, v8t.stride(0)), (sv, hd)] + \
+        ([(mu, hd)] if mu is not None else []) + [(out, nq * hd)]
+    _call(f"fg_attn_fwd_{base}{'s' if mu is not None else ''}_bf16{'_b' if b else ''}", *_flat(ops, b), *((b,) if b else ()), nq, nkv, num_heads,
+          hd // num_heads, *tail, _stream(q8))
+    return out
 
 
 def attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None, workspace=None, mu=None):
@@ -1100,35 +1107,10 @@ def attention_pv8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=None, 
     rounded up to 64) e4m3 and sv (H, 128) as attn_quant_vt or attn_shard8_vt left them -> (1, Nq, H*128) bf16.  Nq need not be Nkv (a
     token shard's queries against all keys).  workspace as in attention().  With a leading batch dimension on all six: the batched form.
     mu: attn_quant_vt(smooth=True)'s key means of v, shaped like sv — fg_attn_fwd_pv8s_bf16 / _b, which add them to the output rows."""
-    if mu is not None and (mu.shape != sv.shape or mu.dtype != torch.float32 or not mu.is_contiguous()):
-        raise HipLibraryError(f"attention_pv8_pre: mu must be fp32, contiguous and shaped like sv {tuple(sv.shape)}")
-    if q8.dim() == 3:
-        b, nq, hd, nkv, d = _batch8_check("attention_pv8_pre", q8, k8, sq, sk, v8t, sv, num_heads)
-        out = torch.empty((b, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
-        ws, need = _attn_ws(q8.device, b, nq, nkv, num_heads, workspace, per_element=True)
-        if mu is not None:
-            _call("fg_attn_fwd_pv8s_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
-                  v8t.stride(0), _ptr(sv), hd, _ptr(mu), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d,
-                  float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q8))
-            return out
-        _call("fg_attn_fwd_pv8_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
-              v8t.stride(0), _ptr(sv), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d, float(d) ** -0.5 if scale is None else float(scale),
-              _ptr(ws) if need > 0 else None, need, _stream(q8))
-        return out
-    (nq, hd), nkv = q8.shape, k8.shape[0]
-    d = hd // num_heads
-    if k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads or sv.numel() != hd or not v8t.is_contiguous() or \
-            v8t.shape != (num_heads, d, (nkv + 63) // 64 * 64):
-        raise HipLibraryError(f"attention_pv8_pre: k8, sq, sk, v8t, sv do not match q8 {tuple(q8.shape)} and {nkv} keys")
-    out = torch.empty((1, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
-    ws, need = _attn_ws(q8.device, 1, nq, nkv, num_heads, workspace)
-    if mu is not None:
-        _call("fg_attn_fwd_pv8s_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(mu), _ptr(out), nq, nkv, num_heads, d,
-              float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q8))
-        return out
-    _call("fg_attn_fwd_pv8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
-          float(d) ** -0.5 if scale is None else float(scale), _ptr(ws) if need > 0 else None, need, _stream(q8))
-    return out
+    b, nq, hd, nkv, d = _operands8("attention_pv8_pre", q8, k8, sq, sk, v8t, sv, num_heads, mu)
+    out = torch.empty((b or 1, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
+    ws = _attn_ws(q8.device, b or 1, nq, nkv, num_heads, workspace, per_element=b is not None)
+    return _fwd8("pv8", q8, k8, sq, sk, v8t, sv, mu, out, b, nq, hd, nkv, num_heads, (_softmax_scale(d, scale), *_ws_args(*ws)))
 
 
 def attention_cross8_max_kv():
@@ -1142,33 +1124,9 @@ def attention_cross8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=Non
     attention_pv8_pre without one.  With a leading batch dimension on all six: fg_attn_fwd_cross8_bf16_b, each workgroup on ONE element.
     mu: attn_quant_vt(smooth=True)'s key means of v, shaped like sv, with that call's v8t and sv — fg_attn_fwd_cross8s_bf16 / _b
     (include/fairygen_hip_cross8s.h), which add them to the output rows: the bits of attention_pv8_pre(mu=) without a workspace."""
-    if mu is not None and (mu.shape != sv.shape or mu.dtype != torch.float32 or not mu.is_contiguous()):
-        raise HipLibraryError(f"attention_cross8_pre: mu must be fp32, contiguous and shaped like sv {tuple(sv.shape)}")
-    if q8.dim() == 3:
-        b, nq, hd, nkv, d = _batch8_check("attention_cross8_pre", q8, k8, sq, sk, v8t, sv, num_heads)
-        out = torch.empty((b, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
-        if mu is not None:
-            _call("fg_attn_fwd_cross8s_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
-                  v8t.stride(0), _ptr(sv), hd, _ptr(mu), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d,
-                  float(d) ** -0.5 if scale is None else float(scale), _stream(q8))
-            return out
-        _call("fg_attn_fwd_cross8_bf16_b", _ptr(q8), nq * hd, _ptr(k8), nkv * hd, _ptr(sq), nq * num_heads, _ptr(sk), num_heads, _ptr(v8t),
-              v8t.stride(0), _ptr(sv), hd, _ptr(out), nq * hd, b, nq, nkv, num_heads, d, float(d) ** -0.5 if scale is None else float(scale),
-              _stream(q8))
-        return out
-    (nq, hd), nkv = q8.shape, k8.shape[0]
-    d = hd // num_heads
-    if k8.shape != (nkv, hd) or sq.shape != (nq, num_heads) or sk.numel() != num_heads or sv.numel() != hd or not v8t.is_contiguous() or \
-            v8t.shape != (num_heads, d, (nkv + 63) // 64 * 64):
-        raise HipLibraryError(f"attention_cross8_pre: k8, sq, sk, v8t, sv do not match q8 {tuple(q8.shape)} and {nkv} keys")
-    out = torch.empty((1, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
-    if mu is not None:
-        _call("fg_attn_fwd_cross8s_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(mu), _ptr(out), nq, nkv, num_heads,
-              d, float(d) ** -0.5 if scale is None else float(scale), _stream(q8))
-        return out
-    _call("fg_attn_fwd_cross8_bf16", _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, num_heads, d,
-          float(d) ** -0.5 if scale is None else float(scale), _stream(q8))
-    return out
+    b, nq, hd, nkv, d = _operands8("attention_cross8_pre", q8, k8, sq, sk, v8t, sv, num_heads, mu)
+    out = torch.empty((b or 1, nq, hd), dtype=torch.bfloat16, device=q8.device) if out is None else out
+    return _fwd8("cross8", q8, k8, sq, sk, v8t, sv, mu, out, b, nq, hd, nkv, num_heads, (_softmax_scale(d, scale),))
 
 
 # ---- the e4m3 operands of a token shard (include/fairygen_hip_shard8.h)
@@ -1257,101 +1215,85 @@ def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs
 def attention_qk8_fused_scratch(n, num_heads, head_dim, device, batch=1):
     """The buffers of the fused producers for (n, num_heads * head_dim) q and k: attention_qk8_scratch's five (q8, k8, sq, sk, the key
     mean) and the key-statistics partials rmsnorm_rope_kstats hands to attn_quant_k."""
-    need = load().fg_attn_qk8_fused_scratch_bytes(n, num_heads * head_dim)
-    if need < 0:
-        raise HipLibraryError(f"attention_qk8_fused_scratch: {load().fg_last_error().decode()}")
     return attention_qk8_scratch(n, num_heads, head_dim, device, batch) + \
-        (torch.empty(((batch,) if batch > 1 else ()) + (need,), dtype=torch.uint8, device=device),)
+        (torch.empty(_lead(batch) + (_kstats_bytes("attention_qk8_fused_scratch", n, num_heads * head_dim),), dtype=torch.uint8, device=device),)
+
+
+def _kstats_bytes(who, rows, c):
+    need = load().fg_attn_qk8_fused_scratch_bytes(rows, c)
+    if need < 0:
+        raise HipLibraryError(f"{who}: {load().fg_last_error().decode()}")
+    return need
+
+
+def _norm_rows(x, who):
+    """(lead, rows, row stride) of the input of a fused producer: plain rows (_rows2d), or with B > 1 elements (B, rows, C) the rows of
+    each (_ld_rows) — the _b entry points, the RoPE table per element."""
+    if x.dim() == 3 and x.shape[0] > 1:
+        return (x.shape[0],), x.shape[1], _ld_rows(x, "x")
+    x2 = _rows2d(x, who)
+    return (), x2.shape[0], x2.stride(0)
 
 
 def rmsnorm_rope_q8(x, weight, num_heads, eps, cos=None, sin=None, q8=None, sq=None):
     """rmsnorm_rope (head_dim 128, plain rows) whose row leaves as the e4m3 q operand of attention_qk8_pre: (q8 (rows, C), sq (rows,
-    num_heads)), the bytes attn_quant_qk makes of rmsnorm_rope's output, which is never written."""
+    num_heads)), the bytes attn_quant_qk makes of rmsnorm_rope's output, which is never written.  A batch (B, rows, C): both with a
+    leading B (fg_rmsnorm_rope_q8_bf16_b)."""
     _dev(x, "x"), _dev(weight, "weight")
     c = x.shape[-1]
-    if x.dim() == 3 and x.shape[0] > 1:      # a batch: the B * rows rows of one matrix, the table per element (fg_rmsnorm_rope_q8_bf16_b)
-        ld, (b, rows) = _ld_rows(x, "x"), x.shape[:2]
-        f32tab = _rope_tables("rmsnorm_rope_q8", cos, sin, rows, c // num_heads // 2)
-        q8 = torch.empty((b, rows, c), dtype=torch.float8_e4m3fn, device=x.device) if q8 is None else q8
-        sq = torch.empty((b, rows, num_heads), dtype=torch.float32, device=x.device) if sq is None else sq
-        if q8.shape != (b, rows, c) or sq.shape != (b, rows, num_heads) or not q8.is_contiguous() or not sq.is_contiguous():
-            raise HipLibraryError("rmsnorm_rope_q8: q8 must be (B, rows, C), sq (B, rows, num_heads), contiguous")
-        _call("fg_rmsnorm_rope_q8_bf16_b", _ptr(x), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(q8), _ptr(sq), b, rows, c, num_heads,
-              eps, _stream(x))
-        return q8, sq
-    x2 = _rows2d(x, "rmsnorm_rope_q8")
-    rows, ld = x2.shape[0], x2.stride(0)
+    lead, rows, ld = _norm_rows(x, "rmsnorm_rope_q8")
     f32tab = _rope_tables("rmsnorm_rope_q8", cos, sin, rows, c // num_heads // 2)
-    q8 = torch.empty((rows, c), dtype=torch.float8_e4m3fn, device=x.device) if q8 is None else q8
-    sq = torch.empty((rows, num_heads), dtype=torch.float32, device=x.device) if sq is None else sq
-    if q8.shape != (rows, c) or sq.shape != (rows, num_heads) or not q8.is_contiguous() or not sq.is_contiguous():
-        raise HipLibraryError("rmsnorm_rope_q8: q8 must be (rows, C), sq (rows, num_heads), contiguous")
-    _call("fg_rmsnorm_rope_q8_bf16", _ptr(x2), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(q8), _ptr(sq), rows, c, num_heads, eps,
-          _stream(x))
+    q8 = torch.empty(lead + (rows, c), dtype=torch.float8_e4m3fn, device=x.device) if q8 is None else q8
+    sq = torch.empty(lead + (rows, num_heads), dtype=torch.float32, device=x.device) if sq is None else sq
+    if q8.shape != lead + (rows, c) or sq.shape != lead + (rows, num_heads) or not q8.is_contiguous() or not sq.is_contiguous():
+        raise HipLibraryError(f"rmsnorm_rope_q8: q8 must be {'(B, rows, C), sq (B, ' if lead else '(rows, C), sq ('}rows, num_heads), contiguous")
+    _call("fg_rmsnorm_rope_q8_bf16" + ("_b" if lead else ""), _ptr(x), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(q8), _ptr(sq), *lead,
+          rows, c, num_heads, eps, _stream(x))
     return q8, sq
 
 
 def rmsnorm_rope_kstats(x, weight, num_heads, eps, cos=None, sin=None, out=None, partials=None):
     """rmsnorm_rope (head_dim 128, plain rows) that also leaves the key statistics of the rows it wrote: (k, partials), k rmsnorm_rope's
-    bytes, partials (attention_qk8_fused_scratch's last buffer, else allocated) for attn_quant_k."""
+    bytes, partials (attention_qk8_fused_scratch's last buffer, else allocated) for attn_quant_k.  A batch (B, rows, C): one partials
+    block per element, (B, bytes) (fg_rmsnorm_rope_kstats_bf16_b)."""
     _dev(x, "x"), _dev(weight, "weight")
     c = x.shape[-1]
-    if x.dim() == 3 and x.shape[0] > 1:      # a batch: one partials block per element (fg_rmsnorm_rope_kstats_bf16_b)
-        ld, (b, rows) = _ld_rows(x, "x"), x.shape[:2]
-        f32tab = _rope_tables("rmsnorm_rope_kstats", cos, sin, rows, c // num_heads // 2)
-        out = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
-        if out.shape != x.shape or not out.is_contiguous():
-            raise HipLibraryError("rmsnorm_rope_kstats: out must be contiguous and of x's shape")
-        if partials is None:
-            need = load().fg_attn_qk8_fused_scratch_bytes(rows, c)
-            if need < 0:
-                raise HipLibraryError(f"rmsnorm_rope_kstats: {load().fg_last_error().decode()}")
-            partials = torch.empty((b, need), dtype=torch.uint8, device=x.device)
-        if partials.dim() != 2 or partials.shape[0] != b or partials.stride(1) != 1:
-            raise HipLibraryError("rmsnorm_rope_kstats: partials of a batch must be (B, bytes)")
-        _call("fg_rmsnorm_rope_kstats_bf16_b", _ptr(x), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(out), _ptr(partials),
-              partials.shape[1], partials.stride(0), b, rows, c, num_heads, eps, _stream(x))
-        return out, partials
-    x2 = _rows2d(x, "rmsnorm_rope_kstats")
-    rows, ld = x2.shape[0], x2.stride(0)
+    lead, rows, ld = _norm_rows(x, "rmsnorm_rope_kstats")
     f32tab = _rope_tables("rmsnorm_rope_kstats", cos, sin, rows, c // num_heads // 2)
     out = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
     if out.shape != x.shape or not out.is_contiguous():
         raise HipLibraryError("rmsnorm_rope_kstats: out must be contiguous and of x's shape")
     if partials is None:
-        need = load().fg_attn_qk8_fused_scratch_bytes(rows, c)
-        if need < 0:
-            raise HipLibraryError(f"rmsnorm_rope_kstats: {load().fg_last_error().decode()}")
-        partials = torch.empty(need, dtype=torch.uint8, device=x.device)
-    _call("fg_rmsnorm_rope_kstats_bf16", _ptr(x2), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(out), _ptr(partials),
-          partials.numel(), rows, c, num_heads, eps, _stream(x))
+        partials = torch.empty(lead + (_kstats_bytes("rmsnorm_rope_kstats", rows, c),), dtype=torch.uint8, device=x.device)
+    if lead and (partials.dim() != 2 or partials.shape[0] != lead[0] or partials.stride(1) != 1):
+        raise HipLibraryError("rmsnorm_rope_kstats: partials of a batch must be (B, bytes)")
+    _call("fg_rmsnorm_rope_kstats_bf16" + ("_b" if lead else ""), _ptr(x), ld, _ptr(weight), _ptr(cos), _ptr(sin), f32tab, _ptr(out), _ptr(partials),
+          *((partials.shape[1], partials.stride(0)) + lead if lead else (partials.numel(),)), rows, c, num_heads, eps, _stream(x))
     return out, partials
 
 
 def attn_quant_k(k, partials, num_heads, k8=None, sk=None, kbar=None):
-    """The e4m3 k operand from rmsnorm_rope_kstats's pair: k (1, N, H*128) bf16 -> (k8 (N, H*128), sk (H), the key mean (H*128))."""
+    """The e4m3 k operand from rmsnorm_rope_kstats's pair: k (1, N, H*128) bf16 -> (k8 (N, H*128), sk (H), the key mean (H*128)).  A batch
+    (B, N, H*128) with its (B, bytes) partials: the three with a leading B (fg_attn_quant_k_bf16_b)."""
     ldk = _ld_rows(k, "k")
     b, n, hd = k.shape
-    if b > 1:      # a batch: fg_attn_quant_k_bf16_b on rmsnorm_rope_kstats's (B, bytes) partials
-        f32 = torch.float32
-        k8 = torch.empty((b, n, hd), dtype=torch.float8_e4m3fn, device=k.device) if k8 is None else k8
-        sk = torch.empty((b, num_heads), dtype=f32, device=k.device) if sk is None else sk
-        kbar = torch.empty((b, hd), dtype=f32, device=k.device) if kbar is None else kbar
+    if b < 1:
+        raise HipLibraryError(f"attn_quant_k: k must be (1, N, H*D), got {tuple(k.shape)}")
+    lead = _lead(b)
+    k8 = torch.empty(lead + (n, hd), dtype=torch.float8_e4m3fn, device=k.device) if k8 is None else k8
+    sk = torch.empty(lead + (num_heads,), dtype=torch.float32, device=k.device) if sk is None else sk
+    kbar = torch.empty(lead + (hd,), dtype=torch.float32, device=k.device) if kbar is None else kbar
+    if lead:
         if k8.shape != (b, n, hd) or sk.shape != (b, num_heads) or kbar.shape != (b, hd) or partials.dim() != 2 or partials.shape[0] != b or \
                 not all(t.is_contiguous() for t in (k8, sk, kbar)):
             raise HipLibraryError("attn_quant_k: k8, sk, kbar, partials do not match (B, N, H*D)")
-        _call("fg_attn_quant_k_bf16_b", _ptr(k), ldk, k.stride(0), _ptr(partials), partials.shape[1], partials.stride(0), _ptr(k8), n * hd,
-              _ptr(sk), num_heads, _ptr(kbar), hd, b, n, num_heads, hd // num_heads, _stream(k))
+        _call("fg_attn_quant_k_bf16_b", _ptr(k), ldk, k.stride(0), _ptr(partials), partials.shape[1], partials.stride(0),
+              *_flat([(k8, n * hd), (sk, num_heads), (kbar, hd)], True), b, n, num_heads, hd // num_heads, _stream(k))
         return k8, sk, kbar
-    if b != 1:
-        raise HipLibraryError(f"attn_quant_k: k must be (1, N, H*D), got {tuple(k.shape)}")
-    k8 = torch.empty((n, hd), dtype=torch.float8_e4m3fn, device=k.device) if k8 is None else k8
-    sk = torch.empty(num_heads, dtype=torch.float32, device=k.device) if sk is None else sk
-    kbar = torch.empty(hd, dtype=torch.float32, device=k.device) if kbar is None else kbar
-    if k8.shape != (n, hd) or sk.numel() != num_heads or kbar.numel() < hd:
+    if k8.shape != (n, hd) or sk.numel() != num_heads or kbar.numel() < hd:      # one element: sk and the key mean go by size
         raise HipLibraryError("attn_quant_k: k8, sk, kbar do not match (N, H*D)")
-    _call("fg_attn_quant_k_bf16", _ptr(k), ldk, _ptr(partials), partials.numel(), _ptr(k8), _ptr(sk), _ptr(kbar), n, num_heads,
-          hd // num_heads, _stream(k))
+    _call("fg_attn_quant_k_bf16", _ptr(k), ldk, _ptr(partials), partials.numel(), _ptr(k8), _ptr(sk), _ptr(kbar), n, num_heads, hd // num_heads,
+          _stream(k))
     return k8, sk, kbar
 
 

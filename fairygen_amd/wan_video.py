@@ -648,7 +648,10 @@ class GraphedStep:
         with torch.cuda.device(dev):
             self.sched, self.workspace = hip.gemm_state(dev)
         self.attn_workspace = []
-        self.attn_qk8_bufs = {}      # enable_qk8_attention(): (N, heads, head_dim, device) -> the e4m3 q / k, their scales, the key-mean scratch (+ "fused": and the key-statistics partials; + "pv8": v8t, sv and the v-statistics scratch of enable_qk8_attention(pv8=True); "pv8s" in its place with smooth_v=True: those three and mu)
+        # enable_qk8_attention(): (kind, N, heads, head_dim, device) -> the buffers wan_video_dit._BlockAttention._owned made for the step.
+        # kind "qk8": the e4m3 q / k, their scales, the key-mean scratch; "qk8-fused": those and the key-statistics partials; "pv8": v8t, sv
+        # and the v-statistics scratch (pv8=True), "pv8s" in its place with smooth_v=True: those three and mu; "cross8-q": q8, sq (cross=True)
+        self.attn_qk8_bufs = {}
         self.graph = self.latents = None
 
     def _issue(self):

@@ -7,8 +7,8 @@ identification (``core/loader/file.py:117-121``) keep working.  The modules hold
 arithmetic is in ``forward_tokens_steps`` below, built from ``fairygen_amd.hip`` kernels: one block body whose
 Linears go through ``_BlockLinears`` — this repo's persistent MFMA GEMM (bf16 or e4m3, with the residual / gate /
 GELU stores) by default, hipBLASLt (``F.linear``, ``torch._scaled_mm``) where ``FAIRYGEN_GEMM`` / ``FAIRYGEN_FP8_GEMM`` or
-the shape say so — and whose norms hand over an ``Act``.  The embedding and head Linears are ``F.linear``.  Nothing here
-runs on CPU tensors — the HIP library raises.
+the shape say so — and whose norms hand over an ``Act``; its attention goes through ``_BlockAttention`` — bf16, or the e4m3 forms of
+``enable_qk8_attention``.  The embedding and head Linears are ``F.linear``.  Nothing here runs on CPU tensors — the HIP library raises.
 """
 import math
 import os
@@ -171,7 +171,7 @@ class _BlockLinears:
     def __init__(self, model, mod_rows, owned=None):
         self.model, self.eps = model, model.eps
         # None, or what a captured step owns in place of the state hip keeps per (device, stream), which must not be recorded into a graph
-        # (its key outlives the capture stream): .sched / .workspace (hip.gemm_state) for the own GEMMs, .attn_workspace for attention
+        # (its key outlives the capture stream): .sched / .workspace (hip.gemm_state) for the own GEMMs; attention's part: _BlockAttention
         self.owned = owned
         self.fp8 = fp8 = model.fp8_dtype
         self.hot = hot = bool(model.hot_loras)
@@ -242,85 +242,6 @@ class _BlockLinears:
         if self.owned is None:
             return {}
         return {"sched": self.owned.sched, "workspace": self.owned.workspace if hip.gemm_workspace_need(rows, n, k_bytes) > 0 else False}
-
-    def attention(self, attn, q, k, v, scale=None, self_attn=False):
-        kw = {} if scale is None else {"scale": scale}
-        if self.owned is not None:
-            kw["workspace"] = self.owned.attn_workspace
-        if self_attn and takes_qk8_attention(self.model, attn, k.shape[1], q.shape[0]):
-            # the e4m3 Q K^T form (enable_qk8_attention); a captured step owns the quantised operands' buffers as it owns the split-KV scratch
-            if self.owned is not None:
-                kw["bufs"] = self.qk8_bufs(q.shape[1], attn.num_heads, q.shape[2] // attn.num_heads, q.device, False)
-            return hip.attention_qk8(q, k, v, attn.num_heads, **kw, **self.pv8_kw(v, attn.num_heads))
-        return attn(q, k, v, **kw)
-
-    def pv8_kw(self, v, num_heads):
-        """The pv8= / pv8_bufs= of the e4m3 attention call on v (1, N, H*D): nothing unless enable_qk8_attention(pv8=True); a captured step
-        owns v8t, sv and the statistics scratch next to the e4m3 q / k buffers — with smooth_v=True (smooth= of the call) also mu, next
-        to sv, and the larger scratch of that form."""
-        if not self.model.pv8_attention:
-            return {}
-        smooth = {"smooth": True} if self.model.smoothv_attention else {}
-        if self.owned is None:
-            return {"pv8": True, **smooth}
-        key = (v.shape[1], num_heads, v.shape[2] // num_heads, v.device, "pv8s" if smooth else "pv8")
-        if key not in self.owned.attn_qk8_bufs:
-            self.owned.attn_qk8_bufs[key] = hip.attention_pv8_scratch(*key[:4], smooth=bool(smooth))
-        return {"pv8": True, "pv8_bufs": self.owned.attn_qk8_bufs[key], **smooth}
-
-    def cross8_q(self, qc, norm_q, num_heads):
-        """The e4m3 q operand of cross-attention (enable_qk8_attention(cross=True)) from the q Linear's output: the RMSNorm pass without a
-        RoPE table writes the e4m3 rows and their scales and no bf16 q.  A captured step owns the two buffers, one pair per shape for
-        all blocks (a block's pair is consumed before the next block writes it, in stream order)."""
-        kw = {}
-        if self.owned is not None:
-            key = (qc.shape[1], num_heads, qc.shape[2] // num_heads, qc.device, "cross8")
-            if key not in self.owned.attn_qk8_bufs:
-                self.owned.attn_qk8_bufs[key] = (torch.empty(qc.shape[1:], dtype=torch.float8_e4m3fn, device=qc.device),
-                                                 torch.empty((qc.shape[1], num_heads), dtype=torch.float32, device=qc.device))
-            kw["q8"], kw["sq"] = self.owned.attn_qk8_bufs[key]
-        return hip.rmsnorm_rope_q8(qc, norm_q.weight, num_heads, self.eps, **kw)
-
-    def cross8_context(self, kvc, norm_k, num_heads):
-        """The e4m3 operands of a block's context from its k | v rows (1, L, 2 C): (k8, sk, v8t, sv) — the RMSNorm pass of k that also leaves
-        the key statistics, the key conversion behind it, and fg_attn_quant_vt_bf16 on v.  Once per denoise loop with a kv_cache, which
-        then holds these four in place of (k, v); the buffers are the binding's own allocations either way.  With
-        enable_qk8_attention(smooth_v_cross=True) the V producer is the smoothing one (fg_attn_quant_vt_smooth_bf16) and the key means of v
-        follow as a fifth tensor: (k8, sk, v8t, sv, mu)."""
-        c = kvc.shape[-1] // 2
-        k, parts = hip.rmsnorm_rope_kstats(kvc[..., :c], norm_k.weight, num_heads, self.eps)
-        k8, sk, _ = hip.attn_quant_k(k, parts, num_heads)
-        if self.model.smoothv_cross_attention:      # enable_qk8_attention(smooth_v_cross=True): v minus its key mean, and the mean
-            v8t, sv, _, mu = hip.attn_quant_vt(kvc[..., c:], num_heads, smooth=True)
-            return k8, sk, v8t, sv, mu
-        v8t, sv, _ = hip.attn_quant_vt(kvc[..., c:], num_heads)
-        return k8, sk, v8t, sv
-
-    def qk8_bufs(self, n, num_heads, head_dim, device, fused):
-        """The e4m3 operands' buffers: a captured step's own, made once per shape (fused: with the key-statistics partials); None in an
-        eager forward, where the binding allocates."""
-        if self.owned is None:
-            return None
-        key = (n, num_heads, head_dim, device) + (("fused",) if fused else ())
-        if key not in self.owned.attn_qk8_bufs:
-            self.owned.attn_qk8_bufs[key] = (hip.attention_qk8_fused_scratch if fused else hip.attention_qk8_scratch)(*key[:4])
-        return self.owned.attn_qk8_bufs[key]
-
-    def attention_qk8_fused(self, sa, qkv, rq, rk, scale):
-        """Self-attention in the e4m3 Q K^T form straight from the q | k | v buffer (enable_qk8_attention(fused_producer=True)): the
-        RMSNorm+RoPE pass of q writes the e4m3 rows and their scales and no bf16 q, that of k writes bf16 k and the key statistics, one
-        pass converts k.  The bytes of rmsnorm_rope x 2 -> attention_qk8 (tests/test_attention_qk8_fused.py)."""
-        nh, eps = sa.attn.num_heads, self.model.eps
-        c = qkv.shape[-1] // 3
-        n = qkv.shape[1]
-        bufs = self.qk8_bufs(n, nh, c // nh, qkv.device, True) or hip.attention_qk8_fused_scratch(n, nh, c // nh, qkv.device, qkv.shape[0])
-        q8, k8, sq, sk, kbar, parts = bufs
-        k, _ = hip.rmsnorm_rope_kstats(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, partials=parts)
-        hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, q8=q8, sq=sq)
-        hip.attn_quant_k(k, parts, nh, k8, sk, kbar)
-        kw = {} if self.owned is None else {"workspace": self.owned.attn_workspace}
-        v = qkv[..., 2 * c:]
-        return hip.attention_qk8_pre(q8, k8, sq, sk, v, nh, scale=scale, **kw, **self.pv8_kw(v, nh))
 
     def q8(self, a):
         return a.q8 if a.q8 is not None else hip.fp8_quant_rows(a.bf16, None)
@@ -440,8 +361,192 @@ def takes_cross8_attention(model, attn, n_kv, batch):
 
 def takes_qk8_attention(model, attn, n_kv, batch):
     """Whether a block's self-attention over n_kv keys runs the e4m3 Q K^T kernel: the mode on, the stock AttentionModule, more than
-    QK8_MIN_KV keys, one batch element.  The one predicate of _BlockLinears.attention and of the fused producers in front of it."""
+    QK8_MIN_KV keys, one batch element.  n_kv is the TOTAL key count: all ranks' on a token shard (_BlockAttention.self_attention_steps)."""
     return bool(model.qk8_attention) and type(attn) is AttentionModule and n_kv > QK8_MIN_KV and (batch == 1 or bool(model.stacked_cfg))
+
+
+class _BlockAttention:
+    """How the attention of the blocks runs in ONE forward, next to _BlockLinears: the forms enable_qk8_attention switched on (the model's
+    flags, read once; whether a call takes them is takes_qk8_attention / takes_cross8_attention, asked once per attention), what a
+    captured step owns in place of per-call allocations, and the two paths — self_attention_steps between the q | k | v Linear and o,
+    cross_attention from norm3's row to the operand of o."""
+
+    def __init__(self, model, lin, owned=None):
+        self.model, self.lin, self.eps = model, lin, model.eps
+        # None, or a captured step (_BlockLinears.owned): .attn_workspace, the split-KV scratch, and .attn_qk8_bufs, the e4m3 operands
+        self.owned = owned
+        self.fused = model.qk8_fused_producer                                   # the RMSNorm+RoPE pass writes the e4m3 q / k operands
+        self.pv8, self.smooth = model.pv8_attention, model.smoothv_attention    # P V in e4m3 too; with V mean-smoothed
+        self.cross_smooth = model.smoothv_cross_attention                       # the e4m3 cross-attention with V mean-smoothed
+
+    def _owned(self, kind, n, num_heads, head_dim, device, make):
+        """A captured step's buffers of one kind and shape — make(n, num_heads, head_dim, device), once, one set for all blocks (a block's
+        are consumed before the next block writes them, in stream order); None in an eager forward, where the binding allocates."""
+        if self.owned is None:
+            return None
+        key = (kind, n, num_heads, head_dim, device)
+        if key not in self.owned.attn_qk8_bufs:
+            self.owned.attn_qk8_bufs[key] = make(n, num_heads, head_dim, device)
+        return self.owned.attn_qk8_bufs[key]
+
+    def workspace(self):
+        """The workspace= of an attention call: a captured step's own split-KV scratch; nothing in an eager forward, so that the seams
+        tools replace (hip.attention behind AttentionModule) are called as they have always been."""
+        return {} if self.owned is None else {"workspace": self.owned.attn_workspace}
+
+    def attention(self, attn, q, k, v, scale=None):
+        """The bf16 form, through the block's AttentionModule (plug point (iii))."""
+        return attn(q, k, v, **({} if scale is None else {"scale": scale}), **self.workspace())
+
+    def pv8_kw(self, v, num_heads):
+        """The pv8= / smooth= / pv8_bufs= of an e4m3 self-attention call on v (1, N, H*D): nothing unless enable_qk8_attention(pv8=True); a
+        captured step owns v8t, sv and the statistics scratch — with smooth_v=True also mu, and the larger scratch of that form."""
+        if not self.pv8:
+            return {}
+        bufs = self._owned("pv8s" if self.smooth else "pv8", v.shape[1], num_heads, v.shape[2] // num_heads, v.device,
+                           lambda *shape: hip.attention_pv8_scratch(*shape, smooth=self.smooth))
+        return {"pv8": True, "smooth": self.smooth, "pv8_bufs": bufs}
+
+    # ---- self-attention
+    def self_attention(self, sa, qkv, rq, rk, scale, e4m3):
+        """The unsharded block, from the q | k | v buffer (B, N, 3 C).  bf16: the two RMSNorm+RoPE passes, then the AttentionModule.
+        e4m3 (takes_qk8_attention said so), two-step: the same two passes, then hip.attention_qk8 (quantise, attend).  e4m3 with
+        enable_qk8_attention(fused_producer=True): the pass of q writes the e4m3 rows and their scales and no bf16 q, that of k writes
+        bf16 k and the key statistics, one pass converts k — the bytes of the two-step form (tests/test_attention_qk8_fused.py)."""
+        nh, eps = sa.attn.num_heads, self.eps
+        c = qkv.shape[-1] // 3
+        shape = (qkv.shape[1], nh, c // nh, qkv.device)
+        v = qkv[..., 2 * c:]
+        if e4m3 and self.fused:
+            q8, k8, sq, sk, kbar, parts = self._owned("qk8-fused", *shape, hip.attention_qk8_fused_scratch) or \
+                hip.attention_qk8_fused_scratch(*shape, qkv.shape[0])
+            k, _ = hip.rmsnorm_rope_kstats(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, partials=parts)
+            hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, q8=q8, sq=sq)
+            hip.attn_quant_k(k, parts, nh, k8, sk, kbar)
+            return hip.attention_qk8_pre(q8, k8, sq, sk, v, nh, scale=scale, **self.workspace(), **self.pv8_kw(v, nh))
+        nb = self.lin.batch_of(qkv)
+        k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, batch=nb)
+        q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, batch=nb)
+        if e4m3:
+            return hip.attention_qk8(q, k, v, nh, scale=scale, bufs=self._owned("qk8", *shape, hip.attention_qk8_scratch), **self.workspace(),
+                                     **self.pv8_kw(v, nh))
+        return self.attention(sa.attn, q, k, v, scale)
+
+    def self_attention_steps(self, i, sa, qkv, rq, rk, scale, shard, shard_total):
+        """Block i's self-attention from its q | k | v buffer: (B, n, C).  Yields i right after each exchange of a token-sharded run has
+        been started.  The e4m3 form is decided once, on the key count of all ranks: a shard of 200 rows of 1 600 keys takes it."""
+        sharded = shard is not None and shard.active
+        e4m3 = takes_qk8_attention(self.model, sa.attn, shard_total if sharded else qkv.shape[1], qkv.shape[0])
+        if not sharded:
+            return self.self_attention(sa, qkv, rq, rk, scale, e4m3)
+        nh, eps = sa.attn.num_heads, self.eps
+        c = qkv.shape[-1] // 3
+        v = qkv[..., 2 * c:]
+        if shard.attn_mode == "ulysses":
+            # token shard -> head shard (all N tokens of 24/P heads), attention, head shard -> token shard.  The
+            # norm+RoPE kernels and one strided copy write q | k | v straight into the all-to-all send buffer.
+            n_loc, p_, size, hl = qkv.shape[1], shard.world_size, shard.chunk(shard_total), shard.heads_local(nh)
+            g = c // nh * hl
+            send = shard.ulysses_send_buffer(shard_total, c, qkv, n_loc)           # (P, chunk, 3, g)
+            flat, layout = send.view(-1), (g, size * 3 * g, 3 * g)
+            hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, grouped=(flat, *layout))
+            hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, grouped=(flat[g:], *layout))
+            hip.copy_groups(qkv.view(-1)[2 * c:], g, 3 * c, flat[2 * g:], size * 3 * g, 3 * g, p_, n_loc, g)
+            pending = shard.ulysses_exchange_async(send, shard_total)
+            yield i
+            qg, kg, vg = pending.wait()
+            o_full = shard.ulysses_out_buffer(shard_total, g, qkv)
+            out = o_full[:shard_total].unsqueeze(0)
+            if e4m3:      # all N tokens of this rank's heads: every statistic is local
+                hip.attention_qk8(qg, kg, vg, hl, out=out, scale=scale, **self.pv8_kw(vg, hl))
+            else:
+                hip.attention(qg, kg, vg, hl, out=out, scale=scale)
+            pending = shard.ulysses_out_async(o_full, shard_total, n_loc)
+            yield i
+            a = torch.empty((1, n_loc, c), dtype=qkv.dtype, device=qkv.device)
+            hip.copy_groups(pending.wait_blocks().view(-1), size * g, g, a.view(-1), g, c, p_, n_loc, g)
+            return a
+        if e4m3:
+            return (yield from self._shard8_steps(i, sa, qkv, rq, rk, scale, shard, shard_total))
+        k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
+        pending = shard.all_gather_kv_async(k, v, shard_total)
+        q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)
+        yield i
+        k, v = pending.wait()
+        return self.attention(sa.attn, q, k, v, scale)
+
+    def _shard8_steps(self, i, sa, qkv, rq, rk, scale, shard, shard_total):
+        """Block i's self-attention in the e4m3 form on the K / V all-gather layout (enable_qk8_attention(sharded=True),
+        include/fairygen_hip_shard8.h): this rank's queries against all N keys.  Two exchanges, a yield after each has been started: the
+        ranks' statistics records (20 * C bytes each), from which every rank derives the unsharded key mean, sk and sv; then k8 and v (with
+        pv8: v8) through all_gather_kv_async, as uint8 views.  A rank without rows launches nothing and sends the neutral record."""
+        nh, eps, pv8 = sa.attn.num_heads, self.eps, self.pv8
+        c = qkv.shape[-1] // 3
+        n_loc, dev = qkv.shape[1], qkv.device
+        v = qkv[..., 2 * c:]
+        if n_loc:
+            k, parts = hip.rmsnorm_rope_kstats(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
+            record = hip.attn_shard8_stats(parts, n_loc, nh, v if pv8 else None)
+        else:
+            record = hip.attn_shard8_neutral_record(c, dev)
+        pending = shard.all_gather_records_async(record)
+        yield i
+        if n_loc:
+            q8, sq = hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)      # overlaps the record exchange
+            k8, v8, sk, _, sv = hip.attn_shard8_quant(pending.wait(), shard_total, k, nh, v if pv8 else None)
+            k8, v_send = k8.view(torch.uint8), (v8.view(torch.uint8) if pv8 else v[0])
+        else:
+            pending.wait()
+            k8 = torch.empty((0, c), dtype=torch.uint8, device=dev)
+            v_send = k8 if pv8 else v[0]
+        pending = shard.all_gather_kv_async(k8.unsqueeze(0), v_send.unsqueeze(0), shard_total)
+        yield i
+        k8f, vf = pending.wait()
+        if not n_loc:
+            return torch.empty((1, 0, c), dtype=qkv.dtype, device=dev)
+        k8f = k8f[0].view(torch.float8_e4m3fn)
+        if pv8:
+            return hip.attention_pv8_pre(q8, k8f, sq, sk, hip.attn_shard8_vt(vf[0].contiguous(), nh), sv, nh, scale=scale)
+        return hip.attention_qk8_pre(q8, k8f, sq, sk, vf, nh, scale=scale)
+
+    # ---- cross-attention
+    def cross_attention(self, i, ca, h, ctx, kv_cache, wkv, bkv, w8):
+        """Block i's cross-attention (reference :170-185) from h = norm3(x) against the context, both Acts: the q Linear and its norm,
+        the block's context operands — computed from the k | v Linear (wkv, bkv: DiTBlock.fused_weights') on the context rows, or read
+        back from kv_cache, which holds them once per denoise loop — and the attention; returns the operand of o.
+        bf16: the operands are (k after norm_k, v).  e4m3 (enable_qk8_attention(cross=True), takes_cross8_attention): the q norm writes
+        the e4m3 rows and their scales and no bf16 q (the RMSNorm pass without a RoPE table; a captured step owns the pair), and the
+        operands are (k8, sk, v8t, sv) — the RMSNorm pass of k that also leaves the key statistics, the key conversion behind it, and
+        fg_attn_quant_vt_bf16 on v.  With smooth_v_cross=True the V producer is the smoothing one and the key means of v follow as a
+        fifth tensor, mu."""
+        lin, nh, eps = self.lin, ca.attn.num_heads, self.eps
+        q = lin.plain(h, (f"blocks.{i}.cross_attn.q",), ca.q.weight, ca.q.bias, w8[2], own=lin.own)
+        e4m3 = takes_cross8_attention(self.model, ca.attn, ctx.rows, q.shape[0])
+        if e4m3:
+            q8, sq = self._owned("cross8-q", q.shape[1], nh, q.shape[2] // nh, q.device, lambda n, heads, hd, dev: (
+                torch.empty((n, heads * hd), dtype=torch.float8_e4m3fn, device=dev), torch.empty((n, heads), dtype=torch.float32, device=dev))) \
+                or (None, None)
+            q8, sq = hip.rmsnorm_rope_q8(q, ca.norm_q.weight, nh, eps, q8=q8, sq=sq)
+        else:
+            q = hip.rmsnorm_rope(q, ca.norm_q.weight, nh, eps)
+        if kv_cache is not None and i in kv_cache:
+            ops = kv_cache[i]
+        else:      # 512 context rows, once per denoise loop with a kv_cache: library GEMM, adapters on the reference's torch ops
+            kv = lin.plain(ctx, (f"blocks.{i}.cross_attn.k", f"blocks.{i}.cross_attn.v"), wkv, bkv, w8[3], hip_adapters=False)
+            c = kv.shape[-1] // 2
+            if e4m3:
+                k, parts = hip.rmsnorm_rope_kstats(kv[..., :c], ca.norm_k.weight, nh, eps)
+                k8, sk, _ = hip.attn_quant_k(k, parts, nh)
+                vbufs = hip.attn_quant_vt(kv[..., c:], nh, smooth=self.cross_smooth)      # (v8t, sv, scratch[, mu])
+                ops = (k8, sk, vbufs[0], vbufs[1]) + tuple(vbufs[3:])
+            else:
+                ops = (hip.rmsnorm_rope(kv[..., :c], ca.norm_k.weight, nh, eps, batch=lin.batch_of(kv)), kv[..., c:])
+            if kv_cache is not None:
+                kv_cache[i] = ops
+        if not e4m3:
+            return self.attention(ca.attn, q, *ops)
+        k8, sk, v8t, sv = ops[:4]
+        return hip.attention_cross8_pre(q8, k8, sq, sk, v8t, sv, nh, mu=ops[4] if self.cross_smooth else None)
 
 
 class RMSNorm(nn.Module):
@@ -977,96 +1082,22 @@ class WanModel(nn.Module):
         x = x.view(b, f, h, w, px, py, pz, self.out_dim).permute(0, 7, 1, 4, 2, 5, 3, 6)
         return x.reshape(b, self.out_dim, f * px, h * py, w * pz)
 
-    def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, lin, w8, norm3=True):
+    def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, lin, att, w8, norm3=True):
         """Block i's self-attention half (reference :139-146, :225-226): h = modulate(norm1(x)) in (an Act); returns the residual stream
         after x += gate_msa * o(attn(...)) and h = norm3(x).  Yields right after each exchange of a token-sharded run has been started.
-        lin: the _BlockLinears of this forward; w8: the block's e4m3 weights (Nones in bf16 mode).  norm3=False: no h (returns None for it):
-        the stacked forward computes block 0's half once and norms the copies.  x (B, n, dim) with B > 1 (the stacked forward, unsharded):
-        the RoPE tables are one element's, the norm kernels and attention take the batch."""
-        c, nh, eps = self.dim, self.num_heads, self.eps
-        sharded = shard is not None and shard.active
+        lin, att: the _BlockLinears and _BlockAttention of this forward; w8: the block's e4m3 weights (Nones in bf16 mode).  norm3=False: no
+        h (returns None for it): the stacked forward computes block 0's half once and norms the copies.  x (B, n, dim) with B > 1 (the
+        stacked forward, unsharded): the RoPE tables are one element's, the norm kernels and attention take the batch."""
         wqkv, bqkv, _, _ = blk.fused_weights()
         sa = blk.self_attn
         # one GEMM for q | k | v, and one adapter launch on the fused buffer (hip backend) or one per projection on its column slice
         qkv = lin.plain(h, tuple(f"blocks.{i}.self_attn.{nm}" for nm in "qkv"), wqkv, bqkv, w8[0], own=GEMM_BACKEND == "all")
-        v = qkv[..., 2 * c:]
         # rope tables per operand: fp64 (cos, sin) for both, or the fp32 interleaved tables of k and q (rope_tables)
         rk, rq = ((cos, None), (sin, None)) if cos.dtype == torch.float32 else ((cos, sin), (cos, sin))
         scale = self.attn_scale()[0]      # None (1/sqrt(d)), or the power-of-two form that goes with the pre-multiplied q table
-        if not sharded and self.qk8_fused_producer and takes_qk8_attention(self, sa.attn, qkv.shape[1], qkv.shape[0]):
-            a = lin.attention_qk8_fused(sa, qkv, rq, rk, scale)
-        elif not sharded:
-            nb = lin.batch_of(qkv)
-            k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, batch=nb)
-            q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, batch=nb)
-            a = lin.attention(sa.attn, q, k, v, scale, self_attn=True)
-        elif shard.attn_mode == "ulysses":
-            # token shard -> head shard (all N tokens of 24/P heads), attention, head shard -> token shard.  The
-            # norm+RoPE kernels and one strided copy write q | k | v straight into the all-to-all send buffer.
-            n_loc, p_, size = x.shape[1], shard.world_size, shard.chunk(shard_total)
-            g = c // nh * shard.heads_local(nh)
-            send = shard.ulysses_send_buffer(shard_total, c, qkv, n_loc)           # (P, chunk, 3, g)
-            flat, layout = send.view(-1), (g, size * 3 * g, 3 * g)
-            hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, grouped=(flat, *layout))
-            hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, grouped=(flat[g:], *layout))
-            hip.copy_groups(qkv.view(-1)[2 * c:], g, 3 * c, flat[2 * g:], size * 3 * g, 3 * g, p_, n_loc, g)
-            pending = shard.ulysses_exchange_async(send, shard_total)
-            yield i
-            qg, kg, vg = pending.wait()
-            o_full = shard.ulysses_out_buffer(shard_total, g, qkv)
-            if takes_qk8_attention(self, sa.attn, shard_total, qkv.shape[0]):      # all N tokens of this rank's heads: every statistic is local
-                hip.attention_qk8(qg, kg, vg, shard.heads_local(nh), out=o_full[:shard_total].unsqueeze(0), scale=scale,
-                                  pv8=self.pv8_attention)
-            else:
-                hip.attention(qg, kg, vg, shard.heads_local(nh), out=o_full[:shard_total].unsqueeze(0), scale=scale)
-            pending = shard.ulysses_out_async(o_full, shard_total, n_loc)
-            yield i
-            a = torch.empty((1, n_loc, c), dtype=qkv.dtype, device=qkv.device)
-            hip.copy_groups(pending.wait_blocks().view(-1), size * g, g, a.view(-1), g, c, p_, n_loc, g)
-        elif takes_qk8_attention(self, sa.attn, shard_total, qkv.shape[0]):
-            a = yield from self._shard8_attention_steps(i, sa, qkv, rq, rk, scale, shard, shard_total)
-        else:
-            k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
-            pending = shard.all_gather_kv_async(k, v, shard_total)
-            q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)
-            yield i
-            k, v = pending.wait()
-            a = sa.attn(q, k, v) if scale is None else sa.attn(q, k, v, scale=scale)
+        a = yield from att.self_attention_steps(i, sa, qkv, rq, rk, scale, shard, shard_total)
         # x += gate_msa*y ; h = norm3(x)  (reference :225-226)
         return lin.residual(x, a, f"blocks.{i}.self_attn.o", sa.o.weight, sa.o.bias, w8[1], mod, 2, affine=blk.norm3 if norm3 else None)
-
-    def _shard8_attention_steps(self, i, sa, qkv, rq, rk, scale, shard, shard_total):
-        """Block i's self-attention in the e4m3 form on the K / V all-gather layout (enable_qk8_attention(sharded=True),
-        include/fairygen_hip_shard8.h): this rank's queries against all N keys.  Two exchanges, a yield after each has been started: the
-        ranks' statistics records (20 * C bytes each), from which every rank derives the unsharded key mean, sk and sv; then k8 and v (with
-        pv8: v8) through all_gather_kv_async, as uint8 views.  A rank without rows launches nothing and sends the neutral record."""
-        c, nh, eps, pv8 = self.dim, self.num_heads, self.eps, self.pv8_attention
-        n_loc, dev = qkv.shape[1], qkv.device
-        v = qkv[..., 2 * c:]
-        if n_loc:
-            k, parts = hip.rmsnorm_rope_kstats(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
-            record = hip.attn_shard8_stats(parts, n_loc, nh, v if pv8 else None)
-        else:
-            record = hip.attn_shard8_neutral_record(c, dev)
-        pending = shard.all_gather_records_async(record)
-        yield i
-        if n_loc:
-            q8, sq = hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)      # overlaps the record exchange
-            k8, v8, sk, _, sv = hip.attn_shard8_quant(pending.wait(), shard_total, k, nh, v if pv8 else None)
-            k8, v_send = k8.view(torch.uint8), (v8.view(torch.uint8) if pv8 else v[0])
-        else:
-            pending.wait()
-            k8 = torch.empty((0, c), dtype=torch.uint8, device=dev)
-            v_send = k8 if pv8 else v[0]
-        pending = shard.all_gather_kv_async(k8.unsqueeze(0), v_send.unsqueeze(0), shard_total)
-        yield i
-        k8f, vf = pending.wait()
-        if not n_loc:
-            return torch.empty((1, 0, c), dtype=qkv.dtype, device=dev)
-        k8f = k8f[0].view(torch.float8_e4m3fn)
-        if pv8:
-            return hip.attention_pv8_pre(q8, k8f, sq, sk, hip.attn_shard8_vt(vf[0].contiguous(), nh), sv, nh, scale=scale)
-        return hip.attention_qk8_pre(q8, k8f, sq, sk, vf, nh, scale=scale)
 
     # ------------------------------------------------------------------ the 30-block token forward
     def forward_tokens(self, x, context, mod_rows_t, t_rows, first_rows, rope, shard=None, shard_total=None, tea_cache=None,
@@ -1107,7 +1138,7 @@ class WanModel(nn.Module):
         The stacked CFG forward (enable_stacked_cfg): context (2, L, dim), everything else ONE element's.  x (1, n, dim): block 0's
         self-attention half, which does not see the context, is computed once on n rows and copied into both halves of the (2, n, dim)
         residual stream; x (2, n, dim): that half runs stacked as well.  Returns the head output (2, n, out)."""
-        c, nh, eps = self.dim, self.num_heads, self.eps
+        eps = self.eps
         cos, sin = rope
         x = x.contiguous()
         nb = context.shape[0]
@@ -1120,7 +1151,8 @@ class WanModel(nn.Module):
             blocks, x = [], tea_cache.update(x)
         fp8 = self.fp8_dtype
         self.check_qk8_layout(shard)
-        lin = _BlockLinears(self, mod_rows_t.shape[0], owned)      # the mode decisions of this forward
+        lin = _BlockLinears(self, mod_rows_t.shape[0], owned)      # the mode decisions of this forward: the Linears and norms,
+        att = _BlockAttention(self, lin, owned)                    # and attention
         ctx = Act(context, hip.fp8_quant_rows(context) if fp8 is not None else None)      # the text context is the same for all blocks
         mods = [hip.ModTable((blk.modulation.to(mod_rows_t.dtype) + mod_rows_t).contiguous(), first_rows) for blk in blocks]
         h = lin.modulate(x, mods[0], 0, 1) if blocks else None
@@ -1144,39 +1176,18 @@ class WanModel(nn.Module):
                 cfg_prefix["taken"] = True
                 h = lin.affine(x, blk.norm3)
             elif x.shape[0] != nb:      # stacked, i == 0: once on n rows, then norm3 over the copies' rows
-                x, _ = yield from self._self_attention_steps(i, blk, mod, x, h, cos, sin, shard, shard_total, lin, w8, norm3=False)
+                x, _ = yield from self._self_attention_steps(i, blk, mod, x, h, cos, sin, shard, shard_total, lin, att, w8, norm3=False)
                 x = x.expand(nb, -1, -1).contiguous()
                 h = lin.affine(x, blk.norm3)
             else:
                 if cfg_prefix is not None and i == 0:
                     cfg_prefix["owner"] = True
                 # --- self attention (reference :139-146)
-                x, h = yield from self._self_attention_steps(i, blk, mod, x, h, cos, sin, shard, shard_total, lin, w8)
+                x, h = yield from self._self_attention_steps(i, blk, mod, x, h, cos, sin, shard, shard_total, lin, att, w8)
                 if cfg_prefix is not None and i == 0:
                     cfg_prefix["x_sa"] = x.clone()
             # --- cross attention (reference :170-185)
-            qc = lin.plain(h, (f"blocks.{i}.cross_attn.q",), ca.q.weight, ca.q.bias, w8[2], own=lin.own)
-            if takes_cross8_attention(self, ca.attn, context.shape[1], qc.shape[0]):      # enable_qk8_attention(cross=True)
-                q8c, sqc = lin.cross8_q(qc, ca.norm_q, nh)
-                if kv_cache is not None and i in kv_cache:
-                    ops8 = kv_cache[i]
-                else:
-                    kvc = lin.plain(ctx, (f"blocks.{i}.cross_attn.k", f"blocks.{i}.cross_attn.v"), wkv_c, bkv_c, w8[3], hip_adapters=False)
-                    ops8 = lin.cross8_context(kvc, ca.norm_k, nh)
-                    if kv_cache is not None:
-                        kv_cache[i] = ops8
-                k8c, skc, v8tc, svc, *muc = ops8      # smooth_v_cross=True: the key means of v behind the four
-                ac = hip.attention_cross8_pre(q8c, k8c, sqc, skc, v8tc, svc, nh, mu=muc[0] if muc else None)
-            else:
-                qc = hip.rmsnorm_rope(qc, ca.norm_q.weight, nh, eps)
-                if kv_cache is not None and i in kv_cache:
-                    kc, vc = kv_cache[i]
-                else:      # 512 context rows, once per denoise loop with a kv_cache: library GEMM, adapters on the reference's torch ops
-                    kvc = lin.plain(ctx, (f"blocks.{i}.cross_attn.k", f"blocks.{i}.cross_attn.v"), wkv_c, bkv_c, w8[3], hip_adapters=False)
-                    kc, vc = hip.rmsnorm_rope(kvc[..., :c], ca.norm_k.weight, nh, eps, batch=lin.batch_of(kvc)), kvc[..., c:]
-                    if kv_cache is not None:
-                        kv_cache[i] = (kc, vc)
-                ac = lin.attention(ca.attn, qc, kc, vc)
+            ac = att.cross_attention(i, ca, h, ctx, kv_cache, wkv_c, bkv_c, w8)
             # x += y ; h = modulate(norm2(x))  (reference :226-227); with both norm outputs wanted, norm3's bf16 row is written over
             x, h = lin.residual(x, ac, f"blocks.{i}.cross_attn.o", ca.o.weight, ca.o.bias, w8[4], mod, None, modulate=(mod, 3, 4),
                                 out=h.bf16 if lin.want_q8 else None)

@@ -134,8 +134,7 @@ def test_enable_sets_the_routing():
     assert m.qk8_sharded is False and m.qk8_attention is False
     m.check_qk8_layout(Shard())
     # the predicate is takes_qk8_attention on the TOTAL key count: a shard of 200 rows of 1 600 keys takes the mode, one of 1 000 does not
-    src = open(os.path.join(REPO, "fairygen_amd", "wan_video_dit.py")).read()
-    assert src.count("takes_qk8_attention(self, sa.attn, shard_total, qkv.shape[0])") == 2      # ulysses and allgather
+    # (that the forward asks it about the total: test_emulated_ranks_equal_unsharded_forward counts the kernels)
     attn = m.blocks[0].self_attn.attn
     m.enable_qk8_attention(sharded=True)
     assert dit.takes_qk8_attention(m, attn, dit.QK8_MIN_KV + 1, 1) and not dit.takes_qk8_attention(m, attn, dit.QK8_MIN_KV, 1)
@@ -524,21 +523,36 @@ def test_emulated_ranks_equal_unsharded_forward(medium, attn_mode, world, pv8): 
     pinned by tests/test_attention_qk8.py and tests/test_attention_pv8.py.
 
     Measured on an MI355X: err_ref = 0.03223, bound 0.07446; max|emulated - unsharded| = 0.03125 (one bf16 ulp of a value in [4, 8)) in
-    all ten cases of either form."""
+    all ten cases of either form.
+
+    The routing goes by the TOTAL key count: every rank holds at most 650 rows, below QK8_MIN_KV, of 1 950 keys, above it, so in both
+    exchange modes every rank's self-attention of every block must run the e4m3 forward kernel and fg_attn_fwd_bf16 is left with
+    cross-attention alone.  A branch that asked takes_qk8_attention about its local rows fails the counts."""
+    from fairygen_amd import wan_video_dit
     from fairygen_amd.wan_video import model_fn_wan_video
     dit = medium.dit
     medium.setting(False, True)
+    names, real = [], _hip._call
+
+    def call(name, *args):
+        names.append(name)
+        return real(name, *args)
     try:
         with torch.no_grad():
             if pv8 not in _whole:
                 dit.enable_qk8_attention(pv8=pv8)
                 _whole[pv8] = model_fn_wan_video(dit, **medium.call).float().cpu()
             dit.enable_qk8_attention(pv8=pv8, sharded=True)
-            out, box = run_ranks(dit, world, attn_mode, **medium.call)
+            with pytest.MonkeyPatch.context() as patch:
+                patch.setattr(_hip, "_call", call)
+                out, box = run_ranks(dit, world, attn_mode, **medium.call)
     finally:
         dit.enable_qk8_attention(False)
     out, want = out.float().cpu(), _whole[pv8]
     assert box.completed == 2 * len(dit.blocks) and not box.slots, "not every exchange of every block ran"
+    assert -(-1950 // world) <= wan_video_dit.QK8_MIN_KV < 1950
+    assert names.count("fg_attn_fwd_pv8_bf16" if pv8 else "fg_attn_fwd_qk8_bf16") == world * len(dit.blocks), "self-attention routed by the local rows"
+    assert names.count("fg_attn_fwd_bf16") == world * len(dit.blocks), "fg_attn_fwd_bf16 ran for more than cross-attention"
     bound = 2 * medium.err_ref + 1e-2
     diff = (out - want).abs().max().item()
     print(f"emulated {attn_mode} P={world} {'pv8' if pv8 else 'qk8'}: max|emulated - unsharded| = {diff:.5f}, err_ref = {medium.err_ref:.5f}, "

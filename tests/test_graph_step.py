@@ -385,11 +385,14 @@ def test_eager_forward_calls_the_seams_as_before():
 
     class Model:
         eps, fp8_dtype, hot_loras, hot_lora_backend = 1e-6, None, {}, "torch"
+        qk8_fused_producer = pv8_attention = smoothv_attention = smoothv_cross_attention = False
     lin = wd._BlockLinears(Model(), 2)
     assert lin.owned is None and lin.state(1440, 3072, 6144) == {}
+    att = wd._BlockAttention(Model(), lin)
+    assert att.owned is None and att.workspace() == {}
     called = []
-    lin.attention(lambda *a, **kw: called.append((a, kw)), "q", "k", "v")
-    lin.attention(lambda *a, **kw: called.append((a, kw)), "q", "k", "v", 0.25)
+    att.attention(lambda *a, **kw: called.append((a, kw)), "q", "k", "v")
+    att.attention(lambda *a, **kw: called.append((a, kw)), "q", "k", "v", 0.25)
     assert called == [(("q", "k", "v"), {}), (("q", "k", "v"), {"scale": 0.25})]
     for name in ("gemm_bias_own", "gemm_bias_gelu_own", "gemm_fp8_own", "gemm_residual"):
         params = list(inspect.signature(getattr(wd, name)).parameters.values())
