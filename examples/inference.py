@@ -46,14 +46,18 @@ def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=Fals
         tokenizer_config=ModelConfig(path=tokenizer))
     if lora:
         pipe.load_lora(pipe.dit, lora, alpha=1)
-    if smooth_v and getattr(pipe, "parallel", None) is not None:
-        raise NotImplementedError("--smooth-v on a token-sharded layout: the key mean of V spans every rank's keys and the sharded mode's "
-                                  "statistics record has no V sum")
     if (qk8 or pv8) and getattr(pipe, "parallel", None) is not None:
-        # a token-sharded layout: the e4m3 mode with its statistics exchange (off by default; no multi-GPU hardware run exists); the e4m3
-        # cross-attention (--smooth-v-cross with it) is not run on token shards and is switched off here
-        pipe.dit.enable_qk8_attention(fused_producer=pipe.dit.qk8_fused_producer, pv8=pv8, sharded=True)
+        pipe.dit.enable_qk8_attention(**sharded_attention_switches(pipe.dit.qk8_fused_producer, pv8, cross8, smooth_v, smooth_v_cross))
     return pipe
+
+
+def sharded_attention_switches(fused_producer, pv8, cross8, smooth_v, smooth_v_cross):
+    """The enable_qk8_attention arguments of a token-sharded layout: the e4m3 mode with its statistics exchange (off by default; no
+    multi-GPU hardware run exists).  sharded=True, self-attention qk8 / pv8 alone, unless one of the forms that want sharded="all" is
+    asked for: V smoothing (the statistics record with a V sum), the e4m3 cross-attention, its V smoothing."""
+    every = bool(smooth_v or cross8 or smooth_v_cross)
+    return dict(fused_producer=fused_producer, pv8=pv8, cross=bool(cross8), smooth_v=bool(smooth_v), smooth_v_cross=bool(smooth_v_cross),
+                sharded="all" if every else True)
 
 
 def main():

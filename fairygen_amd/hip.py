@@ -235,6 +235,20 @@ _CROSS8S_QUERIES = {
 }
 CROSS8S_SYMBOLS = sorted(list(_CROSS8S_SIGNATURES) + list(_CROSS8S_QUERIES))    # what include/fairygen_hip_cross8s.h declares
 
+# The extension of include/fairygen_hip_shard8s.h (the operands of a token shard for the e4m3 P V form with V mean-smoothed: a record that
+# carries the fp64 sum, the minimum and the maximum of v beside those of k): a thirteenth pair.  The shard8 signatures, mu behind sv.
+SHARD8S_ABI_VERSION = 1   # fg_attn_shard8s_version
+_SHARD8S_SIGNATURES = {
+    "fg_attn_shard8s_stats": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp],
+    "fg_attn_shard8s_quant": [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
+}
+_SHARD8S_QUERIES = {
+    "fg_attn_shard8s_version": (_i32, []),
+    "fg_attn_shard8s_record_bytes": (_i64, [_i32]),
+    "fg_attn_shard8s_scratch_bytes": (_i64, [_i64, _i32]),
+}
+SHARD8S_SYMBOLS = sorted(list(_SHARD8S_SIGNATURES) + list(_SHARD8S_QUERIES))    # what include/fairygen_hip_shard8s.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -257,12 +271,14 @@ def load():
     for name, argtypes in list(_SIGNATURES.items()) + list(_PV8_SIGNATURES.items()) + list(_SHARD8_SIGNATURES.items()) + \
             list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()) + \
             list(_ROWBATCH8_SIGNATURES.items()) + list(_LORABATCH_SIGNATURES.items()) + list(_UP2PHASE_SIGNATURES.items()) + \
-            list(_GATEGEMM_SIGNATURES.items()) + list(_SMOOTHV_SIGNATURES.items()) + list(_CROSS8S_SIGNATURES.items()):
+            list(_GATEGEMM_SIGNATURES.items()) + list(_SMOOTHV_SIGNATURES.items()) + list(_CROSS8S_SIGNATURES.items()) + \
+            list(_SHARD8S_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
             list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()) + \
             list(_ROWBATCH8_QUERIES.items()) + list(_LORABATCH_QUERIES.items()) + list(_UP2PHASE_QUERIES.items()) + \
-            list(_GATEGEMM_QUERIES.items()) + list(_SMOOTHV_QUERIES.items()) + list(_CROSS8S_QUERIES.items()):
+            list(_GATEGEMM_QUERIES.items()) + list(_SMOOTHV_QUERIES.items()) + list(_CROSS8S_QUERIES.items()) + \
+            list(_SHARD8S_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
@@ -276,7 +292,8 @@ def load():
                                  ("fg_conv_up2phase_version", UP2PHASE_ABI_VERSION, " (upsample conv as four 2x2 phase convs)"),
                                  ("fg_gemm_gate_period_version", GATEGEMM_ABI_VERSION, " (gated GEMM store on batches that share a gate table)"),
                                  ("fg_attn_smoothv_version", SMOOTHV_ABI_VERSION, " (e4m3 P V with mean-smoothed V)"),
-                                 ("fg_attn_cross8s_version", CROSS8S_ABI_VERSION, " (e4m3 cross-attention with mean-smoothed V)")):
+                                 ("fg_attn_cross8s_version", CROSS8S_ABI_VERSION, " (e4m3 cross-attention with mean-smoothed V)"),
+                                 ("fg_attn_shard8s_version", SHARD8S_ABI_VERSION, " (e4m3 operands of a token shard, V mean-smoothed)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -1200,6 +1217,63 @@ def attn_shard8_vt(v8, num_heads, v8t=None):
         raise HipLibraryError(f"attn_shard8_vt: v8t must be {shape} contiguous")
     _call("fg_attn_shard8_vt", _ptr(v8), _ptr(v8t), n, num_heads, 128, _stream(v8))
     return v8t
+
+
+# ---- the same with V mean-smoothed (include/fairygen_hip_shard8s.h)
+def attn_shard8s_record_bytes(c):
+    need = load().fg_attn_shard8s_record_bytes(c)
+    if need < 0:
+        raise HipLibraryError(f"attn_shard8s_record_bytes: {load().fg_last_error().decode()}")
+    return need
+
+
+def attn_shard8s_neutral_record(c, device):
+    """The record of a rank without rows (sums 0, minima +inf, maxima -inf, of k and of v) as (32 * c,) uint8 on `device`."""
+    rec = torch.zeros(attn_shard8s_record_bytes(c), dtype=torch.uint8)
+    for at in (8 * c, 24 * c):
+        rec[at:at + 4 * c].view(torch.float32).fill_(float("inf"))
+        rec[at + 4 * c:at + 8 * c].view(torch.float32).fill_(float("-inf"))
+    return rec.to(device)
+
+
+def attn_shard8s_stats(partials, rows, num_heads, v, record=None):
+    """This rank's statistics record from rmsnorm_rope_kstats's partials of its `rows` local k rows and its v (1, rows, H*128) bf16 (a
+    column slice is fine) -> (32 * H * 128,) uint8: per channel the fp64 sum, the minimum and the maximum of k, then of v."""
+    c = num_heads * 128
+    _dev(partials, "partials", torch.uint8)
+    record = torch.empty(attn_shard8s_record_bytes(c), dtype=torch.uint8, device=partials.device) if record is None else record
+    ldv = _ld_rows(v, "v")
+    if v.shape != (1, rows, c):
+        raise HipLibraryError(f"attn_shard8s_stats: v must be (1, {rows}, {c}), got {tuple(v.shape)}")
+    need = load().fg_attn_shard8s_scratch_bytes(rows, c)
+    if need < 0:
+        raise HipLibraryError(f"attn_shard8s_stats: {load().fg_last_error().decode()}")
+    scratch = torch.empty(need, dtype=torch.uint8, device=v.device)
+    _call("fg_attn_shard8s_stats", _ptr(partials), partials.numel(), _ptr(v), ldv, _ptr(record), record.numel(), _ptr(scratch), scratch.numel(),
+          rows, num_heads, 128, _stream(partials))
+    return record
+
+
+def attn_shard8s_quant(records, n, k, num_heads, v, k8=None, v8=None):
+    """The gathered records (W, 32 * H * 128) uint8 and the key count n of all ranks -> the scales every rank agrees on, and this rank's
+    rows converted: k (1, rows, H*128) bf16 -> k8 (rows, H*128) e4m3; v likewise -> v8 = e4m3((v - mu) / sv) ROW-MAJOR.  Returns (k8, v8,
+    sk (H), kbar (H*128), sv (H, 128), mu (H, 128)): attn_shard8_vt(v8 of all ranks), sv and mu are attention_pv8_pre(mu=)'s."""
+    ldk, ldv = _ld_rows(k, "k"), _ld_rows(v, "v")
+    b, rows, hd = k.shape
+    _dev(records, "records", torch.uint8)
+    if b != 1 or hd != num_heads * 128 or v.shape != k.shape or records.dim() != 2 or not records.is_contiguous():
+        raise HipLibraryError(f"attn_shard8s_quant: k and v must be (1, rows, H*128) and records (W, 32*H*128), got {tuple(k.shape)}, "
+                              f"{tuple(v.shape)}, {tuple(records.shape)}")
+    f8 = torch.float8_e4m3fn
+    k8 = torch.empty((rows, hd), dtype=f8, device=k.device) if k8 is None else k8
+    v8 = torch.empty((rows, hd), dtype=f8, device=k.device) if v8 is None else v8
+    if any(t.shape != (rows, hd) or not t.is_contiguous() for t in (k8, v8)):
+        raise HipLibraryError("attn_shard8s_quant: k8 and v8 must be (rows, H*128) contiguous")
+    sk, kbar = torch.empty(num_heads, dtype=torch.float32, device=k.device), torch.empty(hd, dtype=torch.float32, device=k.device)
+    sv, mu = (torch.empty((num_heads, 128), dtype=torch.float32, device=k.device) for _ in range(2))
+    _call("fg_attn_shard8s_quant", _ptr(records), records.numel(), records.shape[0], n, _ptr(k), ldk, _ptr(v), ldv, _ptr(k8), _ptr(v8), _ptr(sk),
+          _ptr(kbar), _ptr(sv), _ptr(mu), rows, num_heads, 128, _stream(k))
+    return k8, v8, sk, kbar, sv, mu
 
 
 def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs=None, pv8=False, pv8_bufs=None, smooth=False):

@@ -479,21 +479,28 @@ class _BlockAttention:
         """Block i's self-attention in the e4m3 form on the K / V all-gather layout (enable_qk8_attention(sharded=True),
         include/fairygen_hip_shard8.h): this rank's queries against all N keys.  Two exchanges, a yield after each has been started: the
         ranks' statistics records (20 * C bytes each), from which every rank derives the unsharded key mean, sk and sv; then k8 and v (with
-        pv8: v8) through all_gather_kv_async, as uint8 views.  A rank without rows launches nothing and sends the neutral record."""
+        pv8: v8) through all_gather_kv_async, as uint8 views.  A rank without rows launches nothing and sends the neutral record.
+        With smooth_v (enable_qk8_attention(sharded="all"), include/fairygen_hip_shard8s.h) the record has 32 * C bytes — the fp64 sum,
+        the minimum and the maximum of v beside those of k — every rank derives the unsharded mu and sv from them, v8 is e4m3((v - mu) / sv)
+        and the attention adds mu back; the exchanges and their sizes, the record apart, are the same."""
         nh, eps, pv8 = sa.attn.num_heads, self.eps, self.pv8
+        smooth = pv8 and self.smooth
         c = qkv.shape[-1] // 3
         n_loc, dev = qkv.shape[1], qkv.device
         v = qkv[..., 2 * c:]
         if n_loc:
             k, parts = hip.rmsnorm_rope_kstats(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
-            record = hip.attn_shard8_stats(parts, n_loc, nh, v if pv8 else None)
+            record = hip.attn_shard8s_stats(parts, n_loc, nh, v) if smooth else hip.attn_shard8_stats(parts, n_loc, nh, v if pv8 else None)
         else:
-            record = hip.attn_shard8_neutral_record(c, dev)
+            record = (hip.attn_shard8s_neutral_record if smooth else hip.attn_shard8_neutral_record)(c, dev)
         pending = shard.all_gather_records_async(record)
         yield i
         if n_loc:
             q8, sq = hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)      # overlaps the record exchange
-            k8, v8, sk, _, sv = hip.attn_shard8_quant(pending.wait(), shard_total, k, nh, v if pv8 else None)
+            if smooth:
+                k8, v8, sk, _, sv, mu = hip.attn_shard8s_quant(pending.wait(), shard_total, k, nh, v)
+            else:
+                (k8, v8, sk, _, sv), mu = hip.attn_shard8_quant(pending.wait(), shard_total, k, nh, v if pv8 else None), None
             k8, v_send = k8.view(torch.uint8), (v8.view(torch.uint8) if pv8 else v[0])
         else:
             pending.wait()
@@ -506,7 +513,7 @@ class _BlockAttention:
             return torch.empty((1, 0, c), dtype=qkv.dtype, device=dev)
         k8f = k8f[0].view(torch.float8_e4m3fn)
         if pv8:
-            return hip.attention_pv8_pre(q8, k8f, sq, sk, hip.attn_shard8_vt(vf[0].contiguous(), nh), sv, nh, scale=scale)
+            return hip.attention_pv8_pre(q8, k8f, sq, sk, hip.attn_shard8_vt(vf[0].contiguous(), nh), sv, nh, scale=scale, mu=mu)
         return hip.attention_qk8_pre(q8, k8f, sq, sk, vf, nh, scale=scale)
 
     # ---- cross-attention
@@ -520,6 +527,9 @@ class _BlockAttention:
         fg_attn_quant_vt_bf16 on v.  With smooth_v_cross=True the V producer is the smoothing one and the key means of v follow as a
         fifth tensor, mu."""
         lin, nh, eps = self.lin, ca.attn.num_heads, self.eps
+        rows = h.bf16 if h.bf16 is not None else h.q8[0]
+        if rows.shape[-2] == 0:      # a token shard without rows: nothing to attend from, nothing is launched
+            return torch.empty((1, 0, ca.q.weight.shape[0]), dtype=ca.q.weight.dtype, device=rows.device)
         q = lin.plain(h, (f"blocks.{i}.cross_attn.q",), ca.q.weight, ca.q.bias, w8[2], own=lin.own)
         e4m3 = takes_cross8_attention(self.model, ca.attn, ctx.rows, q.shape[0])
         if e4m3:
@@ -775,6 +785,14 @@ class WanModel(nn.Module):
         (include/fairygen_hip.h); the attention kernels are the same.  Composes with enable_fp8_linear, hot adapters and cfg_parallel=2 (the
         shard is then the half-group); graph=True with a shard raises as before; attn_mode="windows" has no exchange in a forward and
         is not affected.  No multi-GPU hardware run of this project exists: the mode is tested with emulated ranks on one GPU.
+        sharded="all": every e4m3 form that is switched on also runs on an active token shard — what True covers, and smooth_v, cross
+        and smooth_v_cross, which True keeps refusing.  smooth_v on attn_mode="allgather" (include/fairygen_hip_shard8s.h): the record
+        carries for v what it carries for k (fp64 sum, minimum, maximum: 32 * C bytes in place of 20 * C), every rank derives the
+        unsharded mu and sv from the W records, v8 = e4m3((v - mu) / sv) crosses the wire and fg_attn_fwd_pv8s_bf16 adds mu back; the
+        operands are byte for byte the unsharded smoothing producer's where the fp64 sums are exact.  On attn_mode="ulysses" it is
+        local like every other statistic.  cross / smooth_v_cross: the context is whole on every rank and the kernel is row-wise in
+        the queries, so a shard's queries give that shard's rows and nothing is exchanged.  A rank without rows launches nothing.
+        Any other value of sharded raises ValueError; m.qk8_sharded holds the value given.
         cross: cross-attention over the text context in the e4m3 form as well, as the reference's sageattn call covers it
         (include/fairygen_hip_cross8.h).  It needs flag and pv8 (the operands are those of the e4m3 P V form).  Only the stock
         AttentionModule, one batch element and a context of at most hip.attention_cross8_max_kv() keys take it (takes_cross8_attention).
@@ -782,18 +800,18 @@ class WanModel(nn.Module):
         quantised where its k | v rows are computed — once per denoise loop with a kv_cache, which then holds (k8, sk, v8t, sv) in place
         of (k, v); per call without one (sliding windows) — and fg_attn_fwd_cross8_bf16 keeps a head's K8 and V8^T in LDS while it walks
         the query blocks.  Composes with enable_fp8_linear, hot adapters and graph=True (the captured step owns the q8 / sq buffers, the
-        context operands live in the loop's kv_cache).  An active token shard raises NotImplementedError, sharded=True or not: the
-        query rows are local and the context is whole on every rank, so no collective would be needed, but no sharded run of it has
-        been tested.
+        context operands live in the loop's kv_cache).  An active token shard raises NotImplementedError, with sharded=True too:
+        sharded="all" asks for it (above).
         smooth_v: off by default.  The e4m3 P V product with V mean-smoothed, what sageattn ships as smooth_v
         (include/fairygen_hip_smoothv.h): the key mean of every head and channel leaves v before it is quantised
         (fg_attn_quant_vt_smooth_bf16 in place of fg_attn_quant_vt_bf16) and joins the output row in fp32 before its rounding to bf16
         (fg_attn_fwd_pv8s_bf16 in place of fg_attn_fwd_pv8_bf16), so the rounding of P no longer scales the part of V that all keys
         share and the e4m3 range covers the spread alone.  It needs pv8 (ValueError without), has its routing, works behind either
         producer path and composes with enable_fp8_linear, hot adapters, graph=True (the captured step owns mu next to sv) and the
-        stacked CFG forward (the batched entry points).  It does NOT run on token shards, sharded=True or not: the mean spans every
-        rank's keys and the statistics record of include/fairygen_hip_shard8.h carries no V sum — together with sharded=True it raises
-        ValueError here, and an active shard raises NotImplementedError at the forward.  With cross=True it smooths self-attention
+        stacked CFG forward (the batched entry points).  It does not run on token shards with sharded=True or False: the mean spans
+        every rank's keys and the statistics record of include/fairygen_hip_shard8.h carries no V sum — together with sharded=True it
+        raises ValueError here, and an active shard raises NotImplementedError at the forward; sharded="all" exchanges the record that
+        has one (above).  With cross=True it smooths self-attention
         only: the e4m3 cross-attention has a switch of its own (below).
         smooth_v_cross: off by default, independent of smooth_v.  The same smoothing for the e4m3 cross-attention
         (include/fairygen_hip_cross8s.h): the context is zeroed behind the prompt's length and the k / v Linears act row by row, so most
@@ -801,9 +819,13 @@ class WanModel(nn.Module):
         goes through fg_attn_quant_vt_smooth_bf16, the kv_cache holds (k8, sk, v8t, sv, mu), still quantised once per denoise loop, and
         fg_attn_fwd_cross8s_bf16 (batched: _b, the stacked CFG forward) takes the place of fg_attn_fwd_cross8_bf16.  It needs flag, pv8
         and cross (ValueError without, and nothing changes); composes with what cross composes with, graph=True included (the context
-        is quantised in the eager first step, replays only read it); an active token shard raises as for cross."""
+        is quantised in the eager first step, replays only read it); an active token shard raises as for cross, and runs as cross
+        does with sharded="all"."""
         if pv8 and not flag:
             raise ValueError("enable_qk8_attention(pv8=True) needs the e4m3 Q K^T mode on (flag=True)")
+        if not (isinstance(sharded, bool) or sharded == "all"):
+            raise ValueError(f"enable_qk8_attention(sharded={sharded!r}): sharded is False, True (self-attention qk8 / pv8 on token shards) or "
+                             "'all' (every e4m3 form that is switched on)")
         if sharded and not flag:
             raise ValueError("enable_qk8_attention(sharded=True) needs the e4m3 Q K^T mode on (flag=True)")
         if cross and not (flag and pv8):
@@ -811,16 +833,17 @@ class WanModel(nn.Module):
         if smooth_v and not (flag and pv8):
             raise ValueError("enable_qk8_attention(smooth_v=True) needs the e4m3 Q K^T mode and its e4m3 P V form on (flag=True, pv8=True): "
                              "it is V of that product that is mean-smoothed")
-        if smooth_v and sharded:
+        if smooth_v and sharded is True:
             raise ValueError("enable_qk8_attention(smooth_v=True, sharded=True): the key mean of V spans every rank's keys and the statistics "
-                             "record of the sharded mode (include/fairygen_hip_shard8.h) has no V sum; run token shards without smooth_v")
+                             "record of the sharded mode (include/fairygen_hip_shard8.h) has no V sum; run token shards without smooth_v, or "
+                             "with sharded='all' (the record of include/fairygen_hip_shard8s.h)")
         if smooth_v_cross and not (flag and pv8 and cross):
             raise ValueError("enable_qk8_attention(smooth_v_cross=True) needs the e4m3 cross-attention on (flag=True, pv8=True, cross=True): "
                              "it is V of that product that is mean-smoothed")
         self.qk8_attention = bool(flag)
         self.qk8_fused_producer = bool(flag) and bool(fused_producer)
         self.pv8_attention = bool(flag) and bool(pv8)
-        self.qk8_sharded = bool(flag) and bool(sharded)
+        self.qk8_sharded = sharded if flag else False      # False, True or "all"
         self.cross8_attention = bool(flag) and bool(pv8) and bool(cross)
         self.smoothv_attention = bool(flag) and bool(pv8) and bool(smooth_v)
         self.smoothv_cross_attention = self.cross8_attention and bool(smooth_v_cross)
@@ -883,13 +906,16 @@ class WanModel(nn.Module):
             raise NotImplementedError(f"stacked_cfg stacks the CFG pair: a context batch of 2, not {context_batch}")
 
     def check_qk8_layout(self, shard):
-        if self.smoothv_attention and shard is not None and shard.active:
+        """What an active token shard must not meet: the e4m3 mode without sharded=, and smooth_v, cross and smooth_v_cross (which needs
+        cross) without sharded="all"."""
+        every = self.qk8_sharded == "all"
+        if self.smoothv_attention and not every and shard is not None and shard.active:
             raise NotImplementedError("enable_qk8_attention(smooth_v=True) with a token-sharded layout: the key mean of V spans every rank's "
                                       "keys and the statistics record of the sharded mode has no V sum; switch it off (smooth_v=False) for a "
-                                      "sharded run")
-        if self.cross8_attention and shard is not None and shard.active:
+                                      "sharded run, or ask for the record that has one (sharded='all')")
+        if self.cross8_attention and not every and shard is not None and shard.active:
             raise NotImplementedError("enable_qk8_attention(cross=True) with a token-sharded layout: the e4m3 cross-attention has not been "
-                                      "run on token shards; switch it off (cross=False) for a sharded run")
+                                      "run on token shards; switch it off (cross=False) for a sharded run, or ask for it (sharded='all')")
         if self.qk8_attention and not self.qk8_sharded and shard is not None and shard.active:
             raise NotImplementedError("enable_qk8_attention() with a token-sharded layout: the key mean and the per-head key scale of the e4m3 "
                                       "Q K^T form span all ranks' tokens and would need a collective; enable_qk8_attention(sharded=True) "
@@ -1082,6 +1108,32 @@ class WanModel(nn.Module):
         x = x.view(b, f, h, w, px, py, pz, self.out_dim).permute(0, 7, 1, 4, 2, 5, 3, 6)
         return x.reshape(b, self.out_dim, f * px, h * py, w * pz)
 
+    def _empty_rank_steps(self, x, blocks, shard, shard_total, att, cfg_prefix):
+        """The forward of a rank of the K / V all-gather layout that holds no token rows (the ceil split leaves trailing ranks empty when
+        N is small against the world): it launches nothing, takes its part in every exchange of every block — the neutral statistics
+        record and no k8 / v rows in the e4m3 form, no k / v rows in bf16 — in the order the other ranks run them, cfg_prefix included,
+        and returns an empty head output (1, 0, out)."""
+        c = self.dim
+        qkv = x.new_empty((1, 0, 3 * c))
+        for i, blk in enumerate(blocks):
+            if cfg_prefix is not None and i == 0:
+                if "owner" in cfg_prefix:      # the other branch of the step runs block 0's exchanges
+                    while "x_sa" not in cfg_prefix:
+                        yield i
+                    cfg_prefix.pop("x_sa")
+                    cfg_prefix["taken"] = True
+                    continue
+                cfg_prefix["owner"] = True
+            if takes_qk8_attention(self, blk.self_attn.attn, shard_total, 1):
+                yield from att._shard8_steps(i, blk.self_attn, qkv, None, None, None, shard, shard_total)
+            else:
+                pending = shard.all_gather_kv_async(qkv[..., c:2 * c], qkv[..., 2 * c:], shard_total)
+                yield i
+                pending.wait()
+            if cfg_prefix is not None and i == 0:
+                cfg_prefix["x_sa"] = x
+        return x.new_empty((1, 0, self.head.head.weight.shape[0]))
+
     def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, lin, att, w8, norm3=True):
         """Block i's self-attention half (reference :139-146, :225-226): h = modulate(norm1(x)) in (an Act); returns the residual stream
         after x += gate_msa * o(attn(...)) and h = norm3(x).  Yields right after each exchange of a token-sharded run has been started.
@@ -1153,6 +1205,8 @@ class WanModel(nn.Module):
         self.check_qk8_layout(shard)
         lin = _BlockLinears(self, mod_rows_t.shape[0], owned)      # the mode decisions of this forward: the Linears and norms,
         att = _BlockAttention(self, lin, owned)                    # and attention
+        if x.shape[1] == 0 and tea_cache is None and shard is not None and shard.active and shard.attn_mode == "allgather":
+            return (yield from self._empty_rank_steps(x, blocks, shard, shard_total, att, cfg_prefix))
         ctx = Act(context, hip.fp8_quant_rows(context) if fp8 is not None else None)      # the text context is the same for all blocks
         mods = [hip.ModTable((blk.modulation.to(mod_rows_t.dtype) + mod_rows_t).contiguous(), first_rows) for blk in blocks]
         h = lin.modulate(x, mods[0], 0, 1) if blocks else None

@@ -48,7 +48,8 @@ def shard8(a):
     """--shard8: one rank's attention chain of the K / V all-gather layout, from its rows of the q | k | v buffer to its attention output, at
     nq = ceil(nkv / world) local rows against nkv keys: 'chain-bf16' (RMSNorm+RoPE x 2, gather of k and v, fg_attn_fwd_bf16), 'chain-qk8-sharded'
     and 'chain-pv8-sharded' (enable_qk8_attention(sharded=True): key statistics, record, e4m3 q, quantise, gather of the e4m3 bytes, the
-    transpose pass, the e4m3 attention).  ONE process, ONE GPU: local copies of the same size stand in for the collectives, so nothing here
+    transpose pass, the e4m3 attention) and 'chain-pv8s-sharded' (sharded="all" with smooth_v: the 32 C byte record, v8 of v - mu, the
+    attention that adds mu back).  ONE process, ONE GPU: local copies of the same size stand in for the collectives, so nothing here
     says anything about xGMI.  Then the HBM-bound passes alone with their achieved GB/s, beside fg_attn_quant_vt_bf16 on the same rows."""
     dev, heads, n = "cuda", a.heads, a.nkv
     c, nl = heads * 128, -(-a.nkv // a.world)
@@ -80,14 +81,26 @@ def shard8(a):
         else:
             hip.attention_qk8_pre(q8, k8f, sq, sk, gather(vs[0]).unsqueeze(0), heads, out=out)
 
+    def chain_8s():
+        k, parts = hip.rmsnorm_rope_kstats(ks, w, heads, 1e-6, tab)
+        rec = hip.attn_shard8s_stats(parts, nl, heads, vs)
+        q8, sq = hip.rmsnorm_rope_q8(qs, w, heads, 1e-6, tab)
+        k8, v8, sk, _, sv, mu = hip.attn_shard8s_quant(rec.view(1, -1).repeat(a.world, 1), n, k, heads, vs)
+        k8f = gather(k8.view(torch.uint8)).view(torch.float8_e4m3fn)
+        hip.attention_pv8_pre(q8, k8f, sq, sk, hip.attn_shard8_vt(gather(v8.view(torch.uint8)), heads), sv, heads, out=out, mu=mu)
+
     k, parts = hip.rmsnorm_rope_kstats(ks, w, heads, 1e-6, tab)
     rec = hip.attn_shard8_stats(parts, nl, heads, vs).view(1, -1).repeat(a.world, 1)
+    rec_s = hip.attn_shard8s_stats(parts, nl, heads, vs).view(1, -1).repeat(a.world, 1)
     v8_full = torch.empty((n, c), dtype=torch.uint8, device=dev).random_(0, 120)
     vt_bufs = hip.attention_pv8_scratch(nl, heads, 128, dev)
     mb = nl * c / 1e6
     fns = [("chain-bf16", chain_bf16, None), ("chain-qk8-sharded", lambda: chain_8(False), None), ("chain-pv8-sharded", lambda: chain_8(True), None),
+           ("chain-pv8s-sharded", chain_8s, None),
            ("shard8-stats (v)", lambda: hip.attn_shard8_stats(parts, nl, heads, vs), 2 * mb),
+           ("shard8s-stats (v)", lambda: hip.attn_shard8s_stats(parts, nl, heads, vs), 2 * mb),
            ("shard8-quant (k, v)", lambda: hip.attn_shard8_quant(rec, n, k, heads, vs), 6 * mb),
+           ("shard8s-quant (k, v)", lambda: hip.attn_shard8s_quant(rec_s, n, k, heads, vs), 6 * mb),
            ("shard8-vt", lambda: hip.attn_shard8_vt(v8_full, heads), 2 * n * c / 1e6),
            ("quant-vt (same rows)", lambda: hip.attn_quant_vt(vs, heads, vt_bufs), 5 * mb)]
     times = {name: [] for name, _, _ in fns}
@@ -104,8 +117,8 @@ def shard8(a):
           "local copies stand in for the collectives (no xGMI figure)")
     for name, _, mbytes in fns:
         t = sorted(times[name][a.iters:])
-        med = t[len(t) // 2]
-        print(f"{name:24s} {med:8.3f} ms" + (f"   {mbytes / med:7.0f} GB/s ({mbytes:.1f} MB read + written)" if mbytes else ""), flush=True)
+        med, sd = t[len(t) // 2], torch.tensor(t).std().item()
+        print(f"{name:24s} {med:8.3f} ms  (sd {sd:.3f})" + (f"   {mbytes / med:7.0f} GB/s ({mbytes:.1f} MB read + written)" if mbytes else ""), flush=True)
 
 
 def padded_context_v(l_text, l=512, heads=24, seed=180, device="cuda"):

@@ -3,10 +3,11 @@ same size (no xGMI), so a step's time is what rank 0 of a P-rank job computes pl
 communication-free upper bound of the scaling the driver's 8-GPU run can reach, and the place to see which layout
 loses how much to small shapes.
 
-    python tools/shard_dryrun.py [--steps 2] [--worlds 2,4,8] [--attention {bf16,qk8,pv8}]
+    python tools/shard_dryrun.py [--steps 2] [--worlds 2,4,8] [--attention {bf16,qk8,pv8,pv8-cross,full}]
 
 --attention qk8 / pv8: the e4m3 self-attention on the sharded layouts (enable_qk8_attention(sharded=True)), the single-GPU line in the
-same mode; the record exchange is a local copy like the others.
+same mode; the record exchange is a local copy like the others.  pv8-cross: with the e4m3 cross-attention as well; full: that with both
+V smoothings (enable_qk8_attention(pv8=True, cross=True, smooth_v=True, smooth_v_cross=True, sharded="all")).
 """
 import argparse
 import os
@@ -79,16 +80,20 @@ def main():
     ap.add_argument("--height", type=int, default=704)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--frames", type=int, default=121)
-    ap.add_argument("--attention", choices=("bf16", "qk8", "pv8"), default="bf16", help="self-attention form of every line (default: bf16)")
+    ap.add_argument("--attention", choices=("bf16", "qk8", "pv8", "pv8-cross", "full"), default="bf16",
+                    help="attention form of every line (default: bf16)")
     a = ap.parse_args()
     args = argparse.Namespace(layers=0, no_lora=True, height=a.height, width=a.width, frames=a.frames)
     device = "cuda:0"
     sp._staged = lambda t, group: True                       # take the synchronous branch of the pending objects ...
     sp._all_to_all_rows = _copy_rows                         # ... and copy instead of exchanging
     pipe, cfg = bench.build_pipeline(args, device)
-    if a.attention != "bf16":
+    if a.attention in ("qk8", "pv8"):
         pipe.dit.enable_qk8_attention(pv8=a.attention == "pv8", sharded=True)
-    print(f"self-attention: {a.attention}")
+    elif a.attention != "bf16":
+        full = a.attention == "full"
+        pipe.dit.enable_qk8_attention(pv8=True, fused_producer=True, cross=True, smooth_v=full, smooth_v_cross=full, sharded="all")
+    print(f"attention: {a.attention}")
     lat_shape = (1, 48, (a.frames - 1) // 4 + 1, a.height // 16, a.width // 16)
     noise = bench.seeded(lat_shape, 1).to(device)
     ctx_p, ctx_n = bench.seeded((1, 512, 4096), 2).to(device), bench.seeded((1, 512, 4096), 3).to(device)
