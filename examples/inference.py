@@ -48,7 +48,24 @@ def build_pipeline(weights, tokenizer, lora=None, fp8=False, qk8=False, pv8=Fals
         pipe.load_lora(pipe.dit, lora, alpha=1)
     if (qk8 or pv8) and getattr(pipe, "parallel", None) is not None:
         pipe.dit.enable_qk8_attention(**sharded_attention_switches(pipe.dit.qk8_fused_producer, pv8, cross8, smooth_v, smooth_v_cross))
+    if stacked_cfg and stacked_cfg_on_layout(getattr(pipe, "parallel", None)):
+        if fp8 and (qk8 or pv8):
+            raise SystemExit("--stacked-cfg on a parallel layout with --fp8 AND an e4m3 attention form: that composition is not carried on "
+                             "token shards (WanModel.check_stacked_cfg); drop --fp8 or the e4m3 attention switches, or drop --stacked-cfg")
+        d = pipe.dit      # restate what the loader switched on: a call that does not restate a form clears it
+        d.enable_stacked_cfg(fp8_linear=d.stacked_cfg_fp8, hot_lora=d.stacked_cfg_hot_lora, periodic_gate=d.stacked_cfg_periodic_gate, sharded=True)
     return pipe
+
+
+def stacked_cfg_on_layout(layout):
+    """Whether --stacked-cfg needs enable_stacked_cfg(sharded=True): False on a single GPU; True on a parallel layout that the stacked
+    forward takes, the K / V all-gather exchange with cfg_parallel=1; any other parallel layout is an error said here, before anything runs."""
+    if layout is None or layout.shard is None or not layout.shard.active:
+        return False
+    if layout.cfg_parallel != 1 or layout.attn_mode != "allgather":
+        raise SystemExit(f"--stacked-cfg on the parallel layout {layout.describe()}: the stacked CFG forward runs on token shards of the K / V "
+                         "all-gather layout with cfg_parallel=1 only (attn_mode='allgather'); use that layout, or drop --stacked-cfg")
+    return True
 
 
 def sharded_attention_switches(fused_producer, pv8, cross8, smooth_v, smooth_v_cross):
@@ -82,7 +99,8 @@ def main():
                     help="with e4m3 cross-attention: the same smoothing for V of the text context, most of whose 512 keys carry one padding "
                          "row (ModelConfig(cross_attention_v_smoothing=True)); independent of --smooth-v; implies --cross8-attention")
     ap.add_argument("--stacked-cfg", action="store_true",
-                    help="both CFG branches in ONE stacked forward of the DiT per step (implies cfg_merge=True); single GPU, bf16 Linears or, "
+                    help="both CFG branches in ONE stacked forward of the DiT per step (implies cfg_merge=True); single GPU, or a parallel layout "
+                         "with the K / V all-gather exchange and cfg_parallel=1 (enable_stacked_cfg(sharded=True)); bf16 Linears or, "
                          "with --fp8, the fp8 Linear mode (the loader then calls enable_stacked_cfg(fp8_linear=True)); --lora here is fused into the weights and works; unfused hot-loaded "
                          "adapters need hot_backend='hip' and ModelConfig(stacked_cfg_hot_lora=True)")
     ap.add_argument("--stacked-cfg-periodic-gate", action="store_true",

@@ -249,6 +249,22 @@ _SHARD8S_QUERIES = {
 }
 SHARD8S_SYMBOLS = sorted(list(_SHARD8S_SIGNATURES) + list(_SHARD8S_QUERIES))    # what include/fairygen_hip_shard8s.h declares
 
+# The extension of include/fairygen_hip_shard8b.h (the producers of the two token-shard extensions on a batch: the stacked CFG forward on a
+# rank of the K / V all-gather layout): a fourteenth pair, the thirteenth extension.  The single forms' signatures with an element stride
+# behind every input's leading dimension and B in front of the row count.
+SHARD8B_ABI_VERSION = 1   # fg_attn_shard8b_version
+_SHARD8B_SIGNATURES = {
+    "fg_attn_shard8_stats_b": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i64, _i32, _i32, _vp],
+    "fg_attn_shard8_quant_b": [_vp, _i64, _i32, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp],
+    "fg_attn_shard8_vt_b": [_vp, _i64, _vp, _i32, _i64, _i32, _i32, _vp],
+    "fg_attn_shard8s_stats_b": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i64, _i32, _i32, _vp],
+    "fg_attn_shard8s_quant_b": [_vp, _i64, _i32, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp],
+}
+_SHARD8B_QUERIES = {
+    "fg_attn_shard8b_version": (_i32, []),
+}
+SHARD8B_SYMBOLS = sorted(list(_SHARD8B_SIGNATURES) + list(_SHARD8B_QUERIES))    # what include/fairygen_hip_shard8b.h declares
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -272,13 +288,13 @@ def load():
             list(_CROSS8_SIGNATURES.items()) + list(_BATCH8_SIGNATURES.items()) + list(_ROWBATCH_SIGNATURES.items()) + \
             list(_ROWBATCH8_SIGNATURES.items()) + list(_LORABATCH_SIGNATURES.items()) + list(_UP2PHASE_SIGNATURES.items()) + \
             list(_GATEGEMM_SIGNATURES.items()) + list(_SMOOTHV_SIGNATURES.items()) + list(_CROSS8S_SIGNATURES.items()) + \
-            list(_SHARD8S_SIGNATURES.items()):
+            list(_SHARD8S_SIGNATURES.items()) + list(_SHARD8B_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = _i32, argtypes
     for name, (restype, argtypes) in list(_QUERIES.items()) + list(_PV8_QUERIES.items()) + list(_SHARD8_QUERIES.items()) + \
             list(_CROSS8_QUERIES.items()) + list(_BATCH8_QUERIES.items()) + list(_ROWBATCH_QUERIES.items()) + \
             list(_ROWBATCH8_QUERIES.items()) + list(_LORABATCH_QUERIES.items()) + list(_UP2PHASE_QUERIES.items()) + \
             list(_GATEGEMM_QUERIES.items()) + list(_SMOOTHV_QUERIES.items()) + list(_CROSS8S_QUERIES.items()) + \
-            list(_SHARD8S_QUERIES.items()):
+            list(_SHARD8S_QUERIES.items()) + list(_SHARD8B_QUERIES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     for name, expected, what in (("fg_version", ABI_VERSION, ""), ("fg_attn_qk8_version", QK8_ABI_VERSION, " (e4m3 Q K^T extension)"),
                                  ("fg_attn_qk8_fused_version", QK8F_ABI_VERSION, " (fused e4m3 producers)"),
@@ -293,7 +309,8 @@ def load():
                                  ("fg_gemm_gate_period_version", GATEGEMM_ABI_VERSION, " (gated GEMM store on batches that share a gate table)"),
                                  ("fg_attn_smoothv_version", SMOOTHV_ABI_VERSION, " (e4m3 P V with mean-smoothed V)"),
                                  ("fg_attn_cross8s_version", CROSS8S_ABI_VERSION, " (e4m3 cross-attention with mean-smoothed V)"),
-                                 ("fg_attn_shard8s_version", SHARD8S_ABI_VERSION, " (e4m3 operands of a token shard, V mean-smoothed)")):
+                                 ("fg_attn_shard8s_version", SHARD8S_ABI_VERSION, " (e4m3 operands of a token shard, V mean-smoothed)"),
+                                 ("fg_attn_shard8b_version", SHARD8B_ABI_VERSION, " (e4m3 operands of a token shard on batches)")):
         if getattr(lib, name)() != expected:
             raise HipLibraryError(f"ABI mismatch{what}: library {getattr(lib, name)()} != binding {expected}")
     _lib = lib
@@ -1146,7 +1163,8 @@ def attention_cross8_pre(q8, k8, sq, sk, v8t, sv, num_heads, out=None, scale=Non
     return _fwd8("cross8", q8, k8, sq, sk, v8t, sv, mu, out, b, nq, hd, nkv, num_heads, (_softmax_scale(d, scale),))
 
 
-# ---- the e4m3 operands of a token shard (include/fairygen_hip_shard8.h)
+# ---- the e4m3 operands of a token shard (include/fairygen_hip_shard8.h); with a leading batch dimension B > 1 on their tensors the same
+# wrappers take the batched entry points of include/fairygen_hip_shard8b.h (the stacked CFG forward on a shard); B = 1 is the single form
 def attn_shard8_record_bytes(c):
     need = load().fg_attn_shard8_record_bytes(c)
     if need < 0:
@@ -1154,59 +1172,109 @@ def attn_shard8_record_bytes(c):
     return need
 
 
-def attn_shard8_neutral_record(c, device):
-    """The record of a rank without rows (sum 0, minimum +inf, maximum -inf, |v| maximum 0) as (20 * c,) uint8 on `device`."""
+def attn_shard8_neutral_record(c, device, batch=1):
+    """The record of a rank without rows (sum 0, minimum +inf, maximum -inf, |v| maximum 0) as (20 * c,) uint8 on `device`; batch=B > 1:
+    B of them, (B, 20 * c)."""
     rec = torch.zeros(attn_shard8_record_bytes(c), dtype=torch.uint8)
     rec[8 * c:12 * c].view(torch.float32).fill_(float("inf"))
     rec[12 * c:16 * c].view(torch.float32).fill_(float("-inf"))
-    return rec.to(device)
+    return (rec.expand(batch, -1).contiguous() if batch > 1 else rec).to(device)
+
+
+def _shard8_stats(smooth, partials, rows, num_heads, v, record):
+    """attn_shard8_stats / attn_shard8s_stats: one element (partials flat, v (1, rows, C)), or B > 1 (partials (B, bytes), v (B, rows, C))."""
+    who = "attn_shard8s_stats" if smooth else "attn_shard8_stats"
+    c = num_heads * 128
+    _dev(partials, "partials", torch.uint8)
+    lead = (partials.shape[0],) if partials.dim() == 2 and partials.shape[0] > 1 else ()
+    b = lead[0] if lead else 1
+    unit = (attn_shard8s_record_bytes if smooth else attn_shard8_record_bytes)(c)
+    record = torch.empty(lead + (unit,), dtype=torch.uint8, device=partials.device) if record is None else record
+    scratch, ldv, need = None, 0, 0
+    if v is not None:
+        ldv = _ld_rows(v, "v")
+        if v.shape != (b, rows, c):
+            raise HipLibraryError(f"{who}: v must be ({b}, {rows}, {c}), got {tuple(v.shape)}")
+        need = (load().fg_attn_shard8s_scratch_bytes if smooth else load().fg_attn_shard8_scratch_bytes)(rows, c)
+        if need < 0:
+            raise HipLibraryError(f"{who}: {load().fg_last_error().decode()}")
+        scratch = torch.empty(lead + (need,), dtype=torch.uint8, device=v.device)
+    if lead:
+        if partials.stride(1) != 1 or record.shape != (b, unit) or not record.is_contiguous():
+            raise HipLibraryError(f"{who}: a batch takes partials (B, bytes) and records (B, {unit}) contiguous")
+        _call(f"fg_attn_shard8{'s' if smooth else ''}_stats_b", _ptr(partials), partials.shape[1], partials.stride(0), _ptr(v), ldv,
+              v.stride(0) if v is not None else 0, _ptr(record), record.numel(), _ptr(scratch), need, need, b, rows, num_heads, 128,
+              _stream(partials))
+        return record
+    _call(f"fg_attn_shard8{'s' if smooth else ''}_stats", _ptr(partials), partials.numel(), _ptr(v), ldv, _ptr(record), record.numel(), _ptr(scratch),
+          need, rows, num_heads, 128, _stream(partials))
+    return record
 
 
 def attn_shard8_stats(partials, rows, num_heads, v=None, record=None):
     """This rank's statistics record from rmsnorm_rope_kstats's partials of its `rows` local k rows and, for the e4m3 P V form, its v
-    (1, rows, H*128) bf16 (a column slice is fine; None: the |v| maxima are written as 0) -> (20 * H * 128,) uint8."""
-    c = num_heads * 128
-    _dev(partials, "partials", torch.uint8)
-    record = torch.empty(attn_shard8_record_bytes(c), dtype=torch.uint8, device=partials.device) if record is None else record
-    scratch, ldv = None, 0
+    (1, rows, H*128) bf16 (a column slice is fine; None: the |v| maxima are written as 0) -> (20 * H * 128,) uint8.  A batch — partials
+    (B, bytes), v (B, rows, H*128) — gives (B, 20 * H * 128) from one launch sequence (fg_attn_shard8_stats_b)."""
+    return _shard8_stats(False, partials, rows, num_heads, v, record)
+
+
+def _shard8_quant(smooth, records, n, k, num_heads, v, k8, v8):
+    """attn_shard8_quant / attn_shard8s_quant: k (1, rows, C) with records (W, bytes), or k (B, rows, C), B > 1, with records (W, B, bytes)."""
+    who = "attn_shard8s_quant" if smooth else "attn_shard8_quant"
+    ldk = _ld_rows(k, "k")
+    b, rows, hd = k.shape
+    _dev(records, "records", torch.uint8)
+    lead = _lead(b)
+    if b < 1 or hd != num_heads * 128 or records.dim() != 2 + len(lead) or not records.is_contiguous() or (lead and records.shape[1] != b):
+        raise HipLibraryError(f"{who}: k must be (B, rows, H*128) and records (W, bytes) — (W, B, bytes) with B > 1 — got {tuple(k.shape)}, "
+                              f"{tuple(records.shape)}")
+    f8, dev = torch.float8_e4m3fn, k.device
+    k8 = torch.empty(lead + (rows, hd), dtype=f8, device=dev) if k8 is None else k8
+    sk, kbar = torch.empty(lead + (num_heads,), dtype=torch.float32, device=dev), torch.empty(lead + (hd,), dtype=torch.float32, device=dev)
+    sv = mu = None
+    ldv = 0
     if v is not None:
         ldv = _ld_rows(v, "v")
-        if v.shape != (1, rows, c):
-            raise HipLibraryError(f"attn_shard8_stats: v must be (1, {rows}, {c}), got {tuple(v.shape)}")
-        scratch = torch.empty(load().fg_attn_shard8_scratch_bytes(rows, c), dtype=torch.uint8, device=v.device)
-    _call("fg_attn_shard8_stats", _ptr(partials), partials.numel(), _ptr(v), ldv, _ptr(record), record.numel(), _ptr(scratch),
-          scratch.numel() if scratch is not None else 0, rows, num_heads, 128, _stream(partials))
-    return record
+        v8 = torch.empty(lead + (rows, hd), dtype=f8, device=dev) if v8 is None else v8
+        sv = torch.empty(lead + (num_heads, 128), dtype=torch.float32, device=dev)
+        mu = torch.empty(lead + (num_heads, 128), dtype=torch.float32, device=dev) if smooth else None
+        if v.shape != k.shape or v8.shape != lead + (rows, hd) or not v8.is_contiguous():
+            raise HipLibraryError(f"{who}: v and v8 must match k")
+    if k8.shape != lead + (rows, hd) or not k8.is_contiguous():
+        raise HipLibraryError(f"{who}: k8 must be {'(B, ' if lead else '('}rows, H*128) contiguous")
+    outs = (_ptr(k8), _ptr(v8) if v is not None else None, _ptr(sk), _ptr(kbar), _ptr(sv)) + ((_ptr(mu),) if smooth else ())
+    if lead:
+        _call(f"fg_attn_shard8{'s' if smooth else ''}_quant_b", _ptr(records), records.numel(), records.shape[0], n, _ptr(k), ldk, k.stride(0),
+              _ptr(v), ldv, v.stride(0) if v is not None else 0, *outs, b, rows, num_heads, 128, _stream(k))
+    else:
+        _call(f"fg_attn_shard8{'s' if smooth else ''}_quant", _ptr(records), records.numel(), records.shape[0], n, _ptr(k), ldk, _ptr(v), ldv,
+              *outs, rows, num_heads, 128, _stream(k))
+    return (k8, (v8 if v is not None else None), sk, kbar, sv) + ((mu,) if smooth else ())
 
 
 def attn_shard8_quant(records, n, k, num_heads, v=None, k8=None, v8=None):
     """The gathered records (W, 20 * H * 128) uint8 and the key count n of all ranks -> the scales every rank agrees on, and this rank's
     rows converted: k (1, rows, H*128) bf16 -> k8 (rows, H*128) e4m3; v likewise -> v8 ROW-MAJOR (None without v).  Returns (k8, v8, sk
-    (H), kbar (H*128), sv (H, 128) or None)."""
-    ldk = _ld_rows(k, "k")
-    b, rows, hd = k.shape
-    _dev(records, "records", torch.uint8)
-    if b != 1 or hd != num_heads * 128 or records.dim() != 2 or not records.is_contiguous():
-        raise HipLibraryError(f"attn_shard8_quant: k must be (1, rows, H*128) and records (W, 20*H*128), got {tuple(k.shape)}, {tuple(records.shape)}")
-    f8 = torch.float8_e4m3fn
-    k8 = torch.empty((rows, hd), dtype=f8, device=k.device) if k8 is None else k8
-    sk, kbar = torch.empty(num_heads, dtype=torch.float32, device=k.device), torch.empty(hd, dtype=torch.float32, device=k.device)
-    sv, ldv = None, 0
-    if v is not None:
-        ldv = _ld_rows(v, "v")
-        v8 = torch.empty((rows, hd), dtype=f8, device=k.device) if v8 is None else v8
-        sv = torch.empty((num_heads, 128), dtype=torch.float32, device=k.device)
-        if v.shape != k.shape or v8.shape != (rows, hd) or not v8.is_contiguous():
-            raise HipLibraryError("attn_shard8_quant: v and v8 must match k")
-    if k8.shape != (rows, hd) or not k8.is_contiguous():
-        raise HipLibraryError("attn_shard8_quant: k8 must be (rows, H*128) contiguous")
-    _call("fg_attn_shard8_quant", _ptr(records), records.numel(), records.shape[0], n, _ptr(k), ldk, _ptr(v), ldv, _ptr(k8),
-          _ptr(v8) if v is not None else None, _ptr(sk), _ptr(kbar), _ptr(sv), rows, num_heads, 128, _stream(k))
-    return k8, (v8 if v is not None else None), sk, kbar, sv
+    (H), kbar (H*128), sv (H, 128) or None).  A batch — k, v (B, rows, H*128), records (W, B, 20 * H * 128) — gives the five with a leading
+    B from one launch sequence (fg_attn_shard8_quant_b), every statistic per element."""
+    return _shard8_quant(False, records, n, k, num_heads, v, k8, v8)
 
 
 def attn_shard8_vt(v8, num_heads, v8t=None):
-    """The gathered v8 (N, H*128) row-major e4m3 -> v8t (H, 128, N rounded up to 64) in the tile order of PV8_KEY_ORDER, padding zero."""
+    """The gathered v8 (N, H*128) row-major e4m3 -> v8t (H, 128, N rounded up to 64) in the tile order of PV8_KEY_ORDER, padding zero.
+    A batch: v8 (B, N, H*128) with dense rows whose elements may lie further apart than N rows (a gathered slab of W * chunk rows per
+    element is read where it is) -> v8t (B, H, 128, Nkp) from one launch (fg_attn_shard8_vt_b)."""
+    if v8.dim() == 3 and v8.shape[0] > 1:
+        b, n, hd = v8.shape
+        if v8.dtype not in (torch.float8_e4m3fn, torch.uint8) or v8.device.type != "cuda" or hd != num_heads * 128 or v8.stride(2) != 1 or \
+                v8.stride(1) != hd:
+            raise HipLibraryError("attn_shard8_vt: a batch of v8 must be (B, N, H*128) e4m3 on a HIP device with dense rows")
+        shape = (b, num_heads, 128, (n + 63) // 64 * 64)
+        v8t = torch.empty(shape, dtype=torch.float8_e4m3fn, device=v8.device) if v8t is None else v8t
+        if v8t.shape != shape or not v8t.is_contiguous():
+            raise HipLibraryError(f"attn_shard8_vt: v8t must be {shape} contiguous")
+        _call("fg_attn_shard8_vt_b", _ptr(v8), v8.stride(0), _ptr(v8t), b, n, num_heads, 128, _stream(v8))
+        return v8t
     if v8.dtype not in (torch.float8_e4m3fn, torch.uint8) or v8.device.type != "cuda" or v8.dim() != 2 or not v8.is_contiguous() or \
             v8.shape[1] != num_heads * 128:
         raise HipLibraryError("attn_shard8_vt: v8 must be a contiguous (N, H*128) e4m3 tensor on a HIP device")
@@ -1227,53 +1295,33 @@ def attn_shard8s_record_bytes(c):
     return need
 
 
-def attn_shard8s_neutral_record(c, device):
-    """The record of a rank without rows (sums 0, minima +inf, maxima -inf, of k and of v) as (32 * c,) uint8 on `device`."""
+def attn_shard8s_neutral_record(c, device, batch=1):
+    """The record of a rank without rows (sums 0, minima +inf, maxima -inf, of k and of v) as (32 * c,) uint8 on `device`; batch=B > 1:
+    B of them, (B, 32 * c)."""
     rec = torch.zeros(attn_shard8s_record_bytes(c), dtype=torch.uint8)
     for at in (8 * c, 24 * c):
         rec[at:at + 4 * c].view(torch.float32).fill_(float("inf"))
         rec[at + 4 * c:at + 8 * c].view(torch.float32).fill_(float("-inf"))
-    return rec.to(device)
+    return (rec.expand(batch, -1).contiguous() if batch > 1 else rec).to(device)
 
 
 def attn_shard8s_stats(partials, rows, num_heads, v, record=None):
     """This rank's statistics record from rmsnorm_rope_kstats's partials of its `rows` local k rows and its v (1, rows, H*128) bf16 (a
-    column slice is fine) -> (32 * H * 128,) uint8: per channel the fp64 sum, the minimum and the maximum of k, then of v."""
-    c = num_heads * 128
-    _dev(partials, "partials", torch.uint8)
-    record = torch.empty(attn_shard8s_record_bytes(c), dtype=torch.uint8, device=partials.device) if record is None else record
-    ldv = _ld_rows(v, "v")
-    if v.shape != (1, rows, c):
-        raise HipLibraryError(f"attn_shard8s_stats: v must be (1, {rows}, {c}), got {tuple(v.shape)}")
-    need = load().fg_attn_shard8s_scratch_bytes(rows, c)
-    if need < 0:
-        raise HipLibraryError(f"attn_shard8s_stats: {load().fg_last_error().decode()}")
-    scratch = torch.empty(need, dtype=torch.uint8, device=v.device)
-    _call("fg_attn_shard8s_stats", _ptr(partials), partials.numel(), _ptr(v), ldv, _ptr(record), record.numel(), _ptr(scratch), scratch.numel(),
-          rows, num_heads, 128, _stream(partials))
-    return record
+    column slice is fine) -> (32 * H * 128,) uint8: per channel the fp64 sum, the minimum and the maximum of k, then of v.  A batch:
+    attn_shard8_stats's, (B, 32 * H * 128) (fg_attn_shard8s_stats_b)."""
+    if v is None:
+        raise HipLibraryError("attn_shard8s_stats: v is required (the record exists for the smoothing form)")
+    return _shard8_stats(True, partials, rows, num_heads, v, record)
 
 
 def attn_shard8s_quant(records, n, k, num_heads, v, k8=None, v8=None):
     """The gathered records (W, 32 * H * 128) uint8 and the key count n of all ranks -> the scales every rank agrees on, and this rank's
     rows converted: k (1, rows, H*128) bf16 -> k8 (rows, H*128) e4m3; v likewise -> v8 = e4m3((v - mu) / sv) ROW-MAJOR.  Returns (k8, v8,
-    sk (H), kbar (H*128), sv (H, 128), mu (H, 128)): attn_shard8_vt(v8 of all ranks), sv and mu are attention_pv8_pre(mu=)'s."""
-    ldk, ldv = _ld_rows(k, "k"), _ld_rows(v, "v")
-    b, rows, hd = k.shape
-    _dev(records, "records", torch.uint8)
-    if b != 1 or hd != num_heads * 128 or v.shape != k.shape or records.dim() != 2 or not records.is_contiguous():
-        raise HipLibraryError(f"attn_shard8s_quant: k and v must be (1, rows, H*128) and records (W, 32*H*128), got {tuple(k.shape)}, "
-                              f"{tuple(v.shape)}, {tuple(records.shape)}")
-    f8 = torch.float8_e4m3fn
-    k8 = torch.empty((rows, hd), dtype=f8, device=k.device) if k8 is None else k8
-    v8 = torch.empty((rows, hd), dtype=f8, device=k.device) if v8 is None else v8
-    if any(t.shape != (rows, hd) or not t.is_contiguous() for t in (k8, v8)):
-        raise HipLibraryError("attn_shard8s_quant: k8 and v8 must be (rows, H*128) contiguous")
-    sk, kbar = torch.empty(num_heads, dtype=torch.float32, device=k.device), torch.empty(hd, dtype=torch.float32, device=k.device)
-    sv, mu = (torch.empty((num_heads, 128), dtype=torch.float32, device=k.device) for _ in range(2))
-    _call("fg_attn_shard8s_quant", _ptr(records), records.numel(), records.shape[0], n, _ptr(k), ldk, _ptr(v), ldv, _ptr(k8), _ptr(v8), _ptr(sk),
-          _ptr(kbar), _ptr(sv), _ptr(mu), rows, num_heads, 128, _stream(k))
-    return k8, v8, sk, kbar, sv, mu
+    sk (H), kbar (H*128), sv (H, 128), mu (H, 128)): attn_shard8_vt(v8 of all ranks), sv and mu are attention_pv8_pre(mu=)'s.  A batch:
+    attn_shard8_quant's, records (W, B, 32 * H * 128) (fg_attn_shard8s_quant_b)."""
+    if v is None:
+        raise HipLibraryError("attn_shard8s_quant: v is required")
+    return _shard8_quant(True, records, n, k, num_heads, v, k8, v8)
 
 
 def attention_qk8(q, k, v, num_heads, out=None, scale=None, workspace=None, bufs=None, pv8=False, pv8_bufs=None, smooth=False):

@@ -54,6 +54,9 @@ class ModelConfig:
     # True (with stacked_cfg): the gated Linears of that stacked forward whose gate table has two rows (TI2V) run as ONE GEMM launch on
     # the rows of both branches instead of one per branch (enable_stacked_cfg(periodic_gate=True); include/fairygen_hip_gategemm.h)
     stacked_cfg_periodic_gate: bool = False
+    # True (with stacked_cfg): the stacked forward also runs on an active token shard of the K / V all-gather layout, cfg_parallel=1
+    # (enable_stacked_cfg(sharded=True); include/fairygen_hip_shard8b.h); no multi-GPU hardware run exists
+    stacked_cfg_sharded: bool = False
     clear_parameters: bool = False
 
     def check_input(self):
@@ -67,6 +70,8 @@ class ModelConfig:
             raise ValueError("ModelConfig(stacked_cfg_hot_lora=True) is a form of the stacked CFG forward: it needs stacked_cfg=True")
         if self.stacked_cfg_periodic_gate and not self.stacked_cfg:
             raise ValueError("ModelConfig(stacked_cfg_periodic_gate=True) is a form of the stacked CFG forward: it needs stacked_cfg=True")
+        if self.stacked_cfg_sharded and not self.stacked_cfg:
+            raise ValueError("ModelConfig(stacked_cfg_sharded=True) is a form of the stacked CFG forward: it needs stacked_cfg=True")
         if self.path is None and self.model_id is None:
             raise ValueError('No valid model files. Please use `ModelConfig(path="xxx")` or '
                              '`ModelConfig(model_id="xxx/yyy", origin_file_pattern="zzz")`. '
@@ -85,7 +90,7 @@ class ModelConfig:
             "offload_device", "offload_dtype", "onload_device", "onload_dtype",
             "preparing_device", "preparing_dtype", "computation_device", "computation_dtype", "attention_dtype",
             "attention_pv_dtype", "cross_attention_dtype", "attention_v_smoothing", "cross_attention_v_smoothing", "stacked_cfg",
-            "stacked_cfg_hot_lora", "stacked_cfg_periodic_gate")}
+            "stacked_cfg_hot_lora", "stacked_cfg_periodic_gate", "stacked_cfg_sharded")}
 
 
 # --------------------------------------------------------------------------------- state-dict files
@@ -277,7 +282,8 @@ class ModelPool:
                 # with an fp8 computation_dtype the config states both wishes in one place: the stacked forward in the fp8 Linear mode;
                 # stacked_cfg_hot_lora rides along: unfused adapters on the "hip" backend; stacked_cfg_periodic_gate: one gated store per pair
                 model.enable_stacked_cfg(fp8_linear=fp8, hot_lora=bool(vram_config.get("stacked_cfg_hot_lora")),
-                                         periodic_gate=bool(vram_config.get("stacked_cfg_periodic_gate")))
+                                         periodic_gate=bool(vram_config.get("stacked_cfg_periodic_gate")),
+                                         sharded=bool(vram_config.get("stacked_cfg_sharded")))
             self.model.append(model)
             self.model_name.append(cfg["model_name"])
             self.model_path.append(path)

@@ -92,9 +92,32 @@ class TokenShard:
             dist.all_gather_into_tensor(full, buf, group=self.group)
         return full
 
+    def _gather_batch(self, local, size):
+        """local (B, rows<=size, C), B > 1 (the stacked CFG forward) -> the slab (B, world*size, C): one collective per element, each into
+        its own contiguous (world*size, C) part, so element b's rows arrive in token order and nothing is permuted afterwards.  Rows
+        [:n] of every element are the tokens; the slab is the (B, N, C) operand itself when world*size == N."""
+        full = torch.empty((local.shape[0], self.world_size * size, local.shape[-1]), dtype=local.dtype, device=local.device)
+        staged = _staged(local, self.group)
+        for b in range(local.shape[0]):
+            buf = self._padded(local[b], size)
+            if staged:
+                host = torch.empty(full[b].shape, dtype=full.dtype)
+                dist.all_gather_into_tensor(host, buf.cpu(), group=self.group)
+                full[b].copy_(host)
+            else:
+                dist.all_gather_into_tensor(full[b], buf, group=self.group)
+        return full
+
+    @staticmethod
+    def tokens_of(slab, n):
+        """Rows [:n] of every element of a gathered slab as the (B, N, C) operand the batched attention takes (batch stride N * ld): the
+        slab itself when it has no padding rows, else ONE compaction copy."""
+        return slab if slab.shape[1] == n else slab[:, :n].contiguous()
+
     # ------------------------------------------------------------------ K/V all-gather exchange
     def all_gather_kv(self, k, v, n=None):
-        """k, v (1, n_local, C) of this rank's tokens -> (1, N, C) of all tokens, in token order."""
+        """k, v (1, n_local, C) of this rank's tokens -> (1, N, C) of all tokens, in token order.  (B, n_local, C) with B > 1 -> (B, N, C),
+        contiguous, per element what the B = 1 call on that element returns."""
         if not self.active:
             return k, v
         if n is None:
@@ -102,6 +125,8 @@ class TokenShard:
             dist.all_reduce(counts, group=self.group)
             n = int(counts.item())
         size = self.chunk(n)
+        if k.shape[0] > 1:
+            return self.tokens_of(self._gather_batch(k, size), n), self.tokens_of(self._gather_batch(v, size), n)
         kf = self._gather_rows(k[0], size)[:n].unsqueeze(0)
         vf = self._gather_rows(v[0], size)[:n].unsqueeze(0)
         return kf, vf
@@ -110,19 +135,26 @@ class TokenShard:
         """Start the K/V all-gather without blocking the compute stream; `.wait()` -> (k_full, v_full).
 
         The collectives run on the process group's own stream, so whatever the caller enqueues between this call
-        and wait() — in the pipeline: the other CFG branch's GEMMs / attention — overlaps the xGMI transfer."""
+        and wait() — in the pipeline: the other CFG branch's GEMMs / attention — overlaps the xGMI transfer.
+        k, v (B, n_local, C) with B > 1 (the stacked CFG forward): still ONE exchange, one collective per element and tensor into a
+        (B, world*chunk, C) slab; `.wait()` -> the views [:, :N] of the two slabs — element b's rows in token order, the elements
+        world*chunk rows apart.  A consumer that takes an element stride reads them where they are (hip.attn_shard8_vt); tokens_of()
+        makes the dense (B, N, C) the attention kernels want, a copy only when world*chunk != N."""
         return _PendingKV(self, k, v, n)
 
     def all_gather_records_async(self, record):
         """Start the all-gather of one small fixed-size record per rank (the key / value statistics of the e4m3 attention on a token shard:
         20 * C bytes, include/fairygen_hip_shard8.h); `.wait()` -> (world, record.numel()) in rank order, this rank's own included.
-        Staged through the host on a backend without device collectives, like all_gather_kv_async."""
+        Staged through the host on a backend without device collectives, like all_gather_kv_async.  record (B, bytes) with B > 1 (one
+        record per element of a stacked forward): one collective, `.wait()` -> (world, B, bytes)."""
         return _PendingRecords(self, record)
 
     def all_gather_tokens(self, x, n):
-        """x (1, n_local, C) -> (1, N, C) (final head all-gather, wan_video.py:1379-1382)."""
+        """x (1, n_local, C) -> (1, N, C) (final head all-gather, wan_video.py:1379-1382); (B, n_local, C) with B > 1 -> (B, N, C)."""
         if not self.active:
             return x
+        if x.shape[0] > 1:
+            return self.tokens_of(self._gather_batch(x, self.chunk(n)), n)
         return self._gather_rows(x[0], self.chunk(n))[:n].unsqueeze(0).contiguous()
 
     # ------------------------------------------------------------------ Ulysses (head <-> token) exchange
@@ -195,36 +227,45 @@ class TokenShard:
 class _PendingKV:
     def __init__(self, shard, k, v, n):
         self.n, self.works = n, []
+        self.batched = k.shape[0] > 1      # the stacked CFG forward: slabs (B, world*chunk, C), one collective per element
         if not shard.active:
-            self.kf, self.vf = k[0], v[0]
+            self.kf, self.vf = (k, v) if self.batched else (k[0], v[0])
             return
         size = shard.chunk(n)
         if _staged(k, shard.group):      # single-GPU rehearsal backend: synchronous, through the host
-            self.kf, self.vf = shard._gather_rows(k[0], size), shard._gather_rows(v[0], size)
+            if self.batched:
+                self.kf, self.vf = shard._gather_batch(k, size), shard._gather_batch(v, size)
+            else:
+                self.kf, self.vf = shard._gather_rows(k[0], size), shard._gather_rows(v[0], size)
             return
         bufs = []
-        for t in (k[0], v[0]):
-            buf = shard._padded(t, size)
-            full = torch.empty((shard.world_size * size, t.shape[-1]), dtype=t.dtype, device=t.device)
-            self.works.append(dist.all_gather_into_tensor(full, buf, group=shard.group, async_op=True))
-            bufs.append((full, buf))
+        for t in (k, v) if self.batched else (k[0], v[0]):
+            full = torch.empty(t.shape[:-2] + (shard.world_size * size, t.shape[-1]), dtype=t.dtype, device=t.device)
+            sends = []
+            for src, dst in zip(t, full) if self.batched else ((t, full),):
+                sends.append(shard._padded(src, size))
+                self.works.append(dist.all_gather_into_tensor(dst, sends[-1], group=shard.group, async_op=True))
+            bufs.append((full, sends))
         self._keep = bufs      # keep the send buffers alive until wait()
         self.kf, self.vf = bufs[0][0], bufs[1][0]
 
     def wait(self):
         for w in self.works:
             w.wait()
+        if self.batched:
+            return self.kf[:, : self.n], self.vf[:, : self.n]
         return self.kf[: self.n].unsqueeze(0), self.vf[: self.n].unsqueeze(0)
 
 
 class _PendingRecords:
     def __init__(self, shard, record):
         self.work, self._send = None, record.contiguous().view(-1)
+        lead = tuple(record.shape[:1]) if record.dim() == 2 and record.shape[0] > 1 else ()      # (B,): one record per element
         if not shard.active:
-            self.full = self._send.unsqueeze(0)
+            self.full = self._send.view(1, *lead, -1)
             return
         flat = torch.empty(shard.world_size * self._send.numel(), dtype=record.dtype, device=record.device)
-        self.full = flat.view(shard.world_size, -1)
+        self.full = flat.view(shard.world_size, *lead, -1)
         if _staged(record, shard.group):      # single-GPU rehearsal backend: synchronous, through the host
             host = torch.empty(flat.shape, dtype=record.dtype)
             dist.all_gather_into_tensor(host, self._send.cpu(), group=shard.group)

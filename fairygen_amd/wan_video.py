@@ -812,12 +812,15 @@ def _kv_entry(kv_cache, context):
     return kv
 
 
-def _stacked_cfg_steps(dit, latents, timestep, context, fuse_vae_embedding_in_latents, gather_output, kv_cache):
+def _stacked_cfg_steps(dit, latents, timestep, context, fuse_vae_embedding_in_latents, gather_output, kv_cache, sequence_shard=None):
     """The merged CFG call as ONE forward (WanModel.enable_stacked_cfg; checked by the caller): the time rows, the modulation and RoPE
     tables and the patch embedding are built once — they depend on the timestep, the grid and the latents only — the context is the
     batch (2, L, dim), and WanModel.forward_tokens_steps runs on the stacked residual stream.  With CFG_SHARE_PREFIX block 0's
     self-attention half is computed once on N rows (x goes in as one element); without it the whole forward is stacked.  kv_cache then
-    holds the (2, ...) cross-attention operands of the pair under the batched context tensor."""
+    holds the (2, ...) cross-attention operands of the pair under the batched context tensor.
+    sequence_shard: an active shard of the K / V all-gather layout (WanModel.enable_stacked_cfg(sharded=True)): the stacked forward runs on
+    this rank's rows, with their RoPE rows and first_rows counted from the rank's first row as in the batch-1 sharded call, and the head
+    output (2, n_local, out) is all-gathered when gather_output is set."""
     dev, dt = latents.device, latents.dtype
     ti2v = dit.seperated_timestep and fuse_vae_embedding_in_latents
     t_rows, mod_rows_t = time_embedding_rows(dit, timestep, ti2v, dev, dt)
@@ -834,7 +837,17 @@ def _stacked_cfg_steps(dit, latents, timestep, context, fuse_vae_embedding_in_la
     first_rows = h * w if ti2v else 0
     if not CFG_SHARE_PREFIX:
         x = x.expand(context.shape[0], -1, -1).contiguous()
-    out = yield from dit.forward_tokens_steps(x, ctx, mod_rows_t, t_rows, first_rows, dit.rope_tables(f, h, w, dev), kv_cache=kv)
+    cos, sin = dit.rope_tables(f, h, w, dev)
+    if sequence_shard is not None and sequence_shard.active:
+        n = f * h * w
+        lo, hi = sequence_shard.local_range(n)
+        out = yield from dit.forward_tokens_steps(x[:, lo:hi].contiguous(), ctx, mod_rows_t, t_rows, min(max(first_rows - lo, 0), hi - lo),
+                                                  (cos[lo:hi].contiguous(), sin[lo:hi].contiguous() if sin is not None else None),
+                                                  sequence_shard, n, kv_cache=kv)
+        if not gather_output:
+            return out, (f, h, w)
+        return dit.unpatchify(sequence_shard.all_gather_tokens(out, n), (f, h, w))
+    out = yield from dit.forward_tokens_steps(x, ctx, mod_rows_t, t_rows, first_rows, (cos, sin), kv_cache=kv)
     if not gather_output:
         return out, (f, h, w)
     return dit.unpatchify(out, (f, h, w))
@@ -864,7 +877,8 @@ def model_fn_wan_video_steps(dit, latents=None, timestep=None, context=None, fus
             dit.check_stacked_cfg(context.shape[0], sequence_shard, sliding_window_size is not None or sliding_window_stride is not None)
             if cfg_prefix is not None or time_rows is not None or owned is not None:
                 raise NotImplementedError("stacked_cfg: the merged call is not recorded into a graph and shares no prefix with another call")
-            return (yield from _stacked_cfg_steps(dit, latents, timestep, context, fuse_vae_embedding_in_latents, gather_output, kv_cache))
+            return (yield from _stacked_cfg_steps(dit, latents, timestep, context, fuse_vae_embedding_in_latents, gather_output, kv_cache,
+                                                  sequence_shard))
         outs = []
         # the elements differ only in their context: block 0's self-attention half is shared — between exactly two (one producer, one consumer)
         prefix = {} if (CFG_SHARE_PREFIX and sliding_window_size is None and context.shape[0] == 2) else None

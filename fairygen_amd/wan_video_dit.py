@@ -365,6 +365,13 @@ def takes_qk8_attention(model, attn, n_kv, batch):
     return bool(model.qk8_attention) and type(attn) is AttentionModule and n_kv > QK8_MIN_KV and (batch == 1 or bool(model.stacked_cfg))
 
 
+def dense_tokens(t):
+    """What an exchange of a stacked forward on a token shard hands back, (B, N, C) views of a gathered slab whose elements lie
+    world * chunk rows apart, as the operand the batched attention kernels take (batch stride N * ld): the view itself when the slab has
+    no padding rows (world * chunk == N), else one compaction copy.  One element is never copied."""
+    return t if t.shape[0] == 1 or t.stride(0) == t.shape[1] * t.stride(1) else t.contiguous()
+
+
 class _BlockAttention:
     """How the attention of the blocks runs in ONE forward, next to _BlockLinears: the forms enable_qk8_attention switched on (the model's
     flags, read once; whether a call takes them is takes_qk8_attention / takes_cross8_attention, asked once per attention), what a
@@ -468,12 +475,13 @@ class _BlockAttention:
             return a
         if e4m3:
             return (yield from self._shard8_steps(i, sa, qkv, rq, rk, scale, shard, shard_total))
-        k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
+        nb = self.lin.batch_of(qkv)      # a stacked forward on the shard (enable_stacked_cfg(sharded=True)): ONE exchange carries both elements
+        k = hip.rmsnorm_rope(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk, batch=nb)
         pending = shard.all_gather_kv_async(k, v, shard_total)
-        q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)
+        q = hip.rmsnorm_rope(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq, batch=nb)
         yield i
         k, v = pending.wait()
-        return self.attention(sa.attn, q, k, v, scale)
+        return self.attention(sa.attn, q, dense_tokens(k), dense_tokens(v), scale)
 
     def _shard8_steps(self, i, sa, qkv, rq, rk, scale, shard, shard_total):
         """Block i's self-attention in the e4m3 form on the K / V all-gather layout (enable_qk8_attention(sharded=True),
@@ -482,19 +490,24 @@ class _BlockAttention:
         pv8: v8) through all_gather_kv_async, as uint8 views.  A rank without rows launches nothing and sends the neutral record.
         With smooth_v (enable_qk8_attention(sharded="all"), include/fairygen_hip_shard8s.h) the record has 32 * C bytes — the fp64 sum,
         the minimum and the maximum of v beside those of k — every rank derives the unsharded mu and sv from them, v8 is e4m3((v - mu) / sv)
-        and the attention adds mu back; the exchanges and their sizes, the record apart, are the same."""
+        and the attention adds mu back; the exchanges and their sizes, the record apart, are the same.
+        qkv (B, n, 3 C) with B > 1 (the stacked CFG forward on the shard, enable_stacked_cfg(sharded=True)): the same two exchanges, each
+        carrying both elements — B records per rank, the (B, rows, C) bytes — and one launch sequence per step on the batched producers
+        (include/fairygen_hip_shard8b.h, include/fairygen_hip_batch8.h); every statistic is per element."""
         nh, eps, pv8 = sa.attn.num_heads, self.eps, self.pv8
         smooth = pv8 and self.smooth
         c = qkv.shape[-1] // 3
-        n_loc, dev = qkv.shape[1], qkv.device
+        nb, n_loc, dev = qkv.shape[0], qkv.shape[1], qkv.device
         v = qkv[..., 2 * c:]
         if n_loc:
             k, parts = hip.rmsnorm_rope_kstats(qkv[..., c:2 * c], sa.norm_k.weight, nh, eps, *rk)
             record = hip.attn_shard8s_stats(parts, n_loc, nh, v) if smooth else hip.attn_shard8_stats(parts, n_loc, nh, v if pv8 else None)
         else:
-            record = (hip.attn_shard8s_neutral_record if smooth else hip.attn_shard8_neutral_record)(c, dev)
+            record = (hip.attn_shard8s_neutral_record if smooth else hip.attn_shard8_neutral_record)(c, dev, nb)
         pending = shard.all_gather_records_async(record)
         yield i
+        if nb > 1:
+            return (yield from self._shard8_batch_tail(i, qkv, rq, sa, k if n_loc else None, pending, scale, shard, shard_total))
         if n_loc:
             q8, sq = hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)      # overlaps the record exchange
             if smooth:
@@ -516,6 +529,36 @@ class _BlockAttention:
             return hip.attention_pv8_pre(q8, k8f, sq, sk, hip.attn_shard8_vt(vf[0].contiguous(), nh), sv, nh, scale=scale, mu=mu)
         return hip.attention_qk8_pre(q8, k8f, sq, sk, vf, nh, scale=scale)
 
+    def _shard8_batch_tail(self, i, qkv, rq, sa, k, pending, scale, shard, shard_total):
+        """_shard8_steps behind its first exchange for B > 1 elements: the scales and this rank's e4m3 rows per element, the second
+        exchange — k8 and v (with pv8: v8) of both elements — and the batched attention.  The gathered k8 (and a bf16 v) is compacted to
+        (B, N, C) only when world * chunk != N; the gathered v8 is transposed where it lies (hip.attn_shard8_vt takes the element stride)."""
+        nh, eps, pv8 = sa.attn.num_heads, self.eps, self.pv8
+        smooth = pv8 and self.smooth
+        c = qkv.shape[-1] // 3
+        nb, n_loc, dev = qkv.shape[0], qkv.shape[1], qkv.device
+        v = qkv[..., 2 * c:]
+        if n_loc:
+            q8, sq = hip.rmsnorm_rope_q8(qkv[..., :c], sa.norm_q.weight, nh, eps, *rq)      # overlaps the record exchange
+            if smooth:
+                k8, v8, sk, _, sv, mu = hip.attn_shard8s_quant(pending.wait(), shard_total, k, nh, v)
+            else:
+                (k8, v8, sk, _, sv), mu = hip.attn_shard8_quant(pending.wait(), shard_total, k, nh, v if pv8 else None), None
+            k8, v_send = k8.view(torch.uint8), (v8.view(torch.uint8) if pv8 else v)
+        else:
+            pending.wait()
+            k8 = torch.empty((nb, 0, c), dtype=torch.uint8, device=dev)
+            v_send = k8 if pv8 else v
+        pending = shard.all_gather_kv_async(k8, v_send, shard_total)
+        yield i
+        k8f, vf = pending.wait()
+        if not n_loc:
+            return torch.empty((nb, 0, c), dtype=qkv.dtype, device=dev)
+        k8f = dense_tokens(k8f).view(torch.float8_e4m3fn)
+        if pv8:
+            return hip.attention_pv8_pre(q8, k8f, sq, sk, hip.attn_shard8_vt(vf, nh), sv, nh, scale=scale, mu=mu)
+        return hip.attention_qk8_pre(q8, k8f, sq, sk, dense_tokens(vf), nh, scale=scale)
+
     # ---- cross-attention
     def cross_attention(self, i, ca, h, ctx, kv_cache, wkv, bkv, w8):
         """Block i's cross-attention (reference :170-185) from h = norm3(x) against the context, both Acts: the q Linear and its norm,
@@ -529,7 +572,7 @@ class _BlockAttention:
         lin, nh, eps = self.lin, ca.attn.num_heads, self.eps
         rows = h.bf16 if h.bf16 is not None else h.q8[0]
         if rows.shape[-2] == 0:      # a token shard without rows: nothing to attend from, nothing is launched
-            return torch.empty((1, 0, ca.q.weight.shape[0]), dtype=ca.q.weight.dtype, device=rows.device)
+            return torch.empty((h.batch, 0, ca.q.weight.shape[0]), dtype=ca.q.weight.dtype, device=rows.device)
         q = lin.plain(h, (f"blocks.{i}.cross_attn.q",), ca.q.weight, ca.q.bias, w8[2], own=lin.own)
         e4m3 = takes_cross8_attention(self.model, ca.attn, ctx.rows, q.shape[0])
         if e4m3:
@@ -723,6 +766,8 @@ class WanModel(nn.Module):
         self.stacked_cfg_hot_lora = False
         # ... with the two-row gated stores of the pair in ONE GEMM launch (enable_stacked_cfg(periodic_gate=True)); False: one per element
         self.stacked_cfg_periodic_gate = False
+        # ... also on an active token shard of the K / V all-gather layout (enable_stacked_cfg(sharded=True)); False: an active shard raises
+        self.stacked_cfg_sharded = False
 
     # ------------------------------------------------------------------ load-time hooks
     def invalidate_fused(self):
@@ -850,7 +895,7 @@ class WanModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ the stacked CFG forward
-    def enable_stacked_cfg(self, flag=True, fp8_linear=False, hot_lora=False, periodic_gate=False):
+    def enable_stacked_cfg(self, flag=True, fp8_linear=False, hot_lora=False, periodic_gate=False, sharded=False):
         """Opt-in, off by default: a merged CFG call (cfg_merge=True: the positive and the negative context batched, wan_video.py
         model_fn_wan_video_steps) runs ONE forward on the residual stream (2, N, dim) instead of two batch-1 forwards one after the other.
         The time rows, the modulation tables and the RoPE tables are one element's and shared; the row kernels that read them take the
@@ -877,17 +922,36 @@ class WanModel(nn.Module):
         (include/fairygen_hip_gategemm.h) read the gate row by the row inside the element, rows_per_element = N — the same kernel body
         with another row rule, the same rounding points; the unit plan is that of 2 N rows, so the fp32 summation order of the tiles
         that end up as k-range pieces may differ from the per-element launches'.  Composes with fp8_linear and hot_lora (the adapter
-        launch behind the store is unchanged); stated with every call like them.  Elements below 256 rows keep the per-element launches."""
+        launch behind the store is unchanged); stated with every call like them.  Elements below 256 rows keep the per-element launches.
+        sharded: off by default, and then an active token shard raises at the merged call.  True lets the merged call on an active token
+        shard of the K / V all-gather layout (attn_mode="allgather", cfg_parallel=1) run ONE stacked forward on the rank's rows, residual
+        stream (2, n_local, dim): the local rows and RoPE rows are sliced as for a batch-1 forward, block 0's shared self-attention half
+        runs once with B = 1 exchanges, every later block's exchange carries both elements — one per block in bf16; two with the e4m3
+        modes (enable_qk8_attention(sharded=True) or sharded="all"), the statistics records then come from the batched producers of
+        include/fairygen_hip_shard8b.h — so a block has as many exchanges as in a batch-1 forward, and a rank without rows sends B neutral
+        records and no rows; the head output (2, n_local, out) is all-gathered where the caller asks.  Composes with fp8_linear and
+        periodic_gate, which are row-wise (periodic_gate: rows_per_element is n_local; below 256 rows the per-element launches stay).
+        Not carried, and refused by check_stacked_cfg on an active shard: unfused hot-loaded adapters (hot_lora) — open work, the adapter
+        launches are row-wise and expected to compose, but that has not been run or tested; and the fp8 Linear mode TOGETHER with any e4m3
+        attention form (enable_qk8_attention on, with or without pv8 / smooth_v / cross) — fp8 Linears with the full e4m3 stack measured
+        0.119 from the unsharded stacked forward against the 0.0745 bound of tests/test_stacked_cfg_sharded.py, cause not established, and
+        fp8 Linears with qk8 / pv8 alone were never run.  fp8_linear with bf16 attention and the e4m3 forms with bf16 Linears are taken
+        and tested.  attn_mode="ulysses" raises (the grouped
+        RMSNorm+RoPE destination has no batched form), and so do attn_mode="windows", cfg_parallel=2 with cfg_merge, graph=True with a
+        shard and TeaCache, as without the switch.  Stated with every call like the others.  No multi-GPU hardware run exists: the ranks
+        are emulated on one GPU (tests/test_stacked_cfg_sharded.py)."""
         self.stacked_cfg = bool(flag)
         self.stacked_cfg_fp8 = bool(flag) and bool(fp8_linear)
         self.stacked_cfg_hot_lora = bool(flag) and bool(hot_lora)
         self.stacked_cfg_periodic_gate = bool(flag) and bool(periodic_gate)
+        self.stacked_cfg_sharded = bool(flag) and bool(sharded)
         return self
 
     def check_stacked_cfg(self, context_batch, shard=None, sliding_window=False):
         """What a merged call must not meet while enable_stacked_cfg is on; decided on the host before anything is launched.  The fp8 Linear
         mode passes only with enable_stacked_cfg(fp8_linear=True), unfused adapters only on hot_backend="hip" with
-        enable_stacked_cfg(hot_lora=True); everything else raises with them as without."""
+        enable_stacked_cfg(hot_lora=True), an active token shard only on the K / V all-gather layout with enable_stacked_cfg(sharded=True);
+        everything else raises with them as without."""
         if self.fp8_dtype is not None and not self.stacked_cfg_fp8:
             raise NotImplementedError("stacked_cfg with enable_fp8_linear: the stacked forward takes the fp8 Linear mode only when it is asked "
                                       "to, enable_stacked_cfg(fp8_linear=True)")
@@ -898,8 +962,25 @@ class WanModel(nn.Module):
             raise NotImplementedError(f"stacked_cfg(hot_lora=True) with hot-loaded adapters on hot_backend={self.hot_lora_backend!r}: the stacked "
                                       "forward takes unfused adapters on hot_backend='hip' only (fg_lora_apply_bf16_b); hot_backend='fused' "
                                       "adapters are plain weights and work")
-        if shard is not None and shard.active:
+        if shard is not None and shard.active and not self.stacked_cfg_sharded:
             raise NotImplementedError("stacked_cfg with an active token shard: the stacked forward has no exchange")
+        if shard is not None and shard.active and self.hot_loras:
+            raise NotImplementedError("stacked_cfg(sharded=True) with unfused hot-loaded adapters: open work, not a limit of the kernels — the "
+                                      "adapter launches are row-wise and are expected to compose, but the stacked forward has not been run or "
+                                      "tested with adapters on token shards; hot_backend='fused' adapters are plain weights and work")
+        if shard is not None and shard.active and self.fp8_dtype is not None and self.qk8_attention:
+            raise NotImplementedError("stacked_cfg(sharded=True) with enable_fp8_linear AND enable_qk8_attention: the fp8 Linears together with "
+                                      "an e4m3 attention form are not carried on token shards — with the full e4m3 stack the stacked forward "
+                                      "on emulated ranks was 0.119 from the unsharded stacked forward against a bound of 0.0745, cause not "
+                                      "established; run the shard with one of the two (fp8 Linears with bf16 attention, or e4m3 attention "
+                                      "with bf16 Linears)")
+        if shard is not None and shard.active and shard.attn_mode == "ulysses":
+            raise NotImplementedError("stacked_cfg(sharded=True) with attn_mode='ulysses': the grouped RMSNorm+RoPE destination of the all-to-all "
+                                      "send buffer has no batched form; the stacked forward runs on the K / V all-gather layout "
+                                      "(attn_mode='allgather')")
+        if shard is not None and shard.active and shard.attn_mode != "allgather":
+            raise NotImplementedError(f"stacked_cfg(sharded=True) with attn_mode={shard.attn_mode!r}: windows are not part of the batch; the "
+                                      "stacked forward runs on the K / V all-gather layout (attn_mode='allgather')")
         if sliding_window:
             raise NotImplementedError("stacked_cfg with sliding windows: windows are not part of the batch")
         if context_batch != 2:
@@ -1108,14 +1189,16 @@ class WanModel(nn.Module):
         x = x.view(b, f, h, w, px, py, pz, self.out_dim).permute(0, 7, 1, 4, 2, 5, 3, 6)
         return x.reshape(b, self.out_dim, f * px, h * py, w * pz)
 
-    def _empty_rank_steps(self, x, blocks, shard, shard_total, att, cfg_prefix):
+    def _empty_rank_steps(self, x, blocks, shard, shard_total, att, cfg_prefix, nb=1):
         """The forward of a rank of the K / V all-gather layout that holds no token rows (the ceil split leaves trailing ranks empty when
         N is small against the world): it launches nothing, takes its part in every exchange of every block — the neutral statistics
         record and no k8 / v rows in the e4m3 form, no k / v rows in bf16 — in the order the other ranks run them, cfg_prefix included,
-        and returns an empty head output (1, 0, out)."""
+        and returns an empty head output (1, 0, out).  nb > 1 (the stacked CFG forward on the shard): the exchanges carry nb elements —
+        nb neutral records, no rows — except block 0's when x is one element (its shared self-attention half runs with B = 1 exchanges
+        on every rank); the head output is (nb, 0, out)."""
         c = self.dim
-        qkv = x.new_empty((1, 0, 3 * c))
         for i, blk in enumerate(blocks):
+            qkv = x.new_empty((x.shape[0] if i == 0 else nb, 0, 3 * c))
             if cfg_prefix is not None and i == 0:
                 if "owner" in cfg_prefix:      # the other branch of the step runs block 0's exchanges
                     while "x_sa" not in cfg_prefix:
@@ -1132,7 +1215,7 @@ class WanModel(nn.Module):
                 pending.wait()
             if cfg_prefix is not None and i == 0:
                 cfg_prefix["x_sa"] = x
-        return x.new_empty((1, 0, self.head.head.weight.shape[0]))
+        return x.new_empty((nb, 0, self.head.head.weight.shape[0]))
 
     def _self_attention_steps(self, i, blk, mod, x, h, cos, sin, shard, shard_total, lin, att, w8, norm3=True):
         """Block i's self-attention half (reference :139-146, :225-226): h = modulate(norm1(x)) in (an Act); returns the residual stream
@@ -1189,15 +1272,18 @@ class WanModel(nn.Module):
         owned: the scheduler block and scratch of a caller that records this forward into a graph (_BlockLinears.owned; same bits).
         The stacked CFG forward (enable_stacked_cfg): context (2, L, dim), everything else ONE element's.  x (1, n, dim): block 0's
         self-attention half, which does not see the context, is computed once on n rows and copied into both halves of the (2, n, dim)
-        residual stream; x (2, n, dim): that half runs stacked as well.  Returns the head output (2, n, out)."""
+        residual stream; x (2, n, dim): that half runs stacked as well.  Returns the head output (2, n, out).  With
+        enable_stacked_cfg(sharded=True) and an active shard of the K / V all-gather layout, x is the rank's rows and every exchange of a
+        stacked block carries both elements (_BlockAttention.self_attention_steps)."""
         eps = self.eps
         cos, sin = rope
         x = x.contiguous()
         nb = context.shape[0]
-        if nb > 1 and (not self.stacked_cfg or x.shape[0] not in (1, nb) or tea_cache is not None or (shard is not None and shard.active)
-                       or cfg_prefix is not None or owned is not None):
-            raise ValueError("forward_tokens_steps: a context batch is the stacked CFG forward (enable_stacked_cfg): unsharded, no TeaCache, "
-                             "no cfg_prefix, not recorded")
+        sharded = shard is not None and shard.active
+        if nb > 1 and (not self.stacked_cfg or x.shape[0] not in (1, nb) or tea_cache is not None or cfg_prefix is not None or owned is not None
+                       or (sharded and not (self.stacked_cfg_sharded and shard.attn_mode == "allgather"))):
+            raise ValueError("forward_tokens_steps: a context batch is the stacked CFG forward (enable_stacked_cfg): unsharded — or, with "
+                             "enable_stacked_cfg(sharded=True), on the K / V all-gather layout — no TeaCache, no cfg_prefix, not recorded")
         blocks = list(self.blocks)
         if skip_blocks:
             blocks, x = [], tea_cache.update(x)
@@ -1206,7 +1292,7 @@ class WanModel(nn.Module):
         lin = _BlockLinears(self, mod_rows_t.shape[0], owned)      # the mode decisions of this forward: the Linears and norms,
         att = _BlockAttention(self, lin, owned)                    # and attention
         if x.shape[1] == 0 and tea_cache is None and shard is not None and shard.active and shard.attn_mode == "allgather":
-            return (yield from self._empty_rank_steps(x, blocks, shard, shard_total, att, cfg_prefix))
+            return (yield from self._empty_rank_steps(x, blocks, shard, shard_total, att, cfg_prefix, nb))
         ctx = Act(context, hip.fp8_quant_rows(context) if fp8 is not None else None)      # the text context is the same for all blocks
         mods = [hip.ModTable((blk.modulation.to(mod_rows_t.dtype) + mod_rows_t).contiguous(), first_rows) for blk in blocks]
         h = lin.modulate(x, mods[0], 0, 1) if blocks else None
